@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: frames/sec of CogVideoX-5B-I2V 49-frame x 50-step ALG sampling (BASELINE.json config 2).
 
-    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5] [--cfg-split]
+    python bench.py --gpus N --steps K --warmup W [--workload c2|c3|c4|c5] [--cfg-split] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step (--dump-outputs) and prints the
+JSON line.  Everything else the bench measures -- the HIP-event roofline of the timed region, the box calibration, the A/B
+arms, the filter / VAE micro-benchmarks, the C3 / C4 / C5 legs, the CPU baseline, the multi-rank launch record -- runs
+with --full only (its --no-* options still switch single legs off there).
 
 Invoked plainly with N > 1 it launches its own ranks (re-exec through torch.distributed.run, one process per GPU,
 rendezvous on 127.0.0.1); invoked BY torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
@@ -20,7 +25,7 @@ the workload over different seeds (weak scaling); rank 0 materialises the weight
 there is no per-step collective (``--cfg-split``: the cond / uncond passes of one video on a GPU pair, one all-gather
 per step).
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      -- the dominant kernel (flash attention): algorithmic FLOPs per launch / mean launch duration, timed
                    with HIP events on the launch stream inside the timed region; `extra` holds the same for the GEMMs
                    and the HBM GB/s of the filter and step kernels.
@@ -822,10 +827,11 @@ def private_loop_crosscheck(wl, k_steps):
     return (time.perf_counter() - t0) / k_steps * 1e3
 
 
-def timed_region(wl, warmup, steps, parallel, measure_box=False):
+def timed_region(wl, warmup, steps, parallel, measure_box=False, events=True):
     """W untimed warm-up steps, then EXACTLY `steps` steps between barrier + synchronize on both sides; HIP-event brackets of the
-    kernel families live only inside the timed region (their cost is measured by the `events` arm of --ab).  Returns (elapsed
-    seconds = max over ranks, sample-forwards of this rank, per-family event times in ms).  measure_box: the attention
+    kernel families live only inside the timed region (their cost is measured by the `events` arm of --ab; events=False: none,
+    the plain bench line).  Returns (elapsed seconds = max over ranks, sample-forwards of this rank, per-family event times in
+    ms).  measure_box: the attention
     kernel's own clock taps are switched on (two scalar counter reads in every 64th workgroup; results unaffected) and a
     background thread samples package power / sclk for the length of the region -> wl.box."""
     from alg_amd import _lib
@@ -834,7 +840,8 @@ def timed_region(wl, warmup, steps, parallel, measure_box=False):
     wl.warmup_passes = list(wl.step_passes)
     kinds = {}  # kernel family -> list of event pairs
     wl.step_passes = []
-    wl.instrument(kinds)
+    if events:
+        wl.instrument(kinds)
     taps = smi = None
     try:
         # the tap is a raw device pointer inside the library: whatever happens in the region, it is taken out again before
@@ -855,7 +862,8 @@ def timed_region(wl, warmup, steps, parallel, measure_box=False):
     finally:
         if smi is not None:
             smi.__exit__(None, None, None)
-        wl.instrument(None)
+        if events:
+            wl.instrument(None)
         if measure_box:
             _lib.attn_clock_tap(None)
             torch.cuda.synchronize()
@@ -1116,34 +1124,60 @@ def self_launch(args):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c2",
                     help="c2 = the metric's configuration (default); c3 / c4 / c5 = the other BASELINE configs as bench lines")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: HIP-event roofline of the timed region, box calibration, A/B arms, "
+                         "filter / VAE micro-benchmarks, the c3 / c4 / c5 legs, the CPU baseline, the multi-rank launch record")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned (rank 0's pipeline output latents) "
+                         "as DIR/latents.npy, float32")
     ap.add_argument("--layers", type=int, default=0, help="debug only: fewer layers invalidates the metric")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-c1", action="store_true", help="skip the timed C1 __call__ leg of the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-c1", action="store_true", help="--full: skip the timed C1 __call__ leg of the CPU baseline")
     ap.add_argument("--seed-offset", type=int, default=0, help="debug: added to every rank's video seed")
     ap.add_argument("--dump-latents", default="", metavar="PREFIX",
                     help="debug: every rank saves the final latents of its last __call__ to PREFIX.rank<r>.pt")
-    ap.add_argument("--no-calibration", action="store_true", help="skip the 3 s matrix-pipe calibration of the box")
+    ap.add_argument("--no-calibration", action="store_true", help="--full: skip the 3 s matrix-pipe calibration of the box")
     ap.add_argument("--ab", action="store_true", help="in-run A/B arms (roofline.extra.ab; workloads.*.ab_attn128_q64_statement): ON by "
-                                                      "default for c2 at 1 GPU -- the flag exists so that a command line can say so")
-    ap.add_argument("--no-ab", action="store_true", help="c2 at 1 GPU: skip the in-run A/B arms (roofline.extra.ab, ~40 s)")
+                                                      "default for c2 at 1 GPU with --full -- the flag exists so that a command line can say so")
+    ap.add_argument("--no-ab", action="store_true", help="--full, c2 at 1 GPU: skip the in-run A/B arms (roofline.extra.ab, ~40 s)")
     ap.add_argument("--c1-budget", type=float, default=150.0,
                     help="seconds the C1 CPU leg may take (a 2-layer probe projects it first; beyond the budget the projection is reported)")
     ap.add_argument("--cfg-split", action="store_true",
                     help="opt-in: cond/uncond CFG passes of one video on a pair of GPUs (latency mode, one all-gather per step)")
-    ap.add_argument("--cross-check", action="store_true", help="c2: also time round 1's bench-private loop")
+    ap.add_argument("--cross-check", action="store_true", help="--full, c2: also time round 1's bench-private loop")
     ap.add_argument("--filters-only", action="store_true", help="debug: only the low-pass kernel micro-benchmark")
     ap.add_argument("--set", action="append", default=[], metavar="ATTR=VALUE",
                     help="A/B runs: set an attribute of the transformer (e.g. pair_qkv=0, attn_prescale=0) before the warm-up")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="c2 at 1 GPU: skip the c3 / c4 / c5 legs (2 timed full-depth steps each, ~3 min) that ride behind the headline")
-    args = ap.parse_args()
+                    help="--full, c2 at 1 GPU: skip the c3 / c4 / c5 legs (2 timed full-depth steps each, ~3 min) that ride behind the headline")
+    return ap.parse_args(argv)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float32 (bf16 widens exactly), so that two builds can be compared output
+    for output on the same seeded inputs."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def main():
+    args = parse_args()
     if args.filters_only:
         print(json.dumps(filter_microbench(torch.device("cuda:0"))))
         return
@@ -1181,9 +1215,11 @@ def main():
         if not hasattr(wl.model, k):
             raise SystemExit("--set: the transformer has no attribute %r" % k)
         setattr(wl.model, k, coerce_like(getattr(wl.model, k), v_, k))
-    elapsed, forwards, ms = timed_region(wl, args.warmup, args.steps, parallel, measure_box=(world == 1))
+    # a plain run times the steps alone; the HIP-event brackets and the box taps of the roofline ride along with --full only
+    elapsed, forwards, ms = timed_region(wl, args.warmup, args.steps, parallel, measure_box=(args.full and world == 1),
+                                         events=args.full)
     calibration = None
-    if rank == 0 and world == 1 and not args.no_calibration:
+    if args.full and rank == 0 and world == 1 and not args.no_calibration:
         try:
             calibration = calibrate_box(dev)      # right BEHIND the timed region: the chip in the thermal state the headline ran in
         except Exception as e:                    # an auxiliary leg must never take the headline line down
@@ -1191,9 +1227,10 @@ def main():
 
     if args.dump_latents:
         torch.save(wl.last_out.detach().cpu(), "%s.rank%d.pt" % (args.dump_latents, rank))
+    if args.dump_outputs and rank == 0:          # before the --full legs below run the pipeline again
+        dump_outputs(args.dump_outputs, {"latents": wl.last_out})
     n_videos_parallel = world // 2 if split else world
     value = wl.frames * args.steps / wl.steps_per_video * n_videos_parallel / elapsed
-    roofline = wl.roofline(ms, forwards, elapsed)
 
     cfgd = wl.config(forwards)
     cfgd["parallelism"] = ("cfgpair2xdp%d" % (world // 2)) if split else ("dp%d" % world)
@@ -1203,9 +1240,11 @@ def main():
         "metric": wl.metric, "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": wl.dtype, "data": wl.data, "config": cfgd, "seconds": elapsed,
-        "finite": bool(torch.isfinite(wl.last_out.float()).all().item()), "roofline": roofline,
+        "finite": bool(torch.isfinite(wl.last_out.float()).all().item()),
     }
-    if world > 1 or parallel.FORCE_COLLECTIVES:
+    if args.full:
+        out["roofline"] = wl.roofline(ms, forwards, elapsed)
+    if args.full and (world > 1 or parallel.FORCE_COLLECTIVES):
         # proof that N ranks sat on N distinct GPUs, and what the ONE collective of the data-parallel path cost (start-up only);
         # ALG_DIST_FORCE=1 runs the same collectives on a one-rank group (the one-GPU rehearsal of the RCCL path)
         out["dist_backend"] = torch.distributed.get_backend()
@@ -1228,7 +1267,7 @@ def main():
             out["roofline"]["extra"]["attn_pipe_busy_at_its_clock"] = out["roofline"]["achieved"] / (cus * 4 * 1024.0 * clk["mean"] * 1e6 / 1e12)
         if calibration is not None and calibration.get("mfma_sustained_random_operands_tflops") and out["roofline"].get("achieved"):
             out["roofline"]["extra"]["attn_frac_of_box_sustained_mfma"] = out["roofline"]["achieved"] / calibration["mfma_sustained_random_operands_tflops"]
-    if rank == 0 and world == 1 and args.workload == "c2" and not args.no_ab and not args.layers and not args.set:
+    if args.full and rank == 0 and world == 1 and args.workload == "c2" and not args.no_ab and not args.layers and not args.set:
         try:
             out["roofline"]["extra"]["ab"] = ab_arms(wl, AB_ARMS)
         except Exception as e:
@@ -1237,19 +1276,19 @@ def main():
         out["config"]["overrides"] = args.set
     if args.layers:
         out["INVALID"] = "debug run with %d layers" % args.layers
-    if rank == 0 and world == 1 and args.workload == "c2":
+    if args.full and rank == 0 and world == 1 and args.workload == "c2":
         if args.cross_check:
             out["roofline"]["extra"]["private_loop_ms_per_step"] = private_loop_crosscheck(wl, args.steps)
         out["roofline"]["extra"]["filters"] = filter_microbench(dev)
         out["roofline"]["extra"]["vae_decode"] = vae_decode_microbench(dev, wl.latents0,
                                                                        elapsed / args.steps * wl.steps_per_video)
-    if rank == 0 and world == 1 and args.workload == "c2" and not args.no_other_workloads and not args.layers:
+    if args.full and rank == 0 and world == 1 and args.workload == "c2" and not args.no_other_workloads and not args.layers:
         import gc
         wl.model = wl.pipe = wl.sched = wl.last_out = None
         gc.collect()
         torch.cuda.empty_cache()
         out["roofline"]["extra"]["workloads"] = other_workloads(args, dev, parallel)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(with_c1=not args.no_c1, c1_budget=args.c1_budget)
     if rank == 0:
         print(json.dumps(out))

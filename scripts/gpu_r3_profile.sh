@@ -14,10 +14,10 @@ for ctrs in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_SALU
 done
 python $R/scripts/pmc_summary.py $P > $O/r3_pmc_summary.txt 2>&1
 rm -rf $P/kb_p[0-9]
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd3 -o r3 -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/profd3_bench.json 2> $O/profd3.err
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd3 -o r3 -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/profd3_bench.json 2> $O/profd3.err
 echo "profdefault exit $?"
 find $O/profd3 -name "*kernel_trace*" -delete
 cp $(find $O/profd3 -name "*kernel_stats*" | head -1) $O/r3_bench_default_kernel_stats.csv
 cd $R
-timeout 900 python bench.py --steps 20 --warmup 5 > $O/r3_bench_driver_steps20.json 2> $O/r3_bench.err; echo "bench exit $?"
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/r3_bench_driver_steps20.json 2> $O/r3_bench.err; echo "bench exit $?"
 tail -c 600 $O/r3_bench_driver_steps20.json; head -12 $O/r3_bench_default_kernel_stats.csv | cut -c1-150; grep -c mean $O/r3_pmc_summary.txt

@@ -12,11 +12,11 @@ for w in ${@:-gemmtests bench prof}; do
       cat $O/${TAG}_gemm_tests.log ;;
     bench)
       cd $R
-      timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_steps20.json 2> $O/${TAG}_bench.err; echo "bench exit $?"
+      timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_steps20.json 2> $O/${TAG}_bench.err; echo "bench exit $?"
       tail -c 1500 $O/${TAG}_bench_driver_steps20.json; tail -3 $O/${TAG}_bench.err ;;
     prof)
       cd /tmp
-      timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd4 -o $TAG -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-other-workloads > $O/${TAG}_bench_default_under_rocprof.json 2> $O/profd4.err
+      timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd4 -o $TAG -- python $R/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-other-workloads > $O/${TAG}_bench_default_under_rocprof.json 2> $O/profd4.err
       echo "prof exit $?"
       find $O/profd4 -name "*kernel_trace*" -delete
       cp $(find $O/profd4 -name "*kernel_stats*" | head -1) $O/${TAG}_bench_default_kernel_stats.csv
@@ -78,7 +78,7 @@ PY
     workloads)
       cd $R
       for wl in c3 c4 c5; do
-        timeout 900 python bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench_workload_$wl.json 2>> $O/${TAG}_bench.err; echo "$wl exit $?"
+        timeout 900 python bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline > $O/${TAG}_bench_workload_$wl.json 2>> $O/${TAG}_bench.err; echo "$wl exit $?"
       done ;;
   esac
 done

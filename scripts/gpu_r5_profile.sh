@@ -11,11 +11,11 @@ for w in ${@:-bench prof}; do
       tail -4 $O/${TAG}_pytest_gpu_full.txt ;;
     bench)
       cd $R
-      timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_steps20.json 2> $O/${TAG}_bench.err; echo "bench exit $?"
+      timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${TAG}_bench_driver_steps20.json 2> $O/${TAG}_bench.err; echo "bench exit $?"
       tail -c 600 $O/${TAG}_bench_driver_steps20.json; tail -3 $O/${TAG}_bench.err ;;
     prof)
       cd /tmp
-      timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd5 -o $TAG -- python $R/bench.py --steps 6 --warmup 3 --no-cpu-baseline --no-other-workloads --no-ab --no-calibration > $O/${TAG}_bench_default_under_rocprof.json 2> $O/profd5.err
+      timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd5 -o $TAG -- python $R/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --no-other-workloads --no-ab --no-calibration > $O/${TAG}_bench_default_under_rocprof.json 2> $O/profd5.err
       echo "prof exit $?"
       python $R/scripts/rocprof_timed_region.py $(find $O/profd5 -name "*kernel_trace*" | head -1) $O/${TAG}_bench_default_under_rocprof.json > $O/${TAG}_bench_default_rocprof_vs_events.json 2>&1
       cat $O/${TAG}_bench_default_rocprof_vs_events.json
@@ -26,7 +26,7 @@ for w in ${@:-bench prof}; do
     profwl)
       cd /tmp
       for wl in c3 c4 c5; do
-        timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd5 -o $TAG -- python $R/bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-ab --no-calibration > $O/${TAG}_bench_${wl}_under_rocprof.json 2> $O/profd5.err
+        timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/profd5 -o $TAG -- python $R/bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-ab --no-calibration > $O/${TAG}_bench_${wl}_under_rocprof.json 2> $O/profd5.err
         echo "prof $wl exit $?"
         find $O/profd5 -name "*kernel_trace*" -delete
         cp $(find $O/profd5 -name "*kernel_stats*" | head -1) $O/${TAG}_bench_${wl}_kernel_stats.csv

@@ -12,7 +12,7 @@ i=0
 for ctrs in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" \
             "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_INSTS_VALU GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  (cd $R && timeout 600 rocprofv3 --pmc $ctrs --output-format csv -d $B/bench_p$i -o p -- python bench.py --gpus 1 --steps 4 --warmup 1 --no-ab --no-other-workloads --no-cpu-baseline --no-calibration > $B/bench_p$i.json 2> $B/bench_p$i.err)
+  (cd $R && timeout 600 rocprofv3 --pmc $ctrs --output-format csv -d $B/bench_p$i -o p -- python bench.py --full --gpus 1 --steps 4 --warmup 1 --no-ab --no-other-workloads --no-cpu-baseline --no-calibration > $B/bench_p$i.json 2> $B/bench_p$i.err)
 done
 PMC_BY_GRID=1 python $R/scripts/pmc_summary.py $B > $O/r6_pmc_bench_run.txt 2>&1
 F=$O/filters; rm -rf $F; mkdir -p $F

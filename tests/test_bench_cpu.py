@@ -1,5 +1,6 @@
 """Host-side pieces of bench.py that can be checked without a GPU: the --set coercion ('pair_qkv=false' used to be
-stored as a truthy string), the power / clock sampler degrading to "no reading" instead of raising, the A/B arm table."""
+stored as a truthy string), the power / clock sampler degrading to "no reading" instead of raising, the A/B arm table, the plain /
+--full command line and the --dump-outputs writer."""
 import os
 import sys
 
@@ -71,3 +72,23 @@ def test_whole_video_projection_counts_the_schedules_passes():
         assert (n3, n2, n1) == {"c3": (20, 20, 0), "c5": (10, 40, 0), "c4": (0, 0, 50)}[name]
         if n2:                                                               # (c4 has no 2-pass step: the per-forward formula stands)
             assert abs(out["seconds_per_video"] - (n3 * 3.0 + n2 * 2.5)) < 1e-9 and "MEASURED" in out["what"]
+
+
+def test_a_plain_command_line_is_lean_and_full_is_opt_in():
+    args = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 2, False, "")
+    args = bench.parse_args(["--steps", "3", "--full", "--dump-outputs", "some/dir"])
+    assert args.full and args.dump_outputs == "some/dir" and args.steps == 3
+
+
+def test_dump_outputs_writes_float32_npy_within_the_size_limit(tmp_path):
+    import numpy as np
+    import torch
+    x = torch.randn(2, 3, 5, generator=torch.Generator().manual_seed(0)).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "out"), {"latents": x})
+    y = np.load(tmp_path / "out" / "latents.npy")
+    assert y.dtype == np.float32 and np.array_equal(y, x.float().numpy())
+    big = torch.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, dtype=torch.bfloat16)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"latents": big})
+    assert not (tmp_path / "big").exists()

@@ -10,12 +10,13 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "2", "--warmup", "3", "--layers", "1", "--no-cpu-baseline", "--no-calibration", "--no-other-workloads", "--no-ab"]
+COMMON = ["--full", "--steps", "2", "--warmup", "3", "--layers", "1", "--no-cpu-baseline", "--no-calibration", "--no-other-workloads", "--no-ab"]
 
 
 def _run(cmd, env, timeout=900):
@@ -42,9 +43,11 @@ def test_two_ranks_through_the_drivers_launch_line(tmp_path):
     solo_env = {k: v for k, v in env.items() if k not in ("ALG_DIST_BACKEND", "ALG_DIST_ONE_GPU")}
     for rank in (0, 1):
         one = _run([sys.executable, "bench.py", "--gpus", "1", "--seed-offset", str(rank), "--dump-latents",
-                    str(tmp_path / ("solo%d" % rank)), *COMMON], solo_env)
+                    str(tmp_path / ("solo%d" % rank)), "--dump-outputs", str(tmp_path / ("out%d" % rank)), *COMMON], solo_env)
         assert one["n_gpus"] == 1 and "ranks_seen" not in one
         a = torch.load(tmp_path / ("dp.rank%d.pt" % rank))
         b = torch.load(tmp_path / ("solo%d.rank0.pt" % rank))
         assert a.shape == (1, 13, 16, 60, 90) and torch.equal(a, b), rank
+        dumped = np.load(tmp_path / ("out%d" % rank) / "latents.npy")      # --dump-outputs: the same latents, widened to float32
+        assert dumped.dtype == np.float32 and np.array_equal(dumped, b.float().numpy()), rank
     assert not torch.equal(torch.load(tmp_path / "dp.rank0.pt"), torch.load(tmp_path / "dp.rank1.pt"))   # different videos

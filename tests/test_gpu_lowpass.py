@@ -1,8 +1,5 @@
 """GPU parity of the low-pass kernels (through the C ABI via alg_amd.lp_utils) against the CPU oracle,
 the reference-generated golden vectors, and ATen's own GPU op (the op the reference calls, lp_utils.py:53-54)."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
@@ -10,6 +7,7 @@ import torch.nn.functional as F
 
 import alg_amd
 from alg_amd import lp_utils
+from helpers.golden import down_up_cases
 from oracle import lp_oracle
 
 pytestmark = pytest.mark.gpu
@@ -20,14 +18,11 @@ def bf16_ulp(x):
 
 
 def test_down_up_f32_golden_vectors(device, golden_dir):
-    with open(os.path.join(golden_dir, "lp_misc.json")) as f:
-        meta = json.load(f)["down_up_meta"]
-    vec = np.load(os.path.join(golden_dir, "down_up_vectors.npz"))
-    for m in meta:
-        x = torch.from_numpy(vec[m["name"] + "_in"]).to(device)
+    for m, x_in, ref in down_up_cases(golden_dir):
+        x = torch.from_numpy(x_in).to(device)
         y = lp_utils.apply_low_pass_filter(x, "down_up", 0.0, 0, m["factor"])
         assert y is not x and y.shape == x.shape and y.dtype == x.dtype
-        err = np.abs(y.cpu().numpy() - vec[m["name"] + "_out"]).max()
+        err = np.abs(y.cpu().numpy() - ref).max()
         assert err <= 3e-6, (m["name"], err)  # fp32 rounding (fma vs mul+add ordering)
 
 
@@ -36,13 +31,10 @@ def test_register_blocked_kernels_against_golden_vectors_and_oracle(device, gold
     reference-generated golden vectors (small plane counts) and the oracle cases run through it directly, not only through
     its bit-identity with the plane-per-workgroup kernels."""
     monkeypatch.setenv("ALG_LOWPASS_PATH", "3")      # lowpass_v3.hip at any plane count
-    with open(os.path.join(golden_dir, "lp_misc.json")) as f:
-        meta = json.load(f)["down_up_meta"]
-    vec = np.load(os.path.join(golden_dir, "down_up_vectors.npz"))
-    for m in meta:
-        x = torch.from_numpy(vec[m["name"] + "_in"]).to(device)
+    for m, x_in, ref in down_up_cases(golden_dir):
+        x = torch.from_numpy(x_in).to(device)
         y = lp_utils.apply_low_pass_filter(x, "down_up", 0.0, 0, m["factor"])
-        err = np.abs(y.cpu().numpy() - vec[m["name"] + "_out"]).max()
+        err = np.abs(y.cpu().numpy() - ref).max()
         assert err <= 3e-6, (m["name"], err)
     g = torch.Generator().manual_seed(7)
     for shape, factor in (((1, 16, 13, 60, 90), 0.25), ((1, 20, 21, 60, 104), 0.4), ((1, 16, 1, 90, 160), 0.625),

@@ -119,7 +119,7 @@ def test_bench_line_of_a_forced_one_rank_rccl_run_carries_rccl_version():
     """bench.py end to end on the RCCL backend: the driver's launch line with ONE rank, collectives forced on."""
     env = dict(os.environ, ALG_DIST_FORCE="1", ALG_DIST_BACKEND="nccl", HSA_ENABLE_IPC_MODE_LEGACY="0", PYTHONPATH=ROOT)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "3", "--layers", "1",
+           "--master-port", str(_free_port()), "bench.py", "--full", "--gpus", "1", "--steps", "2", "--warmup", "3", "--layers", "1",
            "--no-cpu-baseline", "--no-calibration", "--no-other-workloads", "--no-ab"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])

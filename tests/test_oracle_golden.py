@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+from helpers.golden import down_up_cases
 from oracle import lp_oracle
 
 
@@ -43,11 +44,9 @@ def test_active_step_tables(golden_dir):
 
 
 def test_down_up_against_reference_vectors(golden_dir):
-    misc = _load(golden_dir, "lp_misc.json")
-    vec = np.load(os.path.join(golden_dir, "down_up_vectors.npz"))
-    assert len(misc["down_up_meta"]) >= 10
-    for m in misc["down_up_meta"]:
-        x, ref = vec[m["name"] + "_in"], vec[m["name"] + "_out"]
+    cases = down_up_cases(golden_dir)
+    assert len(cases) >= 10
+    for m, x, ref in cases:
         assert lp_oracle.down_up_size(x.shape[-2], x.shape[-1], m["factor"]) == (m["h1"], m["w1"])
         # float32 tap arithmetic (what ATen does for float tensors): agreement to fp32 rounding
         got32 = lp_oracle.down_up(x, m["factor"], np.float32)
@@ -58,8 +57,7 @@ def test_down_up_against_reference_vectors(golden_dir):
 
 
 def test_5d_equals_per_plane(golden_dir):
-    vec = np.load(os.path.join(golden_dir, "down_up_vectors.npz"))
-    x, ref = vec["c1_5d_in"], vec["c1_5d_out"]
+    (x, ref), = [(x, ref) for m, x, ref in down_up_cases(golden_dir) if m["name"] == "c1_5d"]
     got = lp_oracle.apply_low_pass_filter(x, "down_up", 0.0, 0, 0.25, ftype=np.float32)
     assert got.shape == x.shape and np.abs(got - ref).max() <= 1e-6
 
