@@ -731,6 +731,8 @@ def gemm_args(A, B, C, M, N, K, lda, ldb, ldc, bias=None, R=None, ldr=0, gate=No
     args = GemmArgs()
     fp8 = a_scale is not None
     if isinstance(B, PackedB):
+        if fp8:
+            raise AlgHipError("a packed B holds bf16 weight fragments for GEMM schedule 11: the e4m3 GEMM takes a row-major B")
         if (B.N, B.K) != (N, K) or b_off or strideB:
             raise AlgHipError("packed B was built for N = %d, K = %d (shared by the batch, no offset)" % (B.N, B.K))
         flags |= GEMM_B_PACKED11
@@ -791,7 +793,9 @@ def gemm(*a, **kw):
 
 def gemm_pair(first, second):
     """Two independent plain bf16 GEMMs -- each a (args, kwargs) pair of `gemm` -- as one persistent launch
-    (alg_gemm_bf16_pair); bit-identical to the two separate calls."""
+    (alg_gemm_bf16_pair); bit-identical to the two separate calls.  A problem whose B is a PackedB is not taken into the
+    persistent launch: the pair then runs as the two `gemm` calls (the packed one on schedule 11).  Both problems are
+    checked before either is launched."""
     lib = load_library()
     a, fa = gemm_args(*first[0], **first[1])
     b, fb = gemm_args(*second[0], **second[1])
@@ -802,7 +806,8 @@ def gemm_pair(first, second):
 
 def gemm_pair_qk(first, second, wq, bq, wk, bk, cos, sin, heads, text_len, eps, q_scale=1.0):
     """`gemm_pair` whose FIRST problem is the CogVideoX Q|K projection, with the per-head LayerNorm + rotary embedding of
-    `qk_norm_rope_` applied in its store loop (alg_gemm_bf16_pair_qk); bit-identical to gemm_pair + qk_norm_rope_."""
+    `qk_norm_rope_` applied in its store loop (alg_gemm_bf16_pair_qk); bit-identical to gemm_pair + qk_norm_rope_, which is
+    what runs when the fused store loop cannot take the call (a PackedB in either problem among those cases)."""
     lib = load_library()
     a, fa = gemm_args(*first[0], **first[1])
     b, fb = gemm_args(*second[0], **second[1])

@@ -25,7 +25,8 @@ int launch_gemm_p6_conv(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_
 // sustains ~10 % more under the package power cap; fp32 rounding points differ from 9 / 6: 32 products per instruction) | 9 (the
 // asm main loop on 32x32x16; round 3: faster than the 8-wave ping-pong on all five C2 shapes) | 6 (the 8-wave ping-pong;
 // bit-identical to 9).  Calls the asm loops cannot take (K < 128, byte offsets past 32 bits) and the convolution operands run
-// schedule 6; e4m3 operands run schedule 9's e4m3 loop under 9 and 10.
+// schedule 6; e4m3 operands run schedule 9's e4m3 loop under 9 and 10.  A packed B (ALG_GEMM_B_PACKED11) runs schedule 11 under
+// every ALG_GEMM_PIPE; the e4m3 and convolution forms refuse it.
 static int gemm_pipe() { return opt(OPT_GEMM_PIPE); }
 static bool asm_pipe() { return gemm_pipe() == 9 || gemm_pipe() == 10; }
 }  // namespace alg
@@ -96,6 +97,24 @@ static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool valid
       return ALG_EINVAL;
     }
   }
+  if (a->flags & ALG_GEMM_B_PACKED11) {
+    // the caller packed B for schedule 11 (alg_pack_b_p11): that schedule or nothing (B cannot be read any other way).  Checked
+    // here, before validate_only returns, so that a pair refuses a bad packed problem before it launches the other one.
+    if (fp8) {
+      set_error("alg_gemm_fp8: a packed B (ALG_GEMM_B_PACKED11) holds bf16 fragments for schedule 11; the e4m3 GEMM reads a row-major B");
+      return ALG_EINVAL;
+    }
+    if (a->conv_wp) {
+      set_error("alg_gemm_bf16: convolution addressing cannot be combined with a packed B (ALG_GEMM_B_PACKED11)");
+      return ALG_EINVAL;
+    }
+    if (a->K < 128 || 256 * a->lda * 2 + (int64_t)a->K * 2 >= (1ll << 32) || a->strideB != 0 ||
+        (a->flags & (ALG_GEMM_BIAS_PER_ROW | ALG_GEMM_PERMUTE_COLS)) || ((uintptr_t)a->B & 15)) {
+      set_error("alg_gemm_bf16: a packed B (ALG_GEMM_B_PACKED11) needs K >= 128, 32-bit byte offsets inside a 256-row A panel, a B shared by "
+                "the batch (strideB = 0) and a plain column layout (no per-row bias / column permutation)");
+      return ALG_EINVAL;
+    }
+  }
   if (validate_only) return ALG_OK;
   if ((int64_t)a->M * a->ldc >= (1ll << 31) || (a->R && (int64_t)a->M * a->ldr >= (1ll << 31))) {
     // Every argument check above has run on the WHOLE call, so a slab can only fail at launch (no error after
@@ -139,16 +158,7 @@ static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool valid
     return launch_gemm_p6_fp8(a, m_tiles, n_tiles, nwg, s);
   }
   if (a->conv_wp) return launch_gemm_p6_conv(a, m_tiles, n_tiles, nwg, s);
-  if (a->flags & ALG_GEMM_B_PACKED11) {
-    // the caller packed B for schedule 11 (alg_pack_b_p11): that schedule or nothing (B cannot be read any other way)
-    if (a->K < 128 || 256 * a->lda * 2 + (int64_t)a->K * 2 >= (1ll << 32) || a->strideB != 0 ||
-        (a->flags & (ALG_GEMM_BIAS_PER_ROW | ALG_GEMM_PERMUTE_COLS)) || ((uintptr_t)a->B & 15)) {
-      set_error("alg_gemm_bf16: a packed B (ALG_GEMM_B_PACKED11) needs K >= 128, 32-bit byte offsets inside a 256-row A panel, a B shared by "
-                "the batch (strideB = 0) and a plain column layout (no per-row bias / column permutation)");
-      return ALG_EINVAL;
-    }
-    return launch_gemm_p11(a, m_tiles, n_tiles, nwg, s);
-  }
+  if (a->flags & ALG_GEMM_B_PACKED11) return launch_gemm_p11(a, m_tiles, n_tiles, nwg, s);   // (arguments checked above)
   switch (gemm_pipe()) {
     case 9:   // 4 waves, hand-written asm main loop; needs two k-tiles and 32-bit byte offsets inside a 256-row panel
     case 10:
@@ -162,11 +172,13 @@ static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool valid
 extern "C" int alg_gemm_bf16(const alg_gemm_args* a, void* stream) { return gemm_entry(a, stream, false); }
 
 // Two independent plain GEMMs in one persistent launch when schedule 9 can take both (no residual / activation / convolution,
-// K >= 128, 32-bit offsets, no slab split); otherwise -- and always with ALG_GEMM_PIPE=6 -- simply one launch after the other.
-// Either way every output element is computed exactly as alg_gemm_bf16 would compute it (bit-identical).
+// row-major B, K >= 128, 32-bit offsets, no slab split); otherwise -- and always with ALG_GEMM_PIPE=6 -- simply one launch
+// after the other.  Either way every output element is computed exactly as alg_gemm_bf16 would compute it (bit-identical).
+// The pair kernels read B as a row-major [N][ldb] panel: a packed B (ALG_GEMM_B_PACKED11) sends its problem to schedule 11
+// through gemm_entry.
 static bool pair_eligible(const alg_gemm_args* a) {
-  return a && a->A && a->B && a->C && !a->R && !a->gate && a->act == ALG_ACT_NONE && !a->conv_wp && a->M > 0 && a->N > 0 &&
-         a->batch > 0 && a->K >= 128 && a->K % 64 == 0 && 256 * a->lda * 2 + (int64_t)a->K * 2 < (1ll << 32) &&
+  return a && a->A && a->B && a->C && !(a->flags & ALG_GEMM_B_PACKED11) && !a->R && !a->gate && a->act == ALG_ACT_NONE &&
+         !a->conv_wp && a->M > 0 && a->N > 0 && a->batch > 0 && a->K >= 128 && a->K % 64 == 0 && 256 * a->lda * 2 + (int64_t)a->K * 2 < (1ll << 32) &&
          256 * a->ldb * 2 + (int64_t)a->K * 2 < (1ll << 32) && (int64_t)a->M * a->ldc < (1ll << 31) &&
          !(a->lda % 8 || a->ldb % 8 || a->strideA % 8 || a->strideB % 8 || ((uintptr_t)a->A & 15) || ((uintptr_t)a->B & 15)) &&
          ((a->N & 3) != 0 || !((a->ldc & 3) || (a->strideC & 3) || ((uintptr_t)a->C & 7) ||
@@ -210,7 +222,8 @@ extern "C" int alg_gemm_bf16_pair_qk(const alg_gemm_args* a, const alg_gemm_args
     return ALG_EINVAL;
   }
   // the store loop owns whole head vectors and whole Q / K tiles: heads * 64 a multiple of the 256-column tile, staged epilogue
-  // (N % 8 == 0 and 16-byte rows hold by the layout; a per-row bias would take the element-exact path)
+  // (N % 8 == 0 and 16-byte rows hold by the layout; a per-row bias would take the element-exact path).  A packed B in either
+  // problem takes the fallback (pair_eligible): its problem runs on schedule 11, the norm + rope as a launch of its own.
   const bool fused = asm_pipe() && pair_eligible(a) && pair_eligible(b) && e->heads % 4 == 0 &&
                      !(a->bias && (a->flags & ALG_GEMM_BIAS_PER_ROW));
   if (fused) {

@@ -139,7 +139,10 @@ int alg_unipc_update(const float* x, const float* m0, const float* m1, const flo
 #define ALG_GEMM_PERMUTE_COLS 4   /* store column n at n with bits 2 and 3 swapped (MFMA k-order for V^T) */
 #define ALG_GEMM_GATE_SEG_STRIDE 16 /* gate[1] sits gate_seg_stride elements after gate[0] instead of N */
 #define ALG_GEMM_B_PACKED11 32     /* B is NOT [N][K] but the panel alg_pack_b_p11 wrote from it (ldb ignored, strideB must be 0): the call runs
-                                     GEMM schedule 11 -- 1 x 4 waves, the weight fetched straight into registers in MFMA-fragment order */
+                                     GEMM schedule 11 -- 1 x 4 waves, the weight fetched straight into registers in MFMA-fragment order --
+                                     under every ALG_GEMM_PIPE.  Accepted by alg_gemm_bf16 and by either problem of alg_gemm_bf16_pair /
+                                     _pair_qk (that problem then runs as its own alg_gemm_bf16 call); alg_gemm_fp8 and the convolution
+                                     addressing refuse it (ALG_EINVAL) */
 #define ALG_GEMM_GATE_F32 8       /* gate is float32 and C = bf16(R + gate * bf16(acc + bias)) with ONE final rounding
                                      (WanTransformerBlock: (x.float() + out * gate_msa).type_as(x)) */
 
@@ -182,9 +185,11 @@ int64_t alg_pack_b_p11_bytes(int N, int K);
 int alg_pack_b_p11(const void* w, void* packed, int N, int K, int64_t ldb, void* stream);
 
 /* Two independent alg_gemm_bf16 calls as ONE persistent launch when both are plain (no residual, gate, activation or
- * convolution addressing; the Q|K and V^T projections of a DiT block, cog:1082-1090, read the same activations): the tiles of
- * `b` follow the tiles of `a` in the tile list, so the two launches' partial last rounds become one.  Every output element is
- * computed exactly as by the two separate calls (bit-identical); calls the pair form cannot take run one after the other.
+ * convolution addressing, a row-major B; the Q|K and V^T projections of a DiT block, cog:1082-1090, read the same activations):
+ * the tiles of `b` follow the tiles of `a` in the tile list, so the two launches' partial last rounds become one.  Every output
+ * element is computed exactly as by the two separate calls (bit-identical); calls the pair form cannot take run one after the
+ * other -- among them a problem with a packed B (ALG_GEMM_B_PACKED11), which runs on schedule 11 as its alg_gemm_bf16 call
+ * would.  Every argument check of alg_gemm_bf16 runs on both problems before anything is launched: a bad call writes no C.
  * C of one problem must not alias an operand of the other. */
 int alg_gemm_bf16_pair(const alg_gemm_args* a, const alg_gemm_args* b, void* stream);
 
@@ -193,7 +198,7 @@ int alg_gemm_bf16_pair(const alg_gemm_args* a, const alg_gemm_args* b, void* str
  * qk->C is the [batch][S][2][heads][64] tensor (M = S, N = ldc = 2*heads*64, strideC = S*N), written ONCE in its final
  * form.  Bit-identical to alg_gemm_bf16_pair followed by alg_qk_norm_rope_scaled(qk->C, ..., qk->batch, qk->M, heads,
  * text_len, eps, q_scale) -- which is exactly what runs when the fused form cannot take the call (heads % 4 != 0, schedule 6,
- * a pair the persistent launch cannot take). */
+ * a pair the persistent launch cannot take, e.g. a packed B in either problem). */
 typedef struct alg_qk_norm_rope_args {
   const void *wq, *bq, *wk, *bk;      /* [64] bf16 LayerNorm weight / bias of norm_q and norm_k */
   const float *cos_tab, *sin_tab;      /* [S - text_len][64] float32, or both NULL (no rotary embedding) */
@@ -204,7 +209,8 @@ int alg_gemm_bf16_pair_qk(const alg_gemm_args* qk, const alg_gemm_args* vt, cons
 
 /* BASELINE config 5 (fp8 weights on the CDNA4 fp8 MFMA): same contract and epilogues with A and B holding OCP e4m3 bytes
  * (lda / ldb / strides in elements = bytes) and per-row float32 scales: C = epilogue(a_scale[m] * b_scale[n] * (A @ B^T)).
- * K % 128 == 0.  Operands come from alg_quantize_fp8_rows (activations: per token, weights: per output channel). */
+ * K % 128 == 0.  Operands come from alg_quantize_fp8_rows (activations: per token, weights: per output channel).  B is always
+ * row-major: ALG_GEMM_B_PACKED11 is refused with ALG_EINVAL before anything is launched. */
 int alg_gemm_fp8(const alg_gemm_args* args, void* stream);
 
 /* Row-wise dynamic quantisation to OCP e4m3: scale[r] = max|x[r]| / 448 (1 if the row is zero), q = e4m3(x / scale).
