@@ -23,7 +23,7 @@ GEMM_B_PACKED11 = 32     # B is the panel pack_b_p11 wrote (GEMM schedule 11: th
 
 EXPORTS = (
     "alg_version", "alg_last_error", "alg_reload_env", "alg_down_up", "alg_gaussian_blur", "alg_cfg_ddim_step", "alg_gemm_bf16", "alg_gemm_bf16_pair", "alg_gemm_bf16_pair_qk", "alg_pack_b_p11", "alg_pack_b_p11_bytes",
-    "alg_flash_attn_d64", "alg_layernorm_modulate", "alg_qk_norm_rope", "alg_patchify", "alg_unpatchify",
+    "alg_flash_attn_d64", "alg_layernorm_modulate", "alg_layernorm_modulate_fp8", "alg_qk_norm_rope", "alg_patchify", "alg_unpatchify",
     "alg_timestep_embedding", "alg_cfg_combine", "alg_lincomb", "alg_unipc_update", "alg_concat_cast", "alg_flash_attn_d128", "alg_layernorm_mod_f32", "alg_layernorm_mod_f32_fp8", "alg_rmsnorm_rope",
     "alg_wan_modulation", "alg_patchify3d", "alg_unpatchify3d", "alg_timestep_embedding_f32", "alg_linear_f32",
     "alg_gelu_erf", "alg_layernorm_modulate_seg", "alg_headnorm_rope", "alg_masked_mean", "alg_silu", "alg_gemm_fp8", "alg_quantize_fp8_rows",
@@ -163,6 +163,7 @@ def load_library():
                                        c_int64, c_int64, c_int64, c_int64, c_float, c_void_p]
     lib.alg_layernorm_modulate.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                            c_int, c_int, c_int64, c_int64, c_int, c_float, c_void_p]
+    lib.alg_layernorm_modulate_fp8.argtypes = [c_void_p] * 7 + [c_int64, c_int, c_int, c_int, c_int64, c_int, c_float, c_void_p]
     lib.alg_qk_norm_rope.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_int, c_int, c_int, c_float, c_void_p]
     lib.alg_qk_norm_rope_scaled.argtypes = [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]
@@ -853,6 +854,18 @@ def layernorm_modulate(x, y, weight, bias, scale, shift, mod_bstride, batch, row
     _check(lib.alg_layernorm_modulate(c_void_p(x.data_ptr() + 2 * x_off), c_void_p(y.data_ptr() + 2 * y_off),
                                       _ptr(weight), _ptr(bias), sc, sh, mod_bstride, batch, rows, D, x_bstride,
                                       y_bstride, seg_split, float(eps), _stream()), "alg_layernorm_modulate")
+
+
+def layernorm_modulate_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstride, batch, rows, D, seg_split, eps,
+                           x_bstride=None, x_off=0, scale_off=0, shift_off=0, q8_off=0, q8_scale_off=0):
+    """layernorm_modulate followed by quantize_fp8_rows, in one pass (bit-identical bytes and scales): q8 [batch * rows, D]
+    e4m3 bytes and q8_scale [batch * rows] float32 are filled in place; *_off are element offsets as in layernorm_modulate
+    (scale_off / shift_off into the modulation vectors, q8_off / q8_scale_off into the two outputs)."""
+    x_bstride = rows * D if x_bstride is None else x_bstride
+    _check(load_library().alg_layernorm_modulate_fp8(_p(x, x_off), _p(q8, q8_off), _p(q8_scale, q8_scale_off), _p(weight), _p(bias),
+                                                     _p(scale, scale_off), _p(shift, shift_off), mod_bstride, batch, rows, D,
+                                                     x_bstride, seg_split, float(eps), _stream()), "alg_layernorm_modulate_fp8")
+    return q8, q8_scale
 
 
 def qk_norm_rope_(qk, wq, bq, wk, bk, cos, sin, batch, S, heads, text_len, eps, q_scale=1.0):

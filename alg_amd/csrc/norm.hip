@@ -173,6 +173,118 @@ __global__ __launch_bounds__(256) void ln_mod_rows_kernel(const bf16_t* __restri
   }
 }
 
+// ---- the same LayerNorm + modulation in front of an fp8 GEMM (alg_layernorm_modulate_fp8) ----
+// The row a wave has just normalised is still in its registers, already rounded to bf16 (the value the bf16 tensor would hold), so it is
+// quantised there exactly as alg_quantize_fp8_rows would quantise that tensor (gemm_p6_fp8.hip: amax / 448 per row, reciprocal, clamp,
+// v_cvt_pk_fp8_f32): the e4m3 bytes + the row scale are the only stores, the bf16 row never reaches HBM.  8 bytes per lane per store.
+
+// max over the wave of a value >= 0, the same in every lane.  A maximum does not depend on the order it is taken in, so unlike the
+// sums of the statistics (whose butterfly order is part of the bit-identity with ln_mod_kernel) it may take the short way: four
+// DPP steps inside each row of 16 lanes, two row broadcasts, one v_readlane -- no trip through the LDS crossbar.
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ float dpp_max(float v) {
+  const int i = __builtin_bit_cast(int, v);
+  return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xf, false)));
+}
+__device__ __forceinline__ float wave_max(float v) {
+  v = dpp_max<0xB1, 0xf>(v);    // quad_perm [1, 0, 3, 2]
+  v = dpp_max<0x4E, 0xf>(v);    // quad_perm [2, 3, 0, 1]
+  v = dpp_max<0x141, 0xf>(v);   // row_half_mirror
+  v = dpp_max<0x140, 0xf>(v);   // row_mirror: every lane holds its row's maximum
+  v = dpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
+  v = dpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds the wave's
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
+}
+
+template <int ITERS>
+__device__ __forceinline__ void quantize_row_store(const float (&v)[ITERS][8], int lane, uint8_t* __restrict__ qr,
+                                                   float* __restrict__ scale_out) {
+  float amax = 0.0f;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(v[i][k]));
+  amax = wave_max(amax);
+  const float qs = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float inv = 1.0f / qs;
+  if (lane == 0) *scale_out = qs;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) {
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = fminf(fmaxf(v[i][k] * inv, -448.0f), 448.0f);
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    *(uint2*)(qr + i * 512 + lane * 8) = make_uint2((unsigned)lo, (unsigned)hi);
+  }
+}
+
+// ln_mod_kernel's arithmetic (one row per wave, any of weight / bias / modulation absent); q8 [total_rows][D], q8_scale [total_rows].
+// Every call takes this form, the many-row AdaLN calls too: with the third reduction and the conversion in the row's dependency
+// chain, the occupancy of this kernel (97 registers at D = 3072) hid more than the rows-per-wave form of ln_mod_rows_kernel saved
+// in parameter traffic (C2 call, 35,552 rows: 95 - 99 us here, 105 - 110 us in that form; profiles/cog_fp8_step_ab.json).
+template <int ITERS>
+__global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restrict__ x, uint8_t* __restrict__ q8,
+                                                         float* __restrict__ q8_scale, const bf16_t* __restrict__ w,
+                                                         const bf16_t* __restrict__ bs, const bf16_t* __restrict__ scale,
+                                                         const bf16_t* __restrict__ shift, int64_t mod_bs, int64_t x_bs,
+                                                         int64_t total_rows, int rows, int seg_split, int64_t seg_stride,
+                                                         float eps) {
+  constexpr int D = ITERS * 512;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= total_rows) return;
+  const int bidx = (int)(row / rows);
+  const int r = (int)(row - (int64_t)bidx * rows);
+  const int seg = r >= seg_split ? 1 : 0;
+  const bf16_t* xr = x + (int64_t)bidx * x_bs + (int64_t)r * D;
+  float v[ITERS][8];
+  float s = 0.0f;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) {
+    unpack8(*(const uint4*)(xr + i * 512 + lane * 8), v[i]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += v[i][k];
+  }
+  const float mean = wave_sum(s) * (1.0f / D);
+  float q = 0.0f;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float d = v[i][k] - mean;
+      q = fmaf(d, d, q);
+    }
+  const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+  const bf16_t* sc = scale ? scale + (int64_t)bidx * mod_bs + (int64_t)seg * seg_stride : nullptr;
+  const bf16_t* sh = shift ? shift + (int64_t)bidx * mod_bs + (int64_t)seg * seg_stride : nullptr;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) {
+    const int c0 = i * 512 + lane * 8;
+    float wv[8], bv[8];
+    if (w) unpack8(*(const uint4*)(w + c0), wv);
+    if (bs) unpack8(*(const uint4*)(bs + c0), bv);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      float n = (v[i][k] - mean) * rstd;
+      if (w) n = n * wv[k];
+      if (bs) n = n + bv[k];
+      v[i][k] = rbf(n);
+    }
+    if (sc) {
+      float scv[8], shv[8];
+      unpack8(*(const uint4*)(sc + c0), scv);
+      unpack8(*(const uint4*)(sh + c0), shv);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[i][k] = rbf(rbf(v[i][k] * rbf(1.0f + scv[k])) + shv[k]);
+    }
+  }
+  quantize_row_store<ITERS>(v, lane, q8 + row * D, q8_scale + row);
+}
+
 // In place per-head LayerNorm(64) + RoPE on qk [batch][S][2][heads][64]; 8 lanes per head vector.
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ qk, const bf16_t* __restrict__ wq,
                                                            const bf16_t* __restrict__ bq,
@@ -347,6 +459,48 @@ extern "C" int alg_layernorm_modulate_seg(const void* x, void* y, const void* we
   }
 #undef LN_CASE
   return check_launch("alg_layernorm_modulate");
+}
+
+extern "C" int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
+                                          const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows,
+                                          int D, int64_t x_bstride, int seg_split, float eps, void* stream) {
+  if (!x || !q8 || !q8_scale || batch <= 0 || rows <= 0 || D <= 0) {
+    set_error("alg_layernorm_modulate_fp8: bad argument (batch=%d rows=%d D=%d)", batch, rows, D);
+    return ALG_EINVAL;
+  }
+  if (D % 512 != 0 || D > 8192) {
+    set_error("alg_layernorm_modulate_fp8: D=%d must be a multiple of 512 and <= 8192", D);
+    return ALG_EINVAL;
+  }
+  if ((scale == nullptr) != (shift == nullptr)) {
+    set_error("alg_layernorm_modulate_fp8: scale and shift must be given together");
+    return ALG_EINVAL;
+  }
+  if (((uintptr_t)x & 15) || ((uintptr_t)q8 & 7) || ((uintptr_t)q8_scale & 3) || ((uintptr_t)weight & 15) ||
+      ((uintptr_t)bias & 15) || ((uintptr_t)scale & 15) || ((uintptr_t)shift & 15) || (mod_bstride % 8) || (x_bstride % 8)) {
+    set_error("alg_layernorm_modulate_fp8: x and the parameter rows must be 16-byte aligned, q8 8-byte aligned");
+    return ALG_EINVAL;
+  }
+  const int64_t total = (int64_t)batch * rows;
+  if ((total + 3) / 4 > 0x7fffffff) {
+    set_error("alg_layernorm_modulate_fp8: batch * rows = %lld is more than one launch covers", (long long)total);
+    return ALG_EINVAL;
+  }
+  const unsigned grid = (unsigned)((total + 3) / 4);
+  const int64_t seg_stride = D;
+  hipStream_t s = (hipStream_t)stream;
+#define LN_CASE(I)                                                                                                  \
+  case I:                                                                                                           \
+    hipLaunchKernelGGL(ln_mod_fp8_kernel<I>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (uint8_t*)q8, q8_scale,  \
+                       (const bf16_t*)weight, (const bf16_t*)bias, (const bf16_t*)scale, (const bf16_t*)shift,      \
+                       mod_bstride, x_bstride, total, rows, seg_split, seg_stride, eps);                            \
+    break;
+  switch (D / 512) {
+    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
+    LN_CASE(9) LN_CASE(10) LN_CASE(11) LN_CASE(12) LN_CASE(13) LN_CASE(14) LN_CASE(15) LN_CASE(16)
+  }
+#undef LN_CASE
+  return check_launch("alg_layernorm_modulate_fp8");
 }
 
 extern "C" int alg_qk_norm_rope_scaled(void* qk, const void* wq, const void* bq, const void* wk, const void* bk,

@@ -129,11 +129,12 @@ class CogVideoXImageToVideoPipeline:
     # -- construction ---------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
-                        scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", **_):
+                        scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False, **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
-        `image_latents` and `output_type="latent"`."""
+        `image_latents` and `output_type="latent"`.  `fp8=True` loads the transformer with e4m3 block linears
+        (CogVideoXTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in."""
         import os
 
         from .autoencoder_kl_cogvideox import AutoencoderKLCogVideoX
@@ -143,7 +144,7 @@ class CogVideoXImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = CogVideoXTransformer3DModel.from_pretrained(model_path, torch_dtype=torch_dtype,
-                                                                      device=device)
+                                                                      device=device, fp8=fp8)
         if vae is None and has("vae"):
             vae = AutoencoderKLCogVideoX.from_pretrained(model_path, device=device)
         if text_encoder is None and has("text_encoder"):

@@ -21,6 +21,10 @@ HBM layout (all bf16, allocated once per batch size N and reused every step):
     att    [N, S, D]        attention output (A operand of the out-projection)
     h      [N, S, 4D]       GELU(FF1)
     mod    [N, L*12D + 4D]  every AdaLN shift/scale/gate vector of the forward, one GEMM
+fp8 mode only (allocated on the first fp8 forward of a shape):
+    q8     [N*S, 4D] bytes  OCP e4m3 copy of the current GEMM input (rows of K = D or 4D bytes, contiguous)
+    q8s    [N, S4] float32  its per-token scales, S4 = S rounded up to a multiple of 4 (the V^T GEMM reads them as its B scales,
+                            16 bytes at a time, per batch item)
 """
 from __future__ import annotations
 
@@ -78,7 +82,15 @@ def _bf(t, device):
 class CogVideoXTransformer3DModel:
     dtype = torch.bfloat16
 
-    def __init__(self, config: CogVideoXTransformerConfig, weights: dict, device="cuda"):
+    # the block linears that fp8 mode quantises, per output channel: Q|K, V, attention out, feed-forward in / out
+    FP8_WEIGHTS = ("wqk", "wv", "wo", "wf1", "wf2")
+
+    def __init__(self, config: CogVideoXTransformerConfig, weights: dict, device="cuda", fp8=False):
+        """``fp8=True``: the five block linears (attn1.to_q | to_k, to_v, to_out.0, ff.net.0.proj, ff.net.2) run on the fp8
+        MFMA (alg_gemm_fp8) -- weights quantised once to OCP e4m3 with one scale per output channel, activations per token
+        in front of each GEMM; embedders, the AdaLN GEMM, proj_out, norms, attention and the residual stream stay bf16.
+        Built this way the model keeps no bf16 (or packed) copy of those weights.  ``model.fp8`` may also be flipped on a
+        model built in bf16 (A/B runs): the e4m3 copies are then made on the first fp8 forward and both sets are kept."""
         cfg = self.config = config
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -90,6 +102,12 @@ class CogVideoXTransformer3DModel:
         D = cfg.inner_dim
         if D % 512:
             raise _lib.AlgHipError("inner_dim must be a multiple of 512 (LayerNorm kernel tiling)")
+        self.fp8 = bool(fp8)
+        if self.fp8:
+            self._check_fp8_shapes()
+        # fp8: the modulated LayerNorms write the e4m3 tokens + row scales themselves (alg_layernorm_modulate_fp8; bit-identical
+        # to the norm into y followed by the quantiser pass, which is what False runs)
+        self.fuse_quant = True
         _lib.load_library()
         # True (default): the softmax scale * log2(e) rides in Q's last rounding and the attention takes log2-unit scores
         # (alg_qk_norm_rope_scaled + ALG_ATTN_Q_PRESCALED); False keeps the per-score multiply (A/B and parity tests)
@@ -160,8 +178,11 @@ class CogVideoXTransformer3DModel:
             L["bf1"] = _bf(w[b + "ff.net.0.proj.bias"], dev)
             L["wf2"] = _bf(w[b + "ff.net.2.weight"], dev)
             L["bf2"] = _bf(w[b + "ff.net.2.bias"], dev)
-            for nm in ("wo", "wf1", "wf2"):
-                L["p" + nm] = _lib.PackedB(L[nm])
+            if self.fp8:
+                self._quantize_layer(L, drop_bf16=True)
+            else:
+                for nm in ("wo", "wf1", "wf2"):
+                    L["p" + nm] = _lib.PackedB(L[nm])
             self.layers.append(L)
         # norm_out: chunk order (shift, scale) -> (shift, shift, scale, scale) so both segments are valid
         ow, ob = w["norm_out.linear.weight"], w["norm_out.linear.bias"]
@@ -181,6 +202,25 @@ class CogVideoXTransformer3DModel:
         self._ws = {}
         self._rope_cache = {}
         self.profile = None  # set to a dict to collect (start, stop) HIP event pairs per kernel family
+
+    def _check_fp8_shapes(self):
+        cfg = self.config
+        D, F4 = cfg.inner_dim, cfg.ff_inner_mult * cfg.inner_dim
+        if D % 128 or F4 % 128:
+            raise ValueError("fp8=True: the e4m3 GEMM needs K %% 128 == 0, this config has inner_dim = %d and a feed-forward "
+                             "width of %d" % (D, F4))
+
+    @staticmethod
+    def _quantize_layer(L, drop_bf16):
+        """e4m3 copies (bytes, per-output-channel float32 scales) of a block's five linears under "<name>8"."""
+        for nm in CogVideoXTransformer3DModel.FP8_WEIGHTS:
+            wt = L[nm]
+            q = torch.empty(wt.shape, dtype=torch.uint8, device=wt.device)
+            sc = torch.empty(wt.shape[0], dtype=torch.float32, device=wt.device)
+            _lib.quantize_fp8_rows(wt, q, sc, wt.shape[0], wt.shape[1])
+            L[nm + "8"] = (q, sc)
+            if drop_bf16:
+                del L[nm]
 
     def _positional(self, Hh, Ww, Fr, S):
         """The joint [text; video] positional embedding added behind the patch embedding, [S, D] bf16, or None.
@@ -236,22 +276,22 @@ class CogVideoXTransformer3DModel:
 
     # ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False):
+    def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False, fp8=False):
         """Seeded synthetic weights at the configured shapes, generated on the device tensor by tensor (the
         real checkpoint cannot be downloaded here).  Matrices N(0, std^2), biases 0, norm gains 1."""
         from .weights import synthetic_state_dict
 
         config = config or CogVideoXTransformerConfig()
         return cls(config, synthetic_state_dict(config, seed=seed, std=std, device=device,
-                                                 randomize_affine=randomize_affine), device=device)
+                                                 randomize_affine=randomize_affine), device=device, fp8=fp8)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", **_):
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", fp8=False, **_):
         """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk."""
         from .weights import load_diffusers_transformer
 
         config, sd = load_diffusers_transformer(path, subfolder)
-        return cls(config, sd, device=device)
+        return cls(config, sd, device=device, fp8=fp8)
 
     def to(self, *args, **kwargs):
         return self
@@ -285,6 +325,70 @@ class CogVideoXTransformer3DModel:
             self._ws.pop(next(iter(self._ws)))
         self._ws[key] = ws
         return ws
+
+    def _fp8_state(self, ws, N, S):
+        """The e4m3 operand workspace of a shape (made on its first fp8 forward) and, for a model built in bf16 whose `fp8`
+        attribute was set afterwards, the e4m3 weights next to the bf16 ones."""
+        if "q8" not in ws:
+            F4 = self.config.ff_inner_mult * self.config.inner_dim
+            ws["q8"] = torch.empty(N * S, F4, dtype=torch.uint8, device=self.device)
+            ws["q8s"] = torch.empty(N * ((S + 3) // 4 * 4), dtype=torch.float32, device=self.device)
+        if self.layers and "wqk8" not in self.layers[0]:
+            self._check_fp8_shapes()
+            for L in self.layers:
+                self._quantize_layer(L, drop_bf16=False)
+        return ws["q8"], ws["q8s"]
+
+    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale):
+        """One transformer block with e4m3 operands on its five linears: the launch order of the bf16 block, each GEMM input
+        quantised per token into q8 / q8s first (by the LayerNorm itself where a norm produces it)."""
+        cfg, G, TM = self.config, _lib.gemm, self._timed
+        D, Hn = cfg.inner_dim, cfg.num_attention_heads
+        F4 = cfg.ff_inner_mult * D
+        x, y, qk, vt, att, h, mod, S_pad = ws["x"], ws["y"], ws["qk"], ws["vt"], ws["att"], ws["h"], ws["mod"], ws["S_pad"]
+        # The scales of a batch item start at a multiple of 4 floats (the V^T GEMM reads them as B scales, 16 bytes at a time).
+        # S % 4 == 0 (the 5B-I2V shape: 226 + 17,550 tokens): the rows of all items are contiguous and one launch quantises
+        # them all; otherwise one launch per item.
+        SS = (S + 3) // 4 * 4
+        items = ((0, N),) if SS == S else tuple((n, 1) for n in range(N))
+
+        def quant(src, K_):
+            for n0, nb in items:
+                TM("quant", _lib.quantize_fp8_rows, src, q8, q8s, nb * S, K_, x_off=n0 * S * K_, q_off=n0 * S * K_,
+                   scale_off=n0 * SS)
+
+        def ln_mod(nw, nb, m):
+            if not self.fuse_quant:
+                TM("ln_mod", _lib.layernorm_modulate, x, y, nw, nb, mod, mod, self.mod_cols, N, S, D, T, cfg.norm_eps,
+                   scale_off=m + 2 * D, shift_off=m)
+                return quant(y, D)
+            for n0, n_ in items:
+                TM("ln_mod", _lib.layernorm_modulate_fp8, x, q8, q8s, nw, nb, mod, mod, self.mod_cols, n_, S, D, T, cfg.norm_eps,
+                   x_off=n0 * S * D, scale_off=n0 * self.mod_cols + m + 2 * D, shift_off=n0 * self.mod_cols + m,
+                   q8_off=n0 * S * D, q8_scale_off=n0 * SS)
+
+        def lin(name, wt, C, N_, K_, ldc, **kw):
+            """C[n] = epilogue(q8[n] @ W^T) per batch item: A = the e4m3 tokens in the workspace, rows of K_ bytes"""
+            TM(name, G, q8, wt[0], C, S, N_, K_, K_, K_, ldc, a_scale=q8s, b_scale=wt[1], batch=N, strideA=S * K_,
+               strideAScale=SS, strideC=S * ldc, **kw)
+
+        ln_mod(L["norm1_w"], L["norm1_b"], m1)
+        lin("gemm_qk", L["wqk8"], qk, 2 * D, D, 2 * D, bias=L["bqk"])
+        # V^T: the weight is the A operand, the (already quantised) tokens are B
+        TM("gemm_vt", G, L["wv8"][0], q8, vt, D, S, D, D, D, S_pad, a_scale=L["wv8"][1], b_scale=q8s, strideBScale=SS,
+           bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+        TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
+           cfg.qk_norm_eps, q_scale=q_scale)
+        TM("attn", _lib.flash_attn_d64, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale,
+           k_off=D, q_prescaled=prescale)
+        quant(att, D)
+        lin("gemm_out", L["wo8"], x, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
+            strideGate=self.mod_cols, seg_split=T, strideR=S * D)
+        ln_mod(L["norm2_w"], L["norm2_b"], m2)
+        lin("gemm_ff1", L["wf18"], h, F4, D, F4, bias=L["bf1"], act=_lib.ACT_GELU_TANH)
+        quant(h, F4)
+        lin("gemm_ff2", L["wf28"], x, D, F4, D, bias=L["bf2"], R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D,
+            strideGate=self.mod_cols, seg_split=T, strideR=S * D)
 
     def _rope(self, image_rotary_emb):
         if image_rotary_emb is None:
@@ -336,6 +440,12 @@ class CogVideoXTransformer3DModel:
         pos_emb = self._positional(Hh, Ww, Fr, S)
         ws = self._workspace(N, S, P)
         x, y, qk, vt, att, h, mod = ws["x"], ws["y"], ws["qk"], ws["vt"], ws["att"], ws["h"], ws["mod"]
+        fp8 = bool(self.fp8)
+        if fp8:
+            q8, q8s = self._fp8_state(ws, N, S)
+        elif self.layers and "wqk" not in self.layers[0]:
+            raise _lib.AlgHipError("this model was built with fp8=True and holds no bf16 copy of its block weights: build it "
+                                   "with fp8=False to run (or switch between) both modes")
         S_pad = ws["S_pad"]
         cos, sin = self._rope(image_rotary_emb)
         G = _lib.gemm
@@ -383,6 +493,9 @@ class CogVideoXTransformer3DModel:
         for li, L in enumerate(self.layers):
             m1 = li * 12 * D          # norm1: shift @+0, scale @+2D, gate @+4D (each [2][D])
             m2 = m1 + 6 * D           # norm2
+            if fp8:
+                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale)
+                continue
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
                T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
             qk_call = ((y, L["wqk"], qk, S, 2 * D, D, D, D, 2 * D), dict(bias=L["bqk"], batch=N, strideA=S * D, strideC=S * 2 * D))

@@ -457,6 +457,14 @@ int alg_layernorm_modulate_seg(const void* x, void* y, const void* weight, const
                                const void* shift, int64_t mod_bstride, int64_t seg_stride, int batch, int rows, int D,
                                int64_t x_bstride, int64_t y_bstride, int seg_split, float eps, void* stream);
 
+/* alg_layernorm_modulate in front of an fp8 GEMM: the same arguments and arithmetic, but instead of y it writes
+ * q8 [batch * rows][D] OCP e4m3 bytes (contiguous) and q8_scale [batch * rows] float32 -- bit for bit what
+ * alg_quantize_fp8_rows makes of the bf16 y (amax / 448 per row), without the bf16 row going through memory.
+ * x 16-byte aligned, q8 8-byte aligned.  D % 512 == 0, D <= 8192; anything else is ALG_EINVAL before any launch. */
+int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
+                               const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows, int D,
+                               int64_t x_bstride, int seg_split, float eps, void* stream);
+
 /* In place on qk: [batch][S][2][heads][64] bf16 (q then k per token):
  * per-head LayerNorm(64) with (wq,bq) / (wk,bk), then RoPE (cos/sin fp32 [S - text_len][64], interleaved-pair
  * convention) on tokens >= text_len. */
