@@ -328,6 +328,8 @@ def dit_forward(cfg: DiTConfig, w, hidden_states, encoder_hidden_states, timeste
             k = torch.cat([k[:, :, :T], apply_rotary(k[:, :, T:], cos, sin)], dim=2)
         if collect is not None and i == 0:
             collect["n1_0"], collect["q_0"], collect["k_0"], collect["v_0"] = n1.clone(), q.clone(), k.clone(), v.clone()
+        if collect is not None and 0 < i == cfg.num_layers - 1:     # the last block's attention operands too
+            collect["q_%d" % i], collect["k_%d" % i] = q.clone(), k.clone()
         a = F.scaled_dot_product_attention(q, k, v)
         a = a.transpose(1, 2).reshape(B, S, D)
         if collect is not None and i == 0:

@@ -247,7 +247,12 @@ def wan_forward(cfg: WanConfig, sd, hidden_states, timestep, encoder_hidden_stat
         k = _rms(lin(n, b + "attn1.to_k"), sd[b + "attn1.norm_k.weight"], cfg.eps, dtype)
         v = lin(n, b + "attn1.to_v")
         rp = lambda t: _rope(t.view(B, -1, heads, D // heads).transpose(1, 2), cos, sin).transpose(1, 2).reshape(B, -1, D)
-        a = lin(_sdpa(rp(q), rp(k), v, heads), b + "attn1.to_out.0")
+        q, k = rp(q), rp(k)
+        if collect is not None and l == 0:       # block 0's self-attention operands, [B, heads, S, d] as the kernel sees them
+            collect["q_0"] = q.view(B, -1, heads, D // heads).transpose(1, 2)
+            collect["k_0"] = k.view(B, -1, heads, D // heads).transpose(1, 2)
+            collect["v_0"] = v.view(B, -1, heads, D // heads).transpose(1, 2)
+        a = lin(_sdpa(q, k, v, heads), b + "attn1.to_out.0")
         x = (x.float() + a * g1).to(dtype)
         # cross-attention (image tokens first, text last)
         n = _ln(x, sd.get(b + "norm2.weight"), sd.get(b + "norm2.bias"), cfg.eps).to(dtype) if cfg.cross_attn_norm else x
