@@ -32,6 +32,7 @@ EXPORTS = (
     "alg_vae_unpack_planes", "alg_rms_norm_rows", "alg_softmax_hilo", "alg_flash_attn_d128_ex", "alg_flash_attn_d128_dual", "alg_rope_half", "alg_patchify_t", "alg_unpatchify_t", "alg_qk_norm_rope_scaled", "alg_flash_attn_d64_ex", "alg_embed_rows", "alg_t5_layernorm", "alg_attn_bias", "alg_mul_bf16", "alg_quick_gelu",
     "alg_lowpass_tables_bytes", "alg_lowpass_tables_build", "alg_down_up_workspace_bytes", "alg_gaussian_blur_workspace_bytes",
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap",
+    "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes")
@@ -120,6 +121,13 @@ def load_library():
     lib.alg_flash_attn_d128_ex.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
     lib.alg_flash_attn_d128_dual.argtypes = ([c_void_p] * 3 + [c_int] + [c_int64] * 4 + [c_void_p] * 2 + [c_int] + [c_int64] * 4 +
                                              [c_void_p] + [c_int] * 3 + [c_int64] * 4 + [c_float, c_void_p])
+    lib.alg_flash_attn_d128_fp8.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
+    lib.alg_quantize_fp8_khead.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p] + [c_int] * 4 + [c_void_p]
+    lib.alg_quantize_fp8_vt.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p] + [c_int] * 4 + [c_void_p]
+    lib.alg_rmsnorm_rope_fp8.argtypes = [c_void_p] * 4 + [c_int64, c_int, c_int, c_int, c_float, c_void_p, c_int64, c_void_p,
+                                         c_void_p, c_void_p]
+    lib.alg_headnorm_rope_fp8.argtypes = [c_void_p] * 4 + [c_int64, c_int64, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int64,
+                                          c_int64, c_void_p, c_int64, c_void_p, c_void_p]
     lib.alg_rope_half.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, c_void_p]
     lib.alg_layernorm_mod_f32.argtypes = [c_void_p] * 6 + [c_int64, c_int, c_int, c_int, c_float, c_void_p]
     lib.alg_layernorm_mod_f32_fp8.argtypes = [c_void_p] * 7 + [c_int64, c_int, c_int, c_int, c_float, c_void_p]
@@ -487,6 +495,62 @@ def flash_attn_d128(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, 
     _check(lib.alg_flash_attn_d128(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale),
                                    _stream()), "alg_flash_attn_d128")
     return o
+
+
+def flash_attn_d128_fp8(q8, q_scale, k8, k_scale, vt8, vt_scale, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs,
+                        o_bs, o_rs, scale, q_off=0, qs_off=0, k_off=0, ks_off=0, vt_off=0, vts_off=0, o_off=0, kv_group=1,
+                        causal=False):
+    """softmax(scale * (q_scale q8)(k_scale k8)^T) (vt_scale vt8)^T for head_dim 128 on the fp8 MFMA (opt-in; see
+    include/alg_hip.h): q8 / k8 / vt8 hold OCP e4m3 bytes (strides and offsets in bytes), q_scale [batch, Sq, heads], k_scale
+    [batch, heads] and vt_scale [batch, heads * 128] are float32 (offsets in elements), o is bf16.  Non-causal, ungrouped only:
+    anything else is refused by the library."""
+    lib = load_library()
+    for t in (q8, q_scale, k8, k_scale, vt8, vt_scale, o):
+        _dev(t, "attention operand")
+    for t in (q8, k8, vt8):
+        if t.element_size() != 1:
+            raise AlgHipError("flash_attn_d128_fp8 takes e4m3 bytes (uint8 / float8_e4m3fn), got %s" % t.dtype)
+    _check(lib.alg_flash_attn_d128_fp8(_p(q8, q_off), _p(q_scale, qs_off), _p(k8, k_off), _p(k_scale, ks_off), _p(vt8, vt_off),
+                                       _p(vt_scale, vts_off), _p(o, o_off), batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs,
+                                       vt_rs, o_bs, o_rs, float(scale), int(kv_group), int(bool(causal)), _stream()),
+           "alg_flash_attn_d128_fp8")
+    return o
+
+
+def quantize_fp8_khead(x, q, scale, batch, heads, S, x_bs, x_rs, q_bs, q_rs, x_off=0, q_off=0, scale_off=0, scale_given=False):
+    """K operand of flash_attn_d128_fp8: bf16 (b, s, h, d) -> e4m3 bytes with ONE float32 scale per (batch, head); scale_given:
+    scale is an input (a bound known beforehand) instead of the measured amax / 448."""
+    _check(load_library().alg_quantize_fp8_khead(_p(x, x_off), x_bs, x_rs, _p(q, q_off), q_bs, q_rs, _p(scale, scale_off), batch,
+                                                 heads, S, int(bool(scale_given)), _stream()), "alg_quantize_fp8_khead")
+    return q, scale
+
+
+def quantize_fp8_vt(x, q, scale, batch, rows, Skv, x_bs, x_rs, q_bs, q_rs, src_permuted=True, x_off=0, q_off=0, scale_off=0):
+    """V^T operand of flash_attn_d128_fp8: bf16 V^T rows -> e4m3 rows in the kernel's key order, one float32 scale per row,
+    padding columns zero.  src_permuted: x is what gemm(..., flags=GEMM_PERMUTE_COLS) wrote."""
+    _check(load_library().alg_quantize_fp8_vt(_p(x, x_off), x_bs, x_rs, _p(q, q_off), q_bs, q_rs, _p(scale, scale_off), batch,
+                                              rows, Skv, int(bool(src_permuted)), _stream()), "alg_quantize_fp8_vt")
+    return q, scale
+
+
+def rmsnorm_rope_fp8(x, weight, cos, sin, x_rstride, batch, rows, D, eps, q8, q8_rstride, scale=None, head_scale=None, x_off=0,
+                     q8_off=0, scale_off=0, hs_off=0):
+    """rmsnorm_rope_ followed by the e4m3 quantiser of flash_attn_d128_fp8, in one pass (bit-identical bytes and scales); x is
+    only read.  scale: per (token, head) output; head_scale [batch, heads]: given scales (the K operand)."""
+    _check(load_library().alg_rmsnorm_rope_fp8(_p(x, x_off), _p(weight), _p(cos), _p(sin), x_rstride, batch, rows, D, float(eps),
+                                               _p(q8, q8_off), q8_rstride, _p(scale, scale_off), _p(head_scale, hs_off), _stream()),
+           "alg_rmsnorm_rope_fp8")
+    return q8
+
+
+def headnorm_rope_fp8(x, weight, cos, sin, x_rstride, x_bstride, batch, rows, heads, rope_tokens, eps, q8, q8_rstride, q8_bstride,
+                      scale=None, scale_bstride=0, head_scale=None, x_off=0, q8_off=0, scale_off=0, hs_off=0):
+    """headnorm_rope_ followed by the e4m3 quantiser of flash_attn_d128_fp8, in one pass (bit-identical); x is only read."""
+    _check(load_library().alg_headnorm_rope_fp8(_p(x, x_off), _p(weight), _p(cos), _p(sin), x_rstride, x_bstride, batch, rows,
+                                                heads, rope_tokens, float(eps), _p(q8, q8_off), q8_rstride, q8_bstride,
+                                                _p(scale, scale_off), scale_bstride, _p(head_scale, hs_off), _stream()),
+           "alg_headnorm_rope_fp8")
+    return q8
 
 
 def _p(t, off=0):

@@ -310,6 +310,83 @@ __global__ __launch_bounds__(256) void rmsnorm_rope_kernel(bf16_t* __restrict__ 
   }
 }
 
+// rmsnorm_rope_kernel writing OCP e4m3 for alg_flash_attn_d128_fp8 instead of updating x: the bf16-rounded result of every 128-wide
+// head (16 lanes) is quantised in registers exactly as a quantiser pass over the bf16 tensor would (scale, reciprocal, clamp,
+// v_cvt_pk_fp8_f32: gemm_p6_fp8.hip).  head_scale == nullptr: one scale per (token, head) = amax / 448 of the head vector, written to
+// scale[row * heads + head] (the Q operand).  head_scale != nullptr: the given scale of (batch, head) is used (the K operand, whose
+// scale is per (batch, head)); nothing is written to `scale`.  x is only read.
+template <int ITERS>
+__global__ __launch_bounds__(256) void rmsnorm_rope_fp8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
+                                                               const float* __restrict__ cos_tab,
+                                                               const float* __restrict__ sin_tab, int64_t x_rs,
+                                                               int64_t total_rows, int rows, float eps, uint8_t* __restrict__ q8,
+                                                               int64_t q8_rs, float* __restrict__ scale,
+                                                               const float* __restrict__ head_scale) {
+  constexpr int D = ITERS * 512;
+  constexpr int HEADS = D / 128;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= total_rows) return;
+  const int tok = (int)(row % rows);
+  const int bidx = (int)(row / rows);
+  const bf16_t* xr = x + row * x_rs;
+  float v[ITERS][8];
+  float q = 0.0f;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) {
+    unpack8(*(const uint4*)(xr + i * 512 + lane * 8), v[i]);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) q = fmaf(v[i][k], v[i][k], q);
+  }
+  const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) {
+    const int c0 = i * 512 + lane * 8;
+    const int head = c0 >> 7;
+    float wv[8], o[8];
+    unpack8(*(const uint4*)(w + c0), wv);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = rbf(rbf(v[i][k] * rstd) * wv[k]);
+    if (cos_tab) {
+      const int j0 = (c0 & 127) >> 1;
+      const float4 cs = *(const float4*)(cos_tab + (int64_t)tok * 64 + j0);
+      const float4 sn = *(const float4*)(sin_tab + (int64_t)tok * 64 + j0);
+      const float cv[4] = {cs.x, cs.y, cs.z, cs.w}, sv[4] = {sn.x, sn.y, sn.z, sn.w};
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        const float a = o[2 * p], b = o[2 * p + 1];
+        o[2 * p] = a * cv[p] - b * sv[p];
+        o[2 * p + 1] = a * sv[p] + b * cv[p];
+      }
+    }
+    float amax = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      o[k] = rbf(o[k]);   // what alg_rmsnorm_rope stores
+      amax = fmaxf(amax, fabsf(o[k]));
+    }
+    float sc;
+    if (head_scale) {
+      sc = head_scale[bidx * HEADS + head];
+    } else {
+#pragma unroll
+      for (int m = 8; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
+      sc = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
+      if ((lane & 15) == 0) scale[row * HEADS + head] = sc;
+    }
+    const float inv = 1.0f / sc;
+    float f[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f[k] = fminf(fmaxf(o[k] * inv, -448.0f), 448.0f);
+    int lo = 0, hi = 0;
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+    *(uint2*)(q8 + row * q8_rs + c0) = make_uint2((unsigned)lo, (unsigned)hi);
+  }
+}
+
 // out[l][b][j][d] = table[l][j][d] + float(vec[b][(per_j ? j * D : 0) + d])
 __global__ __launch_bounds__(256) void modulation_kernel(const float* __restrict__ table, const bf16_t* __restrict__ vec,
                                                          float* __restrict__ out, int L, int B, int J, int D, int per_j) {
@@ -516,6 +593,34 @@ extern "C" int alg_rmsnorm_rope(void* x, const void* weight, const float* cos_ta
     return ALG_ELIMIT;
   }
   return check_launch("alg_rmsnorm_rope");
+}
+
+extern "C" int alg_rmsnorm_rope_fp8(const void* x, const void* weight, const float* cos_tab, const float* sin_tab,
+                                    int64_t x_rstride, int batch, int rows, int D, float eps, void* q8, int64_t q8_rstride,
+                                    float* scale, const float* head_scale, void* stream) {
+  if (batch < 0 || rows < 0 || D <= 0 || D % 512 || x_rstride % 8 || q8_rstride % 8 || q8_rstride < D ||
+      (cos_tab && (D % 128 || !sin_tab))) {
+    set_error("alg_rmsnorm_rope_fp8: bad shape batch=%d rows=%d D=%d strides=%lld / %lld", batch, rows, D, (long long)x_rstride,
+              (long long)q8_rstride);
+    return ALG_EINVAL;
+  }
+  const int64_t total = (int64_t)batch * rows;
+  if (total == 0) return ALG_OK;
+  if (!x || !weight || !q8 || (!scale && !head_scale) || ((uintptr_t)x & 15) || ((uintptr_t)q8 & 7)) {
+    set_error("alg_rmsnorm_rope_fp8: null or misaligned pointer (x 16-byte, q8 8-byte; scale or head_scale is needed)");
+    return ALG_EINVAL;
+  }
+  const dim3 grid((unsigned)((total + 3) / 4)), blk(256);
+  hipStream_t s = (hipStream_t)stream;
+  bool ok = true;
+  DISPATCH_ITERS(D / 512, hipLaunchKernelGGL(wan::rmsnorm_rope_fp8_kernel<IT>, grid, blk, 0, s, (const bf16_t*)x,
+                                             (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, total, rows, eps, (uint8_t*)q8,
+                                             q8_rstride, scale, head_scale));
+  if (!ok) {
+    set_error("alg_rmsnorm_rope_fp8: D=%d is not built (D/512 in {1,2,3,4,6,8,10,12})", D);
+    return ALG_ELIMIT;
+  }
+  return check_launch("alg_rmsnorm_rope_fp8");
 }
 
 static unsigned grid_for(int64_t total) {

@@ -104,7 +104,7 @@ class WanImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, image_encoder=None, image_processor=None, device="cuda",
-                        fp8=False, **_):
+                        fp8=False, fp8_attention=False, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
         (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan)."""
         import os
@@ -117,7 +117,7 @@ class WanImageToVideoPipeline:
 
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
-            transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8)
+            transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention)
         if text_encoder is None and has("text_encoder"):
             text_encoder = UMT5EncoderModel.from_pretrained(model_path, device=device)
         if tokenizer is None:

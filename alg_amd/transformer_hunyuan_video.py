@@ -30,6 +30,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .transformer_wan import k_scale_bound
 
 BF = torch.bfloat16
 
@@ -143,7 +144,12 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
 class HunyuanVideoTransformer3DModel:
     dtype = BF
 
-    def __init__(self, config: HunyuanVideoTransformerConfig, weights: dict, device="cuda"):
+    def __init__(self, config: HunyuanVideoTransformerConfig, weights: dict, device="cuda", fp8_attention=False):
+        """``fp8_attention=True`` (opt-in, may be flipped between calls): the joint attention of the dual- and single-stream
+        blocks runs on alg_flash_attn_d128_fp8 -- the per-head RMSNorm + RoPE pass writes Q (one scale per token and head) and K
+        (one scale per head, transformer_wan.k_scale_bound) as e4m3 itself, V^T is quantised per row behind its GEMMs.  The token
+        refiner stays bf16.  Off, the forward is the bf16 one bit for bit."""
+        self.fp8_attention = bool(fp8_attention)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
         if sum(config.rope_axes_dim) != config.attention_head_dim:
@@ -199,6 +205,9 @@ class HunyuanVideoTransformer3DModel:
             L.nq_c, L.nk_c = bf(b + "attn.norm_added_q.weight"), bf(b + "attn.norm_added_k.weight")
             L.f1, L.f2 = lin(b + "ff.net.0.proj"), lin(b + "ff.net.2")
             L.f1_c, L.f2_c = lin(b + "ff_context.net.0.proj"), lin(b + "ff_context.net.2")
+            # one K scale per head covers the latent keys (norm_k + RoPE) and the prompt keys (norm_added_k) of the joint sequence
+            L.k8_scale = torch.maximum(k_scale_bound(L.nk, 128, config.num_attention_heads, rope=True),
+                                       k_scale_bound(L.nk_c, 128, config.num_attention_heads, rope=False))
             L.packed = {id(t): _lib.PackedB(t) for t in (L.wqk, L.o[0], L.f1[0], L.f2[0])}     # the latent stream's linears (see packed_weights)
             self.dual.append(L)
         self.single = []
@@ -211,6 +220,7 @@ class HunyuanVideoTransformer3DModel:
             L.v = lin(b + "attn.to_v")
             L.nq, L.nk = bf(b + "attn.norm_q.weight"), bf(b + "attn.norm_k.weight")
             L.mlp, L.out = lin(b + "proj_mlp"), lin(b + "proj_out")
+            L.k8_scale = k_scale_bound(L.nk, 128, config.num_attention_heads, rope=True)
             L.packed = {id(t): _lib.PackedB(t) for t in (L.wqk, L.mlp[0], L.out[0])}
             self.single.append(L)
         w.ada_out, w.out = lin("norm_out.linear"), lin("proj_out")
@@ -224,12 +234,12 @@ class HunyuanVideoTransformer3DModel:
         self.packed_weights = True
 
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, device="cuda"):
+    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8_attention=False):
         config = config or HunyuanVideoTransformerConfig()
-        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device)
+        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8_attention=fp8_attention)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", **_):
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8_attention=False, **_):
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -242,7 +252,7 @@ class HunyuanVideoTransformer3DModel:
                                                if k in fields})
         from .weights import read_shards
         sd = read_shards(root)
-        return cls(cfg, sd, device=device)
+        return cls(cfg, sd, device=device, fp8_attention=fp8_attention)
 
     def to(self, *a, **k):
         return self
@@ -307,6 +317,14 @@ class HunyuanVideoTransformer3DModel:
             ws.eh = e(N, L, M)
             ws.rgate = e(N, 2 * D)
             self._ws[key] = ws
+        if self.fp8_attention and not hasattr(ws, "a8"):   # e4m3 operands of the joint attention: only once the flag is on
+            cfg, dev = self.config, self.device
+            D, heads, J = cfg.dim, cfg.num_attention_heads, ws.J
+            ws.a8 = torch.empty(N, J, 2 * D, dtype=torch.uint8, device=dev)               # Q | K, the layout of ws.qk
+            ws.a8s = torch.empty(N, J, heads, dtype=torch.float32, device=dev)            # Q scales
+            ws.k8s = torch.stack([Lw.k8_scale for Lw in self.dual + self.single])[:, None, :].expand(-1, N, -1).contiguous()
+            ws.vt8 = torch.zeros(N, D, ws.J_pad, dtype=torch.uint8, device=dev)
+            ws.vt8s = torch.empty(N, D, dtype=torch.float32, device=dev)
         return ws
 
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask, pooled_projections,
@@ -406,12 +424,25 @@ class HunyuanVideoTransformer3DModel:
         mod_bs, seg = (12 * D, 6 * D) if tr else (6 * D, 0)
         split = first if tr else 0
 
-        def attention():
+        f8 = self.fp8_attention
+        H8 = _lib.headnorm_rope_fp8
+
+        def attention(bi=0):
+            """bi: index of the block in dual + single order (its K scales, fp8_attention)."""
             prof = self.profile
+            if f8:   # V^T of the joint sequence (latent and prompt columns) per row, in the fp8 kernel's key order
+                T("vt_quant", _lib.quantize_fp8_vt, ws.vt, ws.vt8, ws.vt8s, N, D, J, D * ws.J_pad, ws.J_pad, D * ws.J_pad, ws.J_pad)
             if prof is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
             for b in range(N):
+                if f8:
+                    _lib.flash_attn_d128_fp8(ws.a8, ws.a8s, ws.a8, ws.k8s, ws.vt8, ws.vt8s, ws.am, 1, heads, J, S + valid[b],
+                                             J * 2 * D, 2 * D, J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale,
+                                             q_off=b * J * 2 * D, qs_off=b * J * heads, k_off=b * J * 2 * D + D,
+                                             ks_off=(bi * N + b) * heads, vt_off=b * D * ws.J_pad, vts_off=b * D,
+                                             o_off=b * J * (D + M))
+                    continue
                 _lib.flash_attn_d128(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D,
                                      D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, q_off=b * J * 2 * D,
                                      k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad, o_off=b * J * (D + M))
@@ -427,7 +458,7 @@ class HunyuanVideoTransformer3DModel:
         AM = D + M
         use_packed = self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         PK = lambda Lw_, t: (Lw_.packed.get(id(t)) or t) if use_packed else t     # the packed copy of a block's weight, if it has one
-        for Lw in self.dual:
+        for bi, Lw in enumerate(self.dual):
             ada(Lw.ada, ws.semb2 if tr else ws.semb1, ws.mod, 6 * D, tr)     # [N][2][6D] (token replace) or [N][6D]
             mv = ws.mod
             ada(Lw.ada_c, ws.semb1, ws.modc, 6 * D, False)
@@ -444,11 +475,22 @@ class HunyuanVideoTransformer3DModel:
             G(Lw.v_c[0], ws.y, ws.vt, D, L, D, D, D, ws.J_pad, bias=Lw.v_c[1], batch=N, strideB=J * D,
               strideC=D * ws.J_pad, b_off=S * D, perm_col0=S, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
             # latent rows: norm_q / norm_k + rope; prompt rows: norm_added_q / norm_added_k, no rope
-            T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6)
-            T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6, x_off=D)
-            _lib.headnorm_rope_(ws.qk, Lw.nq_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D)
-            _lib.headnorm_rope_(ws.qk, Lw.nk_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D + D)
-            attention()
+            if f8:   # the same four norms, writing e4m3 Q | K (and the Q scales) instead of updating ws.qk
+                qkb, sb, hs = J * 2 * D, J * heads, bi * N * heads
+                T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, qkb, N, S, heads, S, 1e-6, ws.a8, 2 * D, qkb, scale=ws.a8s,
+                  scale_bstride=sb)
+                T("headnorm_rope", H8, ws.qk, Lw.nk, cos, sin, 2 * D, qkb, N, S, heads, S, 1e-6, ws.a8, 2 * D, qkb, head_scale=ws.k8s,
+                  hs_off=hs, x_off=D, q8_off=D)
+                H8(ws.qk, Lw.nq_c, None, None, 2 * D, qkb, N, L, heads, 0, 1e-6, ws.a8, 2 * D, qkb, scale=ws.a8s, scale_bstride=sb,
+                   x_off=S * 2 * D, q8_off=S * 2 * D, scale_off=S * heads)
+                H8(ws.qk, Lw.nk_c, None, None, 2 * D, qkb, N, L, heads, 0, 1e-6, ws.a8, 2 * D, qkb, head_scale=ws.k8s, hs_off=hs,
+                   x_off=S * 2 * D + D, q8_off=S * 2 * D + D)
+            else:
+                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6)
+                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6, x_off=D)
+                _lib.headnorm_rope_(ws.qk, Lw.nq_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D)
+                _lib.headnorm_rope_(ws.qk, Lw.nk_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D + D)
+            attention(bi)
             T("gemm_out", G, ws.am, PK(Lw, Lw.o[0]), ws.x, S, D, D, AM, D, D, bias=Lw.o[1], R=ws.x, ldr=D, gate=mv, gate_off=2 * D,
               strideGate=mod_bs, gate_seg_stride=seg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D)
             G(ws.am, Lw.o_c[0], ws.x, L, D, D, AM, D, D, bias=Lw.o_c[1], R=ws.x, ldr=D, gate=ws.modc, gate_off=2 * D,
@@ -472,7 +514,7 @@ class HunyuanVideoTransformer3DModel:
 
         # ---- single-stream blocks, in place on the joint buffer ----
         smod_bs, sseg = (6 * D, 3 * D) if tr else (3 * D, 0)
-        for Lw in self.single:
+        for bi, Lw in enumerate(self.single, start=len(self.dual)):
             if tr:
                 G(ws.semb2, Lw.ada[0], ws.mod, 2 * N, 3 * D, D, D, D, 3 * D, bias=Lw.ada[1])       # [N][2][3D]: shift, scale, gate
             else:
@@ -483,9 +525,15 @@ class HunyuanVideoTransformer3DModel:
             T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, N * J, 2 * D, D, D, D, 2 * D, bias=Lw.bqk)
             T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, J, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
               strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
-            T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6)
-            T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, x_off=D)
-            attention()
+            if f8:
+                T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
+                  scale=ws.a8s, scale_bstride=J * heads)
+                T("headnorm_rope", H8, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
+                  head_scale=ws.k8s, hs_off=bi * N * heads, x_off=D, q8_off=D)
+            else:
+                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6)
+                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, x_off=D)
+            attention(bi)
             T("gemm_out_mlp", G, ws.am, PK(Lw, Lw.out[0]), ws.x, J, D, AM, AM, AM, D, bias=Lw.out[1], R=ws.x, ldr=D, gate=ws.mod, gate_off=2 * D,
               strideGate=smod_bs, gate_seg_stride=sseg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D,
               strideR=J * D)

@@ -12,6 +12,7 @@ The forward is nothing but launch order over the C ABI of libalg_hip.so:
     text / image embedders: alg_gemm_bf16 (+GELU-tanh), alg_layernorm_mod_f32, alg_gelu_erf
     per block:  alg_layernorm_mod_f32 -> alg_gemm_bf16 (fused QK; V written transposed + permuted) -> alg_rmsnorm_rope x2
                 -> alg_flash_attn_d128 -> alg_gemm_bf16 (out proj, fp32-gate residual epilogue)
+                (fp8_attention: alg_rmsnorm_rope_fp8 x2 + alg_quantize_fp8_vt -> alg_flash_attn_d128_fp8 in their place)
                 alg_layernorm_mod_f32 -> q GEMM + rmsnorm ; text / image K (GEMM + rmsnorm) and V^T (GEMM)
                 -> alg_flash_attn_d128 x2 -> alg_lincomb (text + image) -> alg_gemm_bf16 (out proj + residual)
                 alg_layernorm_mod_f32 -> alg_gemm_bf16 (GELU-tanh) -> alg_gemm_bf16 (fp32-gate residual)
@@ -136,14 +137,34 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
     return sd
 
 
+def k_scale_bound(norm_weight, norm_dim, heads, rope):
+    """The K scale of alg_flash_attn_d128_fp8 is one number per (batch, head), and the norm pass that writes K as e4m3 has to
+    know it before it has seen a token.  RMSNorm bounds its output whatever the input: |x_i| * rsqrt(mean(x^2) + eps) <=
+    sqrt(norm_dim), times |w_i|, times sqrt(2) when RoPE rotates a pair -- so  1.02 * sqrt(norm_dim [* 2]) * max_head |w| / 448
+    (2 % for the two bf16 roundings on the way) is a scale under which no key can leave the e4m3 range.  It is 10-100 x the
+    scale a measured amax would give; e4m3 is a floating-point format, so that costs range, not precision: keys down to 2^-6 of
+    the bound / 448 keep their three mantissa bits (docs/numerics.md).  norm_weight: [heads * 128] (norm across heads) or [128]
+    (per-head norm, shared by all heads).  Returns float32 [heads]."""
+    w = norm_weight.float().abs().reshape(-1, 128).amax(dim=1)
+    if w.numel() == 1:
+        w = w.expand(heads)
+    return (w * (1.02 * math.sqrt(norm_dim * (2.0 if rope else 1.0)) / 448.0)).contiguous()
+
+
 class WanTransformer3DModel:
     dtype = BF
 
-    def __init__(self, config: WanTransformerConfig, weights: dict, device="cuda", fp8=False):
+    def __init__(self, config: WanTransformerConfig, weights: dict, device="cuda", fp8=False, fp8_attention=False):
         """``fp8=True`` (BASELINE config 5): the seven large linears of every block run on the fp8 MFMA -- weights are
         quantised once to OCP e4m3 with one scale per output channel, activations per token right before each GEMM
-        (alg_quantize_fp8_rows); norms, attention, embedders and the residual stream stay bf16 / fp32."""
+        (alg_quantize_fp8_rows); norms, attention, embedders and the residual stream stay bf16 / fp32.
+
+        ``fp8_attention=True`` (opt-in, independent of ``fp8``, may be flipped between calls): the self-attention of every
+        block runs on alg_flash_attn_d128_fp8 -- the RMSNorm + RoPE pass writes Q (one scale per token and head) and K (one
+        scale per head: ``k_scale_bound``) as e4m3 itself, V^T is quantised per row behind its GEMM.  Cross-attention stays
+        bf16.  Off, the forward is the bf16 one bit for bit."""
         self.fp8 = bool(fp8)
+        self.fp8_attention = bool(fp8_attention)
         self.pair_qkv = True     # bf16: Q|K and V^T projections of a block as one alg_gemm_bf16_pair launch (bit-identical)
         self.dual_cross = True   # I2V: text + image cross-attention of a block as one alg_flash_attn_d128_dual launch (bit-identical to two launches + add)
         self.fuse_quant = True   # fp8: the modulated LayerNorm writes the e4m3 tokens + row scales itself (bit-identical to the quantiser pass)
@@ -204,6 +225,7 @@ class WanTransformer3DModel:
             L.wv, L.bv = bf(b + "attn1.to_v.weight"), bf(b + "attn1.to_v.bias")
             L.wo, L.bo = bf(b + "attn1.to_out.0.weight"), bf(b + "attn1.to_out.0.bias")
             L.nq, L.nk = bf(b + "attn1.norm_q.weight"), bf(b + "attn1.norm_k.weight")
+            L.k8_scale = k_scale_bound(L.nk, D, config.num_attention_heads, rope=True)    # [heads] fp32 (fp8_attention)
             L.n2w = f32(b + "norm2.weight") if config.cross_attn_norm else None
             L.n2b = f32(b + "norm2.bias") if config.cross_attn_norm else None
             L.cq_w, L.cq_b = bf(b + "attn2.to_q.weight"), bf(b + "attn2.to_q.bias")
@@ -234,12 +256,13 @@ class WanTransformer3DModel:
 
     # ---- construction ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8=False):
+    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8=False, fp8_attention=False):
         config = config or WanTransformerConfig()
-        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8=fp8)
+        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8=fp8,
+                   fp8_attention=fp8_attention)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8=False, **_):
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8=False, fp8_attention=False, **_):
         """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk."""
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
@@ -252,7 +275,7 @@ class WanTransformer3DModel:
         cfg = WanTransformerConfig(**{k: (tuple(v) if k == "patch_size" else v) for k, v in raw.items() if k in fields})
         from .weights import read_shards
         sd = read_shards(root)
-        return cls(cfg, sd, device=device, fp8=fp8)
+        return cls(cfg, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
 
     def to(self, *args, **kwargs):
         return self
@@ -330,6 +353,14 @@ class WanTransformer3DModel:
                 ws.img_pad = (n_img + 63) // 64 * 64
                 ws.vti = z(N, D, ws.img_pad)
             self._ws[key] = ws
+        if self.fp8_attention and not hasattr(ws, "a8"):   # e4m3 operands of the self-attention: only once the flag is on
+            cfg, dev = self.config, self.device
+            D, heads = cfg.dim, cfg.num_attention_heads
+            ws.a8 = torch.empty(N, S, 2 * D, dtype=torch.uint8, device=dev)              # Q | K, the layout of ws.qk
+            ws.a8s = torch.empty(N, S, heads, dtype=torch.float32, device=dev)           # Q scales
+            ws.k8s = torch.stack([L.k8_scale for L in self.blocks])[:, None, :].expand(-1, N, -1).contiguous()   # [layers, N, heads]
+            ws.vt8 = torch.zeros(N, D, ws.S_pad, dtype=torch.uint8, device=dev)
+            ws.vt8s = torch.empty(N, D, dtype=torch.float32, device=dev)
         return ws
 
     # ---- forward -----------------------------------------------------------------------------------------------------
@@ -430,10 +461,18 @@ class WanTransformer3DModel:
             else:
                 lin("gemm_qk", ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, 2 * D, bias=L.bqk)
                 T("gemm_vt", G, L.wv, ws.y, ws.vt, D, S, D, D, D, S_pad, **vt_kw)
-            T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
-            T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
-            T("attn_self", _lib.flash_attn_d128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
-              S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D)
+            if self.fp8_attention:   # e4m3 Q | K straight out of the norm, V^T per row, attention on the fp8 MFMA
+                T("rms_rope", _lib.rmsnorm_rope_fp8, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps, ws.a8, 2 * D, scale=ws.a8s)
+                T("rms_rope", _lib.rmsnorm_rope_fp8, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, ws.a8, 2 * D,
+                  head_scale=ws.k8s, hs_off=li * N * heads, x_off=D, q8_off=D)
+                T("vt_quant", _lib.quantize_fp8_vt, ws.vt, ws.vt8, ws.vt8s, N, D, S, D * S_pad, S_pad, D * S_pad, S_pad)
+                T("attn_self", _lib.flash_attn_d128_fp8, ws.a8, ws.a8s, ws.a8, ws.k8s, ws.vt8, ws.vt8s, ws.att, N, heads, S, S,
+                  S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D, ks_off=li * N * heads)
+            else:
+                T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
+                T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
+                T("attn_self", _lib.flash_attn_d128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
+                  S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D)
             lin("gemm_out", ws.att, L.wo, ws.x, S, D, D, D, D, bias=L.bo, R=ws.x, ldr=D, gate=ws.mod,
                 gate_off=m0 + 2 * D, strideGate=mod_bs, batch=N, strideA=S * D, strideC=S * D, strideR=S * D,
                 seg_split=1 << 30, flags=_lib.GEMM_GATE_F32)

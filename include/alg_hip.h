@@ -261,6 +261,57 @@ int alg_flash_attn_d128_ex(const void* q, const void* k, const void* vt, void* o
                            int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, int kv_group, int causal,
                            void* stream);
 
+/* Opt-in e4m3 form of alg_flash_attn_d128 on v_mfma_scale_f32_32x32x64_f8f6f4 (attention128_fp8.hip): non-causal, ungrouped
+ * (kv_group != 1 or causal != 0 is ALG_EINVAL), separate Sq / Skv, ragged last tile, bf16 output; strides in elements = bytes.
+ *   q  : OCP e4m3, element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d;  q_scale: float32 [batch][Sq][heads]
+ *        (what alg_quantize_fp8_rows writes for rows of 128 of a contiguous [batch][Sq][heads * 128] tensor)
+ *   k  : likewise with k_bstride / k_rstride;  k_scale: float32 [batch][heads], ONE scale per (batch, head) (alg_quantize_fp8_khead)
+ *   vt : OCP e4m3 V transposed in the kernel's key order (alg_quantize_fp8_vt): element (b, h, d, s) at
+ *        vt + b*vt_bstride + (h*128 + d)*vt_rstride + 64*(s / 64) + perm(s % 64),  perm(32 sub + 8 g + 4 h2 + j) = 32 h2 + 16 sub + 4 g + j
+ *        (sub, h2 < 2; g, j < 4); vt_rstride >= Skv rounded up to 64 and the padding columns must not hold the e4m3 NaN byte
+ *        (they are multiplied by p = 0; alg_quantize_fp8_vt writes zeros);
+ *        vt_scale: float32 [batch][heads * 128], one scale per row
+ *   o  : bf16, element (b, s, h, d) at o + b*o_bstride + s*o_rstride + h*128 + d
+ * o = softmax(scale * (q_scale q)(k_scale k)^T) (vt_scale vt)^T with fp32 accumulation, P rounded to e4m3 at a fixed scale of 2^3
+ * (docs/numerics.md).  q / k / vt 16-byte aligned with strides % 16 == 0, vt_scale 16-byte, o 8-byte aligned (strides % 4 == 0). */
+int alg_flash_attn_d128_fp8(const void* q, const float* q_scale, const void* k, const float* k_scale, const void* vt,
+                            const float* vt_scale, void* o, int batch, int heads, int Sq, int Skv, int64_t q_bstride,
+                            int64_t q_rstride, int64_t k_bstride, int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                            int64_t o_bstride, int64_t o_rstride, float scale, int kv_group, int causal, void* stream);
+
+/* K operand of alg_flash_attn_d128_fp8: x bf16 (b, s, h, d) at x + b*x_bstride + s*x_rstride + h*128 + d becomes e4m3 bytes at
+ * q + b*q_bstride + s*q_rstride + h*128 + d with ONE scale per (batch, head): scale[b*heads + h] = max|x| / 448 over the head's
+ * S x 128 values (1 if all zero), q = e4m3(clamp(x * (1 / scale))) -- the arithmetic of alg_quantize_fp8_rows at that granularity.
+ * scale_given != 0: scale[] is an INPUT (a bound known beforehand; values beyond it saturate at +-448) and only the conversion runs.
+ * x 16-byte, q 8-byte aligned; strides % 8 == 0. */
+int alg_quantize_fp8_khead(const void* x, int64_t x_bstride, int64_t x_rstride, void* q, int64_t q_bstride, int64_t q_rstride,
+                           float* scale, int batch, int heads, int S, int scale_given, void* stream);
+
+/* alg_rmsnorm_rope / alg_headnorm_rope in front of alg_flash_attn_d128_fp8: the same arguments and arithmetic, but x is only
+ * read and the result goes out as OCP e4m3 -- q8 element (row, c) at q8 + row*q8_rstride + c (alg_rmsnorm_rope_fp8; row counts
+ * through the batch) or (b, tok, c) at q8 + b*q8_bstride + tok*q8_rstride + c (alg_headnorm_rope_fp8) -- bit for bit what a
+ * quantiser pass makes of the bf16 tensor the bf16 kernel writes, without that tensor going through memory:
+ *   head_scale == NULL: one scale per (token, head) = max|head vector| / 448 (1 if zero), written to scale[row*heads + head]
+ *                       (alg_headnorm_rope_fp8: scale[b*scale_bstride + tok*heads + head]): alg_quantize_fp8_rows on rows of 128;
+ *   head_scale != NULL: float32 [batch][heads], the scale of (b, head) is READ from it and `scale` is not touched:
+ *                       alg_quantize_fp8_khead with scale_given = 1.
+ * x 16-byte, q8 8-byte aligned; q8_rstride % 8 == 0. */
+int alg_rmsnorm_rope_fp8(const void* x, const void* weight, const float* cos_tab, const float* sin_tab, int64_t x_rstride,
+                         int batch, int rows, int D, float eps, void* q8, int64_t q8_rstride, float* scale,
+                         const float* head_scale, void* stream);
+int alg_headnorm_rope_fp8(const void* x, const void* weight, const float* cos_tab, const float* sin_tab, int64_t x_rstride,
+                          int64_t x_bstride, int batch, int rows, int heads, int rope_tokens, float eps, void* q8,
+                          int64_t q8_rstride, int64_t q8_bstride, float* scale, int64_t scale_bstride, const float* head_scale,
+                          void* stream);
+
+/* V^T operand of alg_flash_attn_d128_fp8: `rows` (= heads * 128) bf16 rows per batch at x + b*x_bstride + r*x_rstride become e4m3
+ * rows at q + b*q_bstride + r*q_rstride in the kernel's key order (see above), scale[b*rows + r] = max|x[r][s < Skv]| / 448 (1 if
+ * zero).  src_permuted = 1: x holds key s at the column alg_gemm_bf16 + ALG_GEMM_PERMUTE_COLS writes (index bits 2 and 3
+ * swapped), 0: at column s.  Columns Skv .. Skv rounded up to 64 of x are never used (they must be readable) and are written as
+ * ZERO.  Both row strides >= Skv rounded up to 64 and % 8 == 0; x 16-byte, q 8-byte aligned. */
+int alg_quantize_fp8_vt(const void* x, int64_t x_bstride, int64_t x_rstride, void* q, int64_t q_bstride, int64_t q_rstride,
+                        float* scale, int batch, int rows, int Skv, int src_permuted, void* stream);
+
 /* Two key / value sets for the same queries, the two attention outputs added: the image + text cross-attention of the Wan I2V DiT
  * (wan:910-917 calls WanTransformer3DModel; its attention processor computes sdpa(q, k_img, v_img) + sdpa(q, k, v) on bf16 tensors)
  * as ONE launch -- o = bf16(bf16(attn(q, k, vt)) + bf16(attn(q, k2, vt2))), bit for bit what two alg_flash_attn_d128 calls and
