@@ -33,6 +33,7 @@ EXPORTS = (
     "alg_lowpass_tables_bytes", "alg_lowpass_tables_build", "alg_down_up_workspace_bytes", "alg_gaussian_blur_workspace_bytes",
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
+    "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes")
@@ -172,6 +173,9 @@ def load_library():
     lib.alg_layernorm_modulate.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                            c_int, c_int, c_int64, c_int64, c_int, c_float, c_void_p]
     lib.alg_layernorm_modulate_fp8.argtypes = [c_void_p] * 7 + [c_int64, c_int, c_int, c_int, c_int64, c_int, c_float, c_void_p]
+    lib.alg_layernorm_modulate_seg_fp8.argtypes = [c_void_p] * 7 + [c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int, c_float,
+                                                   c_void_p]
+    lib.alg_quantize_fp8_rows_batched.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     lib.alg_qk_norm_rope.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                      c_int, c_int, c_int, c_float, c_void_p]
     lib.alg_qk_norm_rope_scaled.argtypes = [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]
@@ -891,6 +895,15 @@ def quantize_fp8_rows(x, q, scale, rows, K, x_rstride=None, x_off=0, q_off=0, sc
     return q, scale
 
 
+def quantize_fp8_rows_batched(x, q, scale, batch, rows, K, x_bstride, x_rstride, x_off=0, q_off=0, scale_off=0):
+    """quantize_fp8_rows on rows inside a wider, batch-strided buffer, all batch items in one launch: row r of item b starts at
+    x_off + b * x_bstride + r * x_rstride (elements); q [batch * rows, K] and scale [batch * rows] are contiguous.  Bit-identical
+    to quantize_fp8_rows on each item."""
+    _check(load_library().alg_quantize_fp8_rows_batched(_p(x, x_off), x_bstride, x_rstride, _p(q, q_off), _p(scale, scale_off),
+                                                        batch, rows, K, _stream()), "alg_quantize_fp8_rows_batched")
+    return q, scale
+
+
 ATTN_Q_PRESCALED = 1
 
 
@@ -929,6 +942,18 @@ def layernorm_modulate_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstr
     _check(load_library().alg_layernorm_modulate_fp8(_p(x, x_off), _p(q8, q8_off), _p(q8_scale, q8_scale_off), _p(weight), _p(bias),
                                                      _p(scale, scale_off), _p(shift, shift_off), mod_bstride, batch, rows, D,
                                                      x_bstride, seg_split, float(eps), _stream()), "alg_layernorm_modulate_fp8")
+    return q8, q8_scale
+
+
+def layernorm_modulate_seg_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstride, seg_stride, batch, rows, D, seg_split,
+                               eps, x_bstride=None, x_off=0, scale_off=0, shift_off=0, q8_off=0, q8_scale_off=0):
+    """layernorm_modulate_seg followed by quantize_fp8_rows, in one pass (bit-identical bytes and scales): layernorm_modulate_fp8
+    with an explicit distance between the two row segments' modulation vectors."""
+    x_bstride = rows * D if x_bstride is None else x_bstride
+    _check(load_library().alg_layernorm_modulate_seg_fp8(_p(x, x_off), _p(q8, q8_off), _p(q8_scale, q8_scale_off), _p(weight),
+                                                         _p(bias), _p(scale, scale_off), _p(shift, shift_off), mod_bstride,
+                                                         seg_stride, batch, rows, D, x_bstride, seg_split, float(eps), _stream()),
+           "alg_layernorm_modulate_seg_fp8")
     return q8, q8_scale
 
 

@@ -464,7 +464,15 @@ extern "C" int alg_layernorm_modulate_seg(const void* x, void* y, const void* we
 extern "C" int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
                                           const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows,
                                           int D, int64_t x_bstride, int seg_split, float eps, void* stream) {
-  if (!x || !q8 || !q8_scale || batch <= 0 || rows <= 0 || D <= 0) {
+  return alg_layernorm_modulate_seg_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstride, D, batch, rows, D, x_bstride,
+                                        seg_split, eps, stream);
+}
+
+extern "C" int alg_layernorm_modulate_seg_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
+                                              const void* scale, const void* shift, int64_t mod_bstride, int64_t seg_stride,
+                                              int batch, int rows, int D, int64_t x_bstride, int seg_split, float eps,
+                                              void* stream) {
+  if (!x || !q8 || !q8_scale || batch <= 0 || rows <= 0 || D <= 0 || seg_stride % 8) {
     set_error("alg_layernorm_modulate_fp8: bad argument (batch=%d rows=%d D=%d)", batch, rows, D);
     return ALG_EINVAL;
   }
@@ -487,7 +495,6 @@ extern "C" int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_sca
     return ALG_EINVAL;
   }
   const unsigned grid = (unsigned)((total + 3) / 4);
-  const int64_t seg_stride = D;
   hipStream_t s = (hipStream_t)stream;
 #define LN_CASE(I)                                                                                                  \
   case I:                                                                                                           \

@@ -120,10 +120,11 @@ class HunyuanVideoImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, text_encoder_2=None, tokenizer_2=None, image_processor=None,
-                        device="cuda", fp8_attention=False, **_):
+                        device="cuda", fp8_attention=False, fp8=False, **_):
         """Local-disk loader of a diffusers-format HunyuanVideo-I2V directory (`run.py:68-90`): `transformer/`,
         `text_encoder/` (Llava-Llama-3) + `tokenizer/` + `image_processor/`, `text_encoder_2/` (CLIP-L text tower) +
-        `tokenizer_2/`, `vae/`, `scheduler/`."""
+        `tokenizer_2/`, `vae/`, `scheduler/`.  `fp8=True` loads the transformer with e4m3 block linears
+        (HunyuanVideoTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in."""
         import os
 
         from .schedulers import FlowMatchEulerDiscreteScheduler
@@ -133,7 +134,8 @@ class HunyuanVideoImageToVideoPipeline:
 
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
-            transformer = HunyuanVideoTransformer3DModel.from_pretrained(model_path, device=device, fp8_attention=fp8_attention)
+            transformer = HunyuanVideoTransformer3DModel.from_pretrained(model_path, device=device, fp8_attention=fp8_attention,
+                                                                         fp8=fp8)
         if text_encoder is None and has("text_encoder"):
             from .text_encoder_llava import LlavaForConditionalGeneration
             text_encoder = LlavaForConditionalGeneration.from_pretrained(model_path, device=device)

@@ -17,6 +17,12 @@ timestep-0 vectors (``alg_layernorm_modulate_seg``, ``alg_gemm_bf16`` gate segme
 Kernels: alg_patchify3d, alg_timestep_embedding, alg_gemm_bf16 (all linears, fused SiLU / GELU-tanh / gated-residual
 epilogues, V written transposed), alg_masked_mean, alg_silu, alg_lincomb, alg_layernorm_modulate(_seg), alg_headnorm_rope,
 alg_flash_attn_d128, alg_unpatchify3d.  No CPU fallback.
+
+fp8 mode only (``fp8=True``; allocated on the first fp8 forward of a shape):
+    q8     [N * J, D + M] bytes  OCP e4m3 copy of the current GEMM input (rows of K = D, M or D + M bytes, contiguous)
+    q8s    [N, J4] float32       its per-token scales, J4 = J rounded up to a multiple of 4 (the V^T GEMM reads them as its B
+                                 scales, 16 bytes at a time, per batch item)
+Kernels added by it: alg_layernorm_modulate_seg_fp8, alg_quantize_fp8_rows_batched, alg_gemm_fp8.
 """
 from __future__ import annotations
 
@@ -144,17 +150,37 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
 class HunyuanVideoTransformer3DModel:
     dtype = BF
 
-    def __init__(self, config: HunyuanVideoTransformerConfig, weights: dict, device="cuda", fp8_attention=False):
-        """``fp8_attention=True`` (opt-in, may be flipped between calls): the joint attention of the dual- and single-stream
+    # the block linears that fp8 mode quantises, per output channel (attribute names of a block's weights): dual blocks, latent
+    # stream: to_q | to_k, to_v, to_out.0, ff.net.0.proj, ff.net.2; single blocks: to_q | to_k, to_v, proj_mlp, proj_out
+    FP8_DUAL = ("wqk", "v", "o", "f1", "f2")
+    FP8_SINGLE = ("wqk", "v", "mlp", "out")
+
+    def __init__(self, config: HunyuanVideoTransformerConfig, weights: dict, device="cuda", fp8_attention=False, fp8=False):
+        """``fp8=True`` (opt-in): the large block linears run on the fp8 MFMA (alg_gemm_fp8) in oracle/fp8_oracle.py's scheme --
+        weights quantised once to OCP e4m3 with one scale per output channel, activations with one scale per token in front of
+        each GEMM, fp32 accumulation, one rounding to bf16 in the epilogue.  Quantised: in the dual-stream blocks the LATENT
+        stream's attn.to_q | to_k, attn.to_v, attn.to_out.0, ff.net.0.proj, ff.net.2; in the single-stream blocks, on the joint
+        [latents; text] rows, attn.to_q | to_k, attn.to_v, proj_mlp and proj_out (whose operand is the 15,360-wide row
+        [attention | gelu(mlp)] with ONE scale per token).  Everything else stays bf16 exactly as without the flag: the prompt
+        stream of the dual blocks (add_q/k/v_proj, to_add_out, ff_context), the token refiner, the embedders, all AdaLN
+        linears, the output head, the norms, the attention and the residual stream.  Built this way the model keeps no bf16 (or
+        packed) copy of the quantised weights and cannot run a bf16 forward.  ``model.fp8`` may also be flipped on a model built
+        in bf16 (A/B runs): the e4m3 copies are then made on the first fp8 forward and both sets are kept.  Needs dim % 512 == 0
+        and dim * mlp_ratio % 128 == 0.  Independent of ``fp8_attention``.
+
+        ``fp8_attention=True`` (opt-in, may be flipped between calls): the joint attention of the dual- and single-stream
         blocks runs on alg_flash_attn_d128_fp8 -- the per-head RMSNorm + RoPE pass writes Q (one scale per token and head) and K
         (one scale per head, transformer_wan.k_scale_bound) as e4m3 itself, V^T is quantised per row behind its GEMMs.  The token
         refiner stays bf16.  Off, the forward is the bf16 one bit for bit."""
         self.fp8_attention = bool(fp8_attention)
+        self.fp8 = bool(fp8)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
         if sum(config.rope_axes_dim) != config.attention_head_dim:
             raise ValueError("rope_axes_dim must add up to the head dimension")
         self.config = config
+        if self.fp8:
+            self._check_fp8_shapes()
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.AlgHipError("HunyuanVideoTransformer3DModel runs on the GPU only (HIP kernels); no CPU fallback")
@@ -208,7 +234,11 @@ class HunyuanVideoTransformer3DModel:
             # one K scale per head covers the latent keys (norm_k + RoPE) and the prompt keys (norm_added_k) of the joint sequence
             L.k8_scale = torch.maximum(k_scale_bound(L.nk, 128, config.num_attention_heads, rope=True),
                                        k_scale_bound(L.nk_c, 128, config.num_attention_heads, rope=False))
-            L.packed = {id(t): _lib.PackedB(t) for t in (L.wqk, L.o[0], L.f1[0], L.f2[0])}     # the latent stream's linears (see packed_weights)
+            if self.fp8:
+                L.packed = {}
+                self._quantize_block(L, self.FP8_DUAL, drop_bf16=True)
+            else:
+                L.packed = {id(t): _lib.PackedB(t) for t in (L.wqk, L.o[0], L.f1[0], L.f2[0])}     # the latent stream's linears (see packed_weights)
             self.dual.append(L)
         self.single = []
         for l in range(config.num_single_layers):
@@ -221,7 +251,11 @@ class HunyuanVideoTransformer3DModel:
             L.nq, L.nk = bf(b + "attn.norm_q.weight"), bf(b + "attn.norm_k.weight")
             L.mlp, L.out = lin(b + "proj_mlp"), lin(b + "proj_out")
             L.k8_scale = k_scale_bound(L.nk, 128, config.num_attention_heads, rope=True)
-            L.packed = {id(t): _lib.PackedB(t) for t in (L.wqk, L.mlp[0], L.out[0])}
+            if self.fp8:
+                L.packed = {}
+                self._quantize_block(L, self.FP8_SINGLE, drop_bf16=True)
+            else:
+                L.packed = {id(t): _lib.PackedB(t) for t in (L.wqk, L.mlp[0], L.out[0])}
             self.single.append(L)
         w.ada_out, w.out = lin("norm_out.linear"), lin("proj_out")
         self.w = w
@@ -233,13 +267,36 @@ class HunyuanVideoTransformer3DModel:
         # False, or ALG_GEMM_PIPE set to another schedule than 10: the row-major weights.  The prompt stream's few rows stay as they are.
         self.packed_weights = True
 
-    @classmethod
-    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8_attention=False):
-        config = config or HunyuanVideoTransformerConfig()
-        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8_attention=fp8_attention)
+    def _check_fp8_shapes(self):
+        D, M = self.config.dim, int(self.config.dim * self.config.mlp_ratio)
+        if D % 512:
+            raise ValueError("fp8=True: the norm that writes the e4m3 tokens needs D %% 512 == 0, this config has dim = %d" % D)
+        if M % 128:
+            raise ValueError("fp8=True: the e4m3 GEMM needs K %% 128 == 0, this config has dim = %d and an MLP width of %d"
+                             % (D, M))
+
+    @staticmethod
+    def _quantize_block(L, names, drop_bf16):
+        """e4m3 copies (bytes, per-output-channel float32 scales) of a block's listed linears under "<name>8"; drop_bf16: the
+        bf16 weight goes (its bias stays)."""
+        for nm in names:
+            held = getattr(L, nm)
+            wt = held[0] if isinstance(held, tuple) else held
+            q = torch.empty(wt.shape, dtype=torch.uint8, device=wt.device)
+            sc = torch.empty(wt.shape[0], dtype=torch.float32, device=wt.device)
+            _lib.quantize_fp8_rows(wt, q, sc, wt.shape[0], wt.shape[1])
+            setattr(L, nm + "8", (q, sc))
+            if drop_bf16:
+                setattr(L, nm, (None, held[1]) if isinstance(held, tuple) else None)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8_attention=False, **_):
+    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8_attention=False, fp8=False):
+        config = config or HunyuanVideoTransformerConfig()
+        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8_attention=fp8_attention,
+                   fp8=fp8)
+
+    @classmethod
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8_attention=False, fp8=False, **_):
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -252,7 +309,7 @@ class HunyuanVideoTransformer3DModel:
                                                if k in fields})
         from .weights import read_shards
         sd = read_shards(root)
-        return cls(cfg, sd, device=device, fp8_attention=fp8_attention)
+        return cls(cfg, sd, device=device, fp8_attention=fp8_attention, fp8=fp8)
 
     def to(self, *a, **k):
         return self
@@ -325,7 +382,21 @@ class HunyuanVideoTransformer3DModel:
             ws.k8s = torch.stack([Lw.k8_scale for Lw in self.dual + self.single])[:, None, :].expand(-1, N, -1).contiguous()
             ws.vt8 = torch.zeros(N, D, ws.J_pad, dtype=torch.uint8, device=dev)
             ws.vt8s = torch.empty(N, D, dtype=torch.float32, device=dev)
+        if self.fp8 and not hasattr(ws, "q8"):             # e4m3 operands of the block linears: only once the flag is on
+            cfg, dev = self.config, self.device
+            ws.q8 = torch.empty(N * ws.J, cfg.dim + int(cfg.dim * cfg.mlp_ratio), dtype=torch.uint8, device=dev)
+            ws.q8s = torch.empty(N * ((ws.J + 3) // 4 * 4), dtype=torch.float32, device=dev)
         return ws
+
+    def _fp8_weights(self):
+        """A model built in bf16 whose `fp8` attribute was set afterwards: the e4m3 weights next to the bf16 ones, made once."""
+        blocks = self.dual + self.single
+        if blocks and not hasattr(blocks[0], "wqk8"):
+            self._check_fp8_shapes()
+            for L in self.dual:
+                self._quantize_block(L, self.FP8_DUAL, drop_bf16=False)
+            for L in self.single:
+                self._quantize_block(L, self.FP8_SINGLE, drop_bf16=False)
 
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask, pooled_projections,
                  guidance=None, attention_kwargs=None, return_dict=True):
@@ -343,6 +414,12 @@ class HunyuanVideoTransformer3DModel:
         if S % 4:
             raise NotImplementedError("the joint [latents; text] layout needs a multiple of 4 latent tokens")
         L = encoder_hidden_states.shape[1]
+        fp8 = bool(self.fp8)
+        if fp8:
+            self._fp8_weights()
+        elif (self.dual + self.single) and (self.dual + self.single)[0].wqk is None:
+            raise _lib.AlgHipError("this model was built with fp8=True and holds no bf16 copy of its block weights: build it "
+                                   "with fp8=False to run (or switch between) both modes")
         ws = self._workspace(N, S, L)
         J, dev = ws.J, self.device
         tr = cfg.image_condition_type == "token_replace"
@@ -454,8 +531,40 @@ class HunyuanVideoTransformer3DModel:
             """AdaLN linear on silu(emb): `two` -> both embeddings of every sample ([N][2][n_out]), else temb only."""
             G(rows_in, lin_[0], out, (2 * N if two else N), n_out, D, D, D, n_out, bias=lin_[1])
 
-        # ---- dual-stream blocks: latent rows [0, S) and text rows [S, J) of the joint buffer ----
         AM = D + M
+        if fp8:
+            # e4m3 operands (self.fp8): every quantised linear reads ws.q8 / ws.q8s, filled in front of it by the norm itself or by
+            # the quantiser.  The scales of a batch item start at a multiple of 4 floats (the V^T GEMM reads them as B scales, 16
+            # bytes at a time): rows % 4 == 0 (the latent rows always; the joint rows of the published shapes) -> the rows of all
+            # items are contiguous and one launch covers them, otherwise one launch per item.
+            q8, q8s = ws.q8, ws.q8s
+            items_of = lambda rows: ((0, N),) if rows % 4 == 0 else tuple((n, 1) for n in range(N))
+            s4 = lambda rows: (rows + 3) // 4 * 4
+
+            def norm8(rows, mod_t, mbs, sg, sc_off, sh_off):
+                """LayerNorm + modulation of rows [0, rows) of every item of ws.x -> e4m3 rows [N * rows, D] + scales"""
+                for n0, nb in items_of(rows):
+                    T("ln_mod", _lib.layernorm_modulate_seg_fp8, ws.x, q8, q8s, None, None, mod_t, mod_t, mbs, sg, nb, rows, D, split,
+                      1e-6, x_bstride=J * D, x_off=n0 * J * D, scale_off=n0 * mbs + sc_off, shift_off=n0 * mbs + sh_off,
+                      q8_off=n0 * rows * D, q8_scale_off=n0 * s4(rows))
+
+            def quant8(rows, K_, col):
+                """columns [col, col + K_) of rows [0, rows) of every item of ws.am -> e4m3 rows [N * rows, K_] + scales"""
+                for n0, nb in items_of(rows):
+                    T("quant", _lib.quantize_fp8_rows_batched, ws.am, q8, q8s, nb, rows, K_, J * AM, AM, x_off=n0 * J * AM + col,
+                      q_off=n0 * rows * K_, scale_off=n0 * s4(rows))
+
+            def lin8(name, w8, C, rows, n_out, K_, ldc, **kw):
+                """C[n] = epilogue(q8[n] @ W^T) per batch item: A = the e4m3 tokens, rows of K_ bytes"""
+                T(name, G, q8, w8[0], C, rows, n_out, K_, K_, K_, ldc, a_scale=q8s, b_scale=w8[1], batch=N, strideA=rows * K_,
+                  strideAScale=s4(rows), **kw)
+
+            def vt8(w8, bias, rows):
+                """V^T of rows [0, rows): the weight is the A operand, the (already quantised) tokens are B"""
+                T("gemm_vt", G, w8[0], q8, ws.vt, D, rows, D, D, D, ws.J_pad, a_scale=w8[1], b_scale=q8s, strideBScale=s4(rows),
+                  bias=bias, batch=N, strideB=rows * D, strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+
+        # ---- dual-stream blocks: latent rows [0, S) and text rows [S, J) of the joint buffer ----
         use_packed = self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         PK = lambda Lw_, t: (Lw_.packed.get(id(t)) or t) if use_packed else t     # the packed copy of a block's weight, if it has one
         for bi, Lw in enumerate(self.dual):
@@ -463,15 +572,24 @@ class HunyuanVideoTransformer3DModel:
             mv = ws.mod
             ada(Lw.ada_c, ws.semb1, ws.modc, 6 * D, False)
             # shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp at +0, +D, ... of every 6D vector
-            T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, mv, mv, mod_bs, seg, N, S, D, split, 1e-6,
-              x_bstride=J * D, y_bstride=J * D, scale_off=D, shift_off=0)
+            if fp8:
+                norm8(S, mv, mod_bs, seg, D, 0)
+            else:
+                T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, mv, mv, mod_bs, seg, N, S, D, split, 1e-6,
+                  x_bstride=J * D, y_bstride=J * D, scale_off=D, shift_off=0)
             _lib.layernorm_modulate_seg(ws.x, ws.y, None, None, ws.modc, ws.modc, 6 * D, 0, N, L, D, 0, 1e-6,
                                         x_bstride=J * D, y_bstride=J * D, x_off=S * D, y_off=S * D, scale_off=D, shift_off=0)
-            T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, S, 2 * D, D, D, D, 2 * D, bias=Lw.bqk, batch=N, strideA=J * D, strideC=J * 2 * D)
+            if fp8:
+                lin8("gemm_qk", Lw.wqk8, ws.qk, S, 2 * D, D, 2 * D, bias=Lw.bqk, strideC=J * 2 * D)
+            else:
+                T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, S, 2 * D, D, D, D, 2 * D, bias=Lw.bqk, batch=N, strideA=J * D, strideC=J * 2 * D)
             G(ws.y, Lw.wqk_c, ws.qk, L, 2 * D, D, D, D, 2 * D, bias=Lw.bqk_c, batch=N, strideA=J * D, strideC=J * 2 * D,
               a_off=S * D, c_off=S * 2 * D)
-            T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, S, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
-              strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+            if fp8:
+                vt8(Lw.v8, Lw.v[1], S)
+            else:
+                T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, S, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
+                  strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
             G(Lw.v_c[0], ws.y, ws.vt, D, L, D, D, D, ws.J_pad, bias=Lw.v_c[1], batch=N, strideB=J * D,
               strideC=D * ws.J_pad, b_off=S * D, perm_col0=S, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
             # latent rows: norm_q / norm_k + rope; prompt rows: norm_added_q / norm_added_k, no rope
@@ -491,23 +609,39 @@ class HunyuanVideoTransformer3DModel:
                 _lib.headnorm_rope_(ws.qk, Lw.nq_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D)
                 _lib.headnorm_rope_(ws.qk, Lw.nk_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D + D)
             attention(bi)
-            T("gemm_out", G, ws.am, PK(Lw, Lw.o[0]), ws.x, S, D, D, AM, D, D, bias=Lw.o[1], R=ws.x, ldr=D, gate=mv, gate_off=2 * D,
-              strideGate=mod_bs, gate_seg_stride=seg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D)
+            if fp8:
+                quant8(S, D, 0)
+                lin8("gemm_out", Lw.o8, ws.x, S, D, D, D, bias=Lw.o[1], R=ws.x, ldr=D, gate=mv, gate_off=2 * D, strideGate=mod_bs,
+                     gate_seg_stride=seg, seg_split=split, strideC=J * D, strideR=J * D)
+            else:
+                T("gemm_out", G, ws.am, PK(Lw, Lw.o[0]), ws.x, S, D, D, AM, D, D, bias=Lw.o[1], R=ws.x, ldr=D, gate=mv, gate_off=2 * D,
+                  strideGate=mod_bs, gate_seg_stride=seg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D)
             G(ws.am, Lw.o_c[0], ws.x, L, D, D, AM, D, D, bias=Lw.o_c[1], R=ws.x, ldr=D, gate=ws.modc, gate_off=2 * D,
               strideGate=6 * D, gate_seg_stride=0, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D, a_off=S * AM,
               c_off=S * D, r_off=S * D)
-            T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, mv, mv, mod_bs, seg, N, S, D, split, 1e-6,
-              x_bstride=J * D, y_bstride=J * D, scale_off=4 * D, shift_off=3 * D)
+            if fp8:
+                norm8(S, mv, mod_bs, seg, 4 * D, 3 * D)
+            else:
+                T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, mv, mv, mod_bs, seg, N, S, D, split, 1e-6,
+                  x_bstride=J * D, y_bstride=J * D, scale_off=4 * D, shift_off=3 * D)
             _lib.layernorm_modulate_seg(ws.x, ws.y, None, None, ws.modc, ws.modc, 6 * D, 0, N, L, D, 0, 1e-6,
                                         x_bstride=J * D, y_bstride=J * D, x_off=S * D, y_off=S * D, scale_off=4 * D,
                                         shift_off=3 * D)
-            T("gemm_ff1", G, ws.y, PK(Lw, Lw.f1[0]), ws.am, S, M, D, D, D, AM, bias=Lw.f1[1], act=_lib.ACT_GELU_TANH, batch=N,
-              strideA=J * D, strideC=J * AM, c_off=D)
+            if fp8:
+                lin8("gemm_ff1", Lw.f18, ws.am, S, M, D, AM, bias=Lw.f1[1], act=_lib.ACT_GELU_TANH, strideC=J * AM, c_off=D)
+            else:
+                T("gemm_ff1", G, ws.y, PK(Lw, Lw.f1[0]), ws.am, S, M, D, D, D, AM, bias=Lw.f1[1], act=_lib.ACT_GELU_TANH, batch=N,
+                  strideA=J * D, strideC=J * AM, c_off=D)
             G(ws.y, Lw.f1_c[0], ws.am, L, M, D, D, D, AM, bias=Lw.f1_c[1], act=_lib.ACT_GELU_TANH, batch=N, strideA=J * D,
               strideC=J * AM, a_off=S * D, c_off=S * AM + D)
-            T("gemm_ff2", G, ws.am, PK(Lw, Lw.f2[0]), ws.x, S, D, M, AM, M, D, bias=Lw.f2[1], R=ws.x, ldr=D, gate=mv, gate_off=5 * D,
-              strideGate=mod_bs, gate_seg_stride=seg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D,
-              a_off=D)
+            if fp8:
+                quant8(S, M, D)
+                lin8("gemm_ff2", Lw.f28, ws.x, S, D, M, D, bias=Lw.f2[1], R=ws.x, ldr=D, gate=mv, gate_off=5 * D, strideGate=mod_bs,
+                     gate_seg_stride=seg, seg_split=split, strideC=J * D, strideR=J * D)
+            else:
+                T("gemm_ff2", G, ws.am, PK(Lw, Lw.f2[0]), ws.x, S, D, M, AM, M, D, bias=Lw.f2[1], R=ws.x, ldr=D, gate=mv, gate_off=5 * D,
+                  strideGate=mod_bs, gate_seg_stride=seg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D,
+                  a_off=D)
             G(ws.am, Lw.f2_c[0], ws.x, L, D, M, AM, M, D, bias=Lw.f2_c[1], R=ws.x, ldr=D, gate=ws.modc, gate_off=5 * D,
               strideGate=6 * D, gate_seg_stride=0, batch=N, strideA=J * AM, strideC=J * D, strideR=J * D, a_off=S * AM + D,
               c_off=S * D, r_off=S * D)
@@ -519,12 +653,18 @@ class HunyuanVideoTransformer3DModel:
                 G(ws.semb2, Lw.ada[0], ws.mod, 2 * N, 3 * D, D, D, D, 3 * D, bias=Lw.ada[1])       # [N][2][3D]: shift, scale, gate
             else:
                 G(ws.semb1, Lw.ada[0], ws.mod, N, 3 * D, D, D, D, 3 * D, bias=Lw.ada[1])
-            T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, ws.mod, ws.mod, smod_bs, sseg, N, J, D, split, 1e-6,
-              scale_off=D, shift_off=0)
-            T("gemm_ff1", G, ws.y, PK(Lw, Lw.mlp[0]), ws.am, N * J, M, D, D, D, AM, bias=Lw.mlp[1], act=_lib.ACT_GELU_TANH, c_off=D)
-            T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, N * J, 2 * D, D, D, D, 2 * D, bias=Lw.bqk)
-            T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, J, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
-              strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+            if fp8:   # one norm over the joint rows feeds proj_mlp, Q|K and V^T
+                norm8(J, ws.mod, smod_bs, sseg, D, 0)
+                lin8("gemm_ff1", Lw.mlp8, ws.am, J, M, D, AM, bias=Lw.mlp[1], act=_lib.ACT_GELU_TANH, strideC=J * AM, c_off=D)
+                lin8("gemm_qk", Lw.wqk8, ws.qk, J, 2 * D, D, 2 * D, bias=Lw.bqk, strideC=J * 2 * D)
+                vt8(Lw.v8, Lw.v[1], J)
+            else:
+                T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, ws.mod, ws.mod, smod_bs, sseg, N, J, D, split, 1e-6,
+                  scale_off=D, shift_off=0)
+                T("gemm_ff1", G, ws.y, PK(Lw, Lw.mlp[0]), ws.am, N * J, M, D, D, D, AM, bias=Lw.mlp[1], act=_lib.ACT_GELU_TANH, c_off=D)
+                T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, N * J, 2 * D, D, D, D, 2 * D, bias=Lw.bqk)
+                T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, J, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
+                  strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
             if f8:
                 T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
                   scale=ws.a8s, scale_bstride=J * heads)
@@ -534,9 +674,14 @@ class HunyuanVideoTransformer3DModel:
                 T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6)
                 T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, x_off=D)
             attention(bi)
-            T("gemm_out_mlp", G, ws.am, PK(Lw, Lw.out[0]), ws.x, J, D, AM, AM, AM, D, bias=Lw.out[1], R=ws.x, ldr=D, gate=ws.mod, gate_off=2 * D,
-              strideGate=smod_bs, gate_seg_stride=sseg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D,
-              strideR=J * D)
+            if fp8:   # the whole [attention | gelu(mlp)] row, ONE scale per token
+                quant8(J, AM, 0)
+                lin8("gemm_out_mlp", Lw.out8, ws.x, J, D, AM, D, bias=Lw.out[1], R=ws.x, ldr=D, gate=ws.mod, gate_off=2 * D,
+                     strideGate=smod_bs, gate_seg_stride=sseg, seg_split=split, strideC=J * D, strideR=J * D)
+            else:
+                T("gemm_out_mlp", G, ws.am, PK(Lw, Lw.out[0]), ws.x, J, D, AM, AM, AM, D, bias=Lw.out[1], R=ws.x, ldr=D, gate=ws.mod, gate_off=2 * D,
+                  strideGate=smod_bs, gate_seg_stride=sseg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D,
+                  strideR=J * D)
 
         # ---- output head: AdaLayerNormContinuous (scale | shift), projection, unpatchify ----
         G(ws.semb1, w.ada_out[0], ws.mod_out, N, 2 * D, D, D, D, 2 * D, bias=w.ada_out[1])

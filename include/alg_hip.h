@@ -216,6 +216,13 @@ int alg_gemm_fp8(const alg_gemm_args* args, void* stream);
 /* Row-wise dynamic quantisation to OCP e4m3: scale[r] = max|x[r]| / 448 (1 if the row is zero), q = e4m3(x / scale).
  * x: rows of K bf16 at stride x_rstride (elements); q: rows of K bytes, contiguous; scale: [rows] float32. */
 int alg_quantize_fp8_rows(const void* x, int64_t x_rstride, void* q, float* scale, int64_t rows, int K, void* stream);
+/* The same quantiser on rows that sit inside a wider, batch-strided bf16 buffer, all batch items in ONE launch: row r of item b
+ * starts at x + b * x_bstride + r * x_rstride (elements, both % 8 == 0; a column offset goes through the pointer); q is
+ * [batch * rows][K] contiguous, scale [batch * rows].  Bit-identical to alg_quantize_fp8_rows on each item.  K = 3072, 12288 and
+ * 15360 (HunyuanVideo's D, M and D + M) keep the row in registers and read it once; every other K % 8 == 0 takes the two-pass form.
+ * x 16-byte, q 8-byte aligned; a bad call is ALG_EINVAL before any launch. */
+int alg_quantize_fp8_rows_batched(const void* x, int64_t x_bstride, int64_t x_rstride, void* q, float* scale, int batch, int rows,
+                                  int K, void* stream);
 
 /* Full (unmasked) softmax attention, head_dim 64.
  *   q, k : bf16, element (b, s, h, d) at  base + b*q_bstride + s*q_rstride + h*64 + d   (same strides for k)
@@ -515,6 +522,12 @@ int alg_layernorm_modulate_seg(const void* x, void* y, const void* weight, const
 int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
                                const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows, int D,
                                int64_t x_bstride, int seg_split, float eps, void* stream);
+/* alg_layernorm_modulate_seg in front of an fp8 GEMM: the explicit distance between the two segments' vectors (seg_stride,
+ * elements, % 8 == 0; 0 = one vector for all rows), otherwise alg_layernorm_modulate_fp8 -- bit for bit alg_layernorm_modulate_seg
+ * into bf16 followed by alg_quantize_fp8_rows.  HunyuanVideo's latent / joint rows with token-replace modulation. */
+int alg_layernorm_modulate_seg_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
+                                   const void* scale, const void* shift, int64_t mod_bstride, int64_t seg_stride, int batch,
+                                   int rows, int D, int64_t x_bstride, int seg_split, float eps, void* stream);
 
 /* In place on qk: [batch][S][2][heads][64] bf16 (q then k per token):
  * per-head LayerNorm(64) with (wq,bq) / (wk,bk), then RoPE (cos/sin fp32 [S - text_len][64], interleaved-pair
