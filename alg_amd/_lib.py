@@ -31,7 +31,7 @@ EXPORTS = (
     "alg_vae_pack_latent", "alg_vae_unpack_video", "alg_vae_group_norm", "alg_vae_pad", "alg_vae_repitch",
     "alg_vae_unpack_planes", "alg_rms_norm_rows", "alg_softmax_hilo", "alg_flash_attn_d128_ex", "alg_flash_attn_d128_dual", "alg_rope_half", "alg_patchify_t", "alg_unpatchify_t", "alg_qk_norm_rope_scaled", "alg_flash_attn_d64_ex", "alg_embed_rows", "alg_t5_layernorm", "alg_attn_bias", "alg_mul_bf16", "alg_quick_gelu",
     "alg_lowpass_tables_bytes", "alg_lowpass_tables_build", "alg_down_up_workspace_bytes", "alg_gaussian_blur_workspace_bytes",
-    "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap",
+    "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap", "alg_attn_path_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched",
 )
@@ -189,9 +189,10 @@ def load_library():
     lib.alg_timestep_embedding.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]
     lib.alg_calib_mfma_bf16.argtypes = [c_void_p, c_int, ctypes.c_uint, c_int, c_void_p, c_void_p]
     lib.alg_attn_clock_tap.argtypes = [c_void_p, c_int]
+    lib.alg_attn_path_tap.argtypes = [c_void_p]
     for name in EXPORTS:
         fn = getattr(lib, name)
-        if name == "alg_attn_clock_tap":
+        if name in ("alg_attn_clock_tap", "alg_attn_path_tap"):
             fn.restype = None
         elif name not in ("alg_version", "alg_last_error", "alg_reload_env"):
             fn.restype = c_int64 if name in _RET_I64 else c_int
@@ -349,6 +350,19 @@ def attn_clock_tap(buffer):
     if not (buffer.is_cuda and buffer.dtype == torch.int64 and buffer.is_contiguous() and buffer.dim() == 2 and buffer.shape[1] == 4):
         raise AlgHipError("attn_clock_tap needs a contiguous int64 device tensor [slots, 4]")
     lib.alg_attn_clock_tap(_ptr(buffer), int(buffer.shape[0]))
+
+
+def attn_path_tap(buf):
+    """buf: zeroed int64 device tensor [3] = {statement entries, tiles inside the statement, tiles in the straight loop}, summed over
+    the waves of every d = 64 pipe-kernel launch while it is registered (or None to switch the counters off) -- see
+    include/alg_hip.h: alg_attn_path_tap."""
+    lib = load_library()
+    if buf is None:
+        lib.alg_attn_path_tap(None)
+        return
+    if not (buf.is_cuda and buf.dtype == torch.int64 and buf.is_contiguous() and buf.dim() == 1 and buf.shape[0] == 3):
+        raise AlgHipError("attn_path_tap needs a contiguous int64 device tensor [3]")
+    lib.alg_attn_path_tap(_ptr(buf))
 
 
 def clock_mhz_from_taps(taps, wall_khz):

@@ -53,6 +53,7 @@
 
 #include "common.h"
 #include "attn_pipe_loop.inc"
+#include "attn_pipe_off_loop.inc"
 
 namespace alg {
 
@@ -80,6 +81,7 @@ struct AttnP {
   int prio;      // 1: the younger half of an 8-wave workgroup (waves 4-7) runs at s_setprio 1 (ALG_ATTN_PRIO, A/B knob)
   uint64_t* clk;   // clock tap (calibrate.hip: alg_attn_clock_tap) or NULL: {cycles, wall} at start / end of every 64th workgroup
   int clk_slots;
+  uint64_t* path;  // path counters (calibrate.hip: alg_attn_path_tap) or NULL: {statement entries, tiles inside, tiles straight}
 };
 
 struct Frag {
@@ -732,8 +734,15 @@ __global__ __launch_bounds__(256) void flash_attn_d64_merge_kernel(const AttnP p
 // Row sums are plain fp32 adds of the unrounded probabilities inside the statement (v_dot2c does not hide behind an MFMA),
 // the bf16-rounded dot2 sums of softmax_tile_zero outside it.
 // ---------------------------------------------------------------------------------------------------------------
-template <int NW>
+//
+// OFF (ALG_ATTN_PP=8, NW = 8 only): the offset form of the statement (attn_pipe_off_loop.inc).  The scores leave the matrix pipe as
+// s - m -- the wave hands in -m of each lane's query and the statement makes it srcC of the first QK k-step -- so a wave enters
+// whatever its rows' offsets are (the first-tile snap to zero stays: rows that snap under 4 still do), and after a refused tile
+// (code 1: the exact path in C++, which may move m) it runs the straight form up to the next t = 1 (mod 4) with t + 4 <= tend
+// and enters again with the new offset.  One loop, one copy of the straight body and of the statement.
+template <int NW, bool OFF = false>
 __global__ __launch_bounds__(NW * 64) void flash_attn_d64_pipe_kernel(const AttnP p) {
+  static_assert(!OFF || NW == 8, "the offset statement exists in the 8-wave form only");
   // NW = 4 (default): four waves x 32 queries, the statement names v[64:165] and a[0:79] (252 registers), two of these
   // workgroups (2 x 64 KiB of LDS) share a CU.  NW = 8 (ALG_ATTN_PP=4): one 256-query unit per workgroup, half the L2 -> LDS
   // traffic per MFMA; hipcc grants an 8-wave workgroup 128 + 128 registers per lane, so that form of the statement lives in
@@ -838,8 +847,9 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d64_pipe_kernel(const Attn
   // the statement only runs iterations t whose DMA target K(t + 3) is a whole tile (its sources are not clamped) and whose
   // tile t + 1 needs no mask
   const int tend = ragged ? T - 4 : T - 3;
-  int t = 1;
+  int t = OFF ? 0 : 1;
   bool top_done = false;
+  int n_ent = 0, n_in = 0;   // path counters: statement entries, tiles run inside the statement
   {
     const LaneCtx c = make_ctx(fresh_lane());
     stage_k(c, 0);
@@ -848,9 +858,57 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d64_pipe_kernel(const Attn
     stage_v(c, 0);       // (filler: four DMAs per batch)
     stage_k(c, 2);       // the batch "iteration -1" would have issued: K(2), V(1)
     stage_v(c, 1);
-    straight(c, 0, 1, false);     // tile 0: establishes the running offset (snapped to zero when its scores allow)
+    if constexpr (!OFF) straight(c, 0, 1, false);     // tile 0: establishes the running offset (snapped to zero when its scores allow)
   }
-  if (1 + 4 <= tend && __all(m_run == 0.0f)) {
+  if constexpr (OFF) {
+    for (;;) {
+      // straight form up to the next entry point: the smallest ta = 1 (mod 4) behind the tile that has to be (re)done here -- tile 0
+      // (establishes the offset, snapped to zero when its scores allow) or a tile the statement refused -- or to the end
+      const int tt = top_done ? t + 1 : t;
+      const int ta = tt + ((1 - tt) & 3);
+      const bool enter = ta + 4 <= tend;
+      {
+        const LaneCtx c = make_ctx(fresh_lane());
+        straight(c, t, enter ? ta : T, top_done);
+      }
+      if (!enter) break;
+      t = ta;
+      const LaneCtx c = make_ctx(fresh_lane());
+      auto sreg = [](int v) -> int { return __builtin_amdgcn_readfirstlane(v); };
+      auto uniform64 = [](const void* ptr) -> uint64_t {
+        const uint64_t v = (uint64_t)(uintptr_t)ptr;
+        return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+               (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+      };
+      // (no V^T fragment addresses: the statement reads the V^T ring through lk + 4 * ATT_TILE -- v_ring = k_ring + 32 KiB above)
+      const uint32_t kl = (uint32_t)(uintptr_t)(lptr_t)k_ring, vl = (uint32_t)(uintptr_t)(lptr_t)v_ring;
+      const int lk0 = kl + c.f.row_off + (((0 + c.h2) ^ c.f.sw) * 16), lk1 = kl + c.f.row_off + (((2 + c.h2) ^ c.f.sw) * 16);
+      const int lk2 = kl + c.f.row_off + (((4 + c.h2) ^ c.f.sw) * 16), lk3 = kl + c.f.row_off + (((6 + c.h2) ^ c.f.sw) * 16);
+      int kvo0 = (int)(((int64_t)((t + 3) * KVB + c.srow) * p.q_rs + c.sslot * 8) * 2);
+      int vvo0 = (int)(((int64_t)c.srow * p.vt_rs + c.sslot * 8 + (t + 2) * KVB) * 2);
+      const int qvo = (int)(((int64_t)min(c.q_row, S - 1) * p.q_rs + c.h2 * 8) * 2);
+      const uint64_t kb = uniform64(K), vb = uniform64(VT), qbs = uniform64(Q);
+      const int kstep = sreg((int)(KVB * p.q_rs * 2)), tend_s = sreg(tend);
+      const int wk = sreg((int)kl + wave * 1024), wv = sreg((int)vl + wave * 1024);
+      int ts = sreg(t), code;
+      float negm = 0.0f - m_run;   // (+0 for a snapped row: the first k-step then starts from what the zero-offset form starts from)
+      float o[32];
+#pragma unroll
+      for (int i = 0; i < 32; ++i) o[i] = oa[i >> 4][i & 15];
+      asm volatile(ALG_ATTN_PIPE8_OFF_LOOP_ASM
+                   : ALG_ATTN_PIPE8_OFF_O_OPERANDS(o), [l] "+v"(l_run), [t] "+s"(ts), [code] "=&s"(code), [kvo0] "+v"(kvo0),
+                     [vvo0] "+v"(vvo0), [negm] "+v"(negm)
+                   : [lk0] "v"(lk0), [lk1] "v"(lk1), [lk2] "v"(lk2), [lk3] "v"(lk3), [qvo] "v"(qvo), [kb] "s"(kb), [vb] "s"(vb),
+                     [qb] "s"(qbs), [kstep] "s"(kstep), [tend] "s"(tend_s), [wk] "s"(wk), [wv] "s"(wv)
+                   : "memory", "vcc", "scc", ALG_ATTN_PIPE8_OFF_CLOBBERS);
+#pragma unroll
+      for (int i = 0; i < 32; ++i) oa[i >> 4][i & 15] = o[i];
+      m_run = 0.0f - negm;   // (travels through the statement in its operand: nothing of the frame's is live across it)
+      n_ent += 1, n_in += ts - t;
+      t = ts;
+      top_done = code != 0;   // 1: iteration t's protocol is done, softmax(t) is not: tile t is redone at the top of the loop
+    }
+  } else if (1 + 4 <= tend && __all(m_run == 0.0f)) {
     const LaneCtx c = make_ctx(fresh_lane());
     auto sreg = [](int v) -> int { return __builtin_amdgcn_readfirstlane(v); };
     auto uniform64 = [](const void* ptr) -> uint64_t {
@@ -894,11 +952,12 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d64_pipe_kernel(const Attn
     }
 #pragma unroll
     for (int i = 0; i < 32; ++i) oa[i >> 4][i & 15] = o[i];
+    n_ent = 1, n_in = ts - t;
     t = ts;
     top_done = code != 0;   // 1: iteration t's protocol is done, softmax(t) is not: tile t is redone below
   }
   LaneCtx c = make_ctx(fresh_lane());
-  straight(c, t, T, top_done);   // the tiles behind the statement (or all of them but tile 0)
+  if constexpr (!OFF) straight(c, t, T, top_done);   // the tiles behind the statement (or all of them but tile 0)
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
   const float inv = 1.0f / l_tot;
@@ -918,6 +977,14 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d64_pipe_kernel(const Attn
   if (tap && c.lane == 0) {
     uint64_t* cp = p.clk + (size_t)(blockIdx.x >> 6) * 4;   // one workgroup owns a slot (block / 64 < slots)
     cp[0] = tap_c0, cp[1] = tap_r0, cp[2] = __builtin_readcyclecounter(), cp[3] = wall_clock64();
+  }
+  if (p.path != nullptr) {   // uniform
+    if (c.lane == 0) {
+      unsigned long long* pc = (unsigned long long*)p.path;
+      atomicAdd(pc + 0, (unsigned long long)n_ent);
+      atomicAdd(pc + 1, (unsigned long long)n_in);
+      atomicAdd(pc + 2, (unsigned long long)(T - n_in));
+    }
   }
 }
 
@@ -981,6 +1048,9 @@ static void launch_main41(dim3 g, dim3 blk, hipStream_t s, const alg::AttnP& p) 
     case 7:   // a call flash_attn_d64_m16() declined (fewer than 12 KV tiles, 31-bit offsets, V^T pitch): the 32x32x16 statement kernel
       hipLaunchKernelGGL(alg::flash_attn_d64_pipe_kernel<8>, g, dim3(512), 0, s, p);
       break;
+    case 8:   // the same statement for any running offset; waves return to it after a refused tile
+      hipLaunchKernelGGL((alg::flash_attn_d64_pipe_kernel<8, true>), g, dim3(512), 0, s, p);
+      break;
     default: hipLaunchKernelGGL((alg::flash_attn_d64_kernel<41, 8>), g, blk, 0, s, p); break;
   }
 }
@@ -1037,6 +1107,7 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
   p.scale_log2 = (flags & ALG_ATTN_Q_PRESCALED) ? 1.0f : scale * 1.4426950408889634f;  // m is in log2 units already
   p.prio = 0;
   p.clk = clock_tap_for((hipStream_t)stream, &p.clk_slots);
+  p.path = path_tap_for((hipStream_t)stream);
   const int nbh = batch * heads;
   const int64_t grid = (int64_t)((nbh + 7) / 8) * 8 * p.q_blocks;
   const dim3 blk(nw * 64);

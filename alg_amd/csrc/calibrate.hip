@@ -15,6 +15,7 @@ namespace alg {
 
 std::atomic<uint64_t*> g_clock_tap{nullptr};
 std::atomic<int> g_clock_tap_slots{0};
+std::atomic<uint64_t*> g_path_tap{nullptr};
 
 __device__ __forceinline__ unsigned hashu(unsigned x) {
   x ^= x >> 16;
@@ -104,3 +105,8 @@ extern "C" void alg_attn_clock_tap(uint64_t* buffer, int slots) {
   g_clock_tap_slots.store(buffer ? slots : 0, std::memory_order_relaxed);
   g_clock_tap.store(slots > 0 ? buffer : nullptr, std::memory_order_release);
 }
+
+/* Path counters of the d = 64 pipe kernels (flash_attn_d64_pipe_kernel, ALG_ATTN_PP 4 and 8): while `buffer` is non-NULL every
+ * wave of every launch adds, at its end, {entries into the asm statement, KV tiles run inside it, KV tiles run in the C++ straight
+ * loop} to buffer[0..2] (uint64, atomicAdd from one lane).  Results are unaffected.  NULL (the default) switches it off. */
+extern "C" void alg_attn_path_tap(uint64_t* buffer) { g_path_tap.store(buffer, std::memory_order_release); }

@@ -21,7 +21,8 @@ enum Opt {
   OPT_ATTN_SPLIT_TAIL,  // ALG_ATTN_SPLIT_TAIL   1 (default) | 0: the d = 64 attention as a single launch (no split-KV tail)
   OPT_ATTN_PP,          // ALG_ATTN_PP           4 (8-wave pipelined main launch, v_mfma_f32_32x32x16_bf16) | 7: the same construction on
                         //                       v_mfma_f32_16x16x32_bf16 (attention64_m16.hip; a call it declines runs the default, 4) |
-                        //                       0: the straight loop
+                        //                       8: statement 4 for ANY running offset (-m as srcC of the first QK k-step; waves
+                        //                       re-enter after a bail-out) | 0: the straight loop
   OPT_ATTN_VARIANT,     // ALG_ATTN_VARIANT      33 (default: lazy running max) | 1: exact running max, fp32 row sums
   OPT_ATTN128_PIPE,     // ALG_ATTN128_PIPE      1 (default: pipelined d = 128 kernel) | 0: the straight loop
   OPT_ATTN128_Q64,      // ALG_ATTN128_Q64       1 (default: 64-queries-per-wave kernel for >= 4,096 keys) | 2: for every call it can
@@ -81,6 +82,17 @@ inline uint64_t* clock_tap_for(hipStream_t s, int* slots) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
   *slots = n;
+  return c;
+}
+
+// Path counters of the d = 64 pipe kernels (calibrate.hip: alg_attn_path_tap): {statement entries, tiles inside the statement,
+// tiles in the straight loop}, three uint64 summed over the waves of every launch.  Same capture rule as the clock tap.
+extern std::atomic<uint64_t*> g_path_tap;
+inline uint64_t* path_tap_for(hipStream_t s) {
+  uint64_t* c = g_path_tap.load(std::memory_order_acquire);
+  if (!c) return nullptr;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(s, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
   return c;
 }
 

@@ -42,8 +42,9 @@ const char* alg_last_error(void);
  * A host that changes one of them afterwards calls alg_reload_env() (host-only, no GPU work; not to be called while another
  * thread is inside the library).  The default build knows seven, each selecting between bit-identical or documented-equivalent
  * schedules (README.md "Run-time options"): ALG_ATTN_SPLIT_TAIL, ALG_ATTN_PP (4 = the 8-wave pipelined statement on v_mfma_f32_32x32x16_bf16, 7 = the same construction on
- * v_mfma_f32_16x16x32_bf16 -- a call it declines (fewer than 12 KV tiles, 31-bit offsets, V^T pitch) runs the default, 4 --, 0 = the
- * straight loop), ALG_ATTN_VARIANT, ALG_ATTN128_PIPE,
+ * v_mfma_f32_16x16x32_bf16 -- a call it declines (fewer than 12 KV tiles, 31-bit offsets, V^T pitch) runs the default, 4 --, 8 = statement 4 for any running
+ * softmax offset: -m enters the fp32 accumulation as srcC of the first QK k-step and a wave returns to the statement after a
+ * refused tile; bit-identical to 4 while every offset snaps to zero --, 0 = the straight loop), ALG_ATTN_VARIANT, ALG_ATTN128_PIPE,
  * ALG_ATTN128_Q64 (1 = the 64-queries-per-wave d = 128 kernel from 4,096 keys on, the default; 2 = for every call it can
  * take; 0 = off: the escape hatch back to the 32-query pipelined kernel), ALG_GEMM_PIPE, ALG_LOWPASS_PATH.  A value must be
  * a whole decimal integer the build knows; anything else (including "off", "1x", an empty string) leaves the default in
@@ -592,6 +593,14 @@ int alg_wall_clock_khz(void);
  * into the graph and outlive the buffer).  Host-only call; NULL (the default) switches the taps off; the caller keeps the
  * buffer alive until it has done so. */
 void alg_attn_clock_tap(uint64_t* buffer, int slots);
+
+/* Path counters of the pipelined d = 64 attention (ALG_ATTN_PP 4 and 8).  While `buffer` (device memory, three uint64, zeroed by
+ * the caller) is non-NULL, every wave of every launch adds at its end, with atomicAdd from one lane: buffer[0] += entries into the
+ * asm statement, buffer[1] += KV tiles run inside the statement, buffer[2] += KV tiles run in the C++ straight loop (tile 0, the
+ * tail, refused tiles and the tiles up to the next entry point).  Per wave [1] + [2] = the number of KV tiles.  Results are
+ * unaffected; with no buffer the cost is one uniform branch per wave.  Capture rule, lifetime and threading as
+ * alg_attn_clock_tap.  Host-only call; NULL (the default) switches the counters off. */
+void alg_attn_path_tap(uint64_t* buffer);
 
 #ifdef __cplusplus
 }

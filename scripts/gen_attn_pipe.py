@@ -38,6 +38,19 @@ k-step (ring base included; slot and sub-tile are immediates), kvo0/1, vvo0/1 "+
 srow + 32) into the K / V^T panels AT TILE (t + 3) / (t + 2) of the entry iteration (advanced inside), qvo "v" byte offset of the lane's Q row, kb / vb /
 qb "s" 64-bit panel bases, kstep "s" bytes per K tile, tend "s" (whole groups of four run while t + 4 <= tend; the caller guarantees t + 3 < T inside),
 wk / wv "s" = LDS byte address of the K / V^T ring + wave * 1024 (DMA destination of this wave).
+
+Offset mode (configure(8, offset=True) -> attn_pipe_off_loop.inc, ALG_ATTN_PIPE8_OFF_*; attention.hip, ALG_ATTN_PP=8): the same
+8-wave statement for waves whose rows keep a NON-ZERO running offset m (first-tile scores beyond +-64 log2 units).  In the
+S^T = K Q^T layout the 16 accumulator values a lane holds of a 32 x 32 block all belong to ONE query, so -m rides in as srcC of the
+first QK k-step of both sub-tiles (that k-step starts from C = 0 in the zero-offset form): the scores come out of the matrix pipe as
+s - m, with -m FIRST in the fp32 accumulation chain, and the softmax mix, the DMA / barrier protocol, `code` and the 2^80 exit are
+unchanged -- no VALU instruction is added to the loop.  m does not change inside the statement (the lazy max stays the frame's).
+One extra operand: negm "+v" = -m of the lane's query (never written: "+" so that the frame reads its m back from it and keeps no
+register of its own live across the statement); the warm-up copies it into the literal block v[10:25] (16 v_mov_b32 per entry).  The block has to be ArchVGPRs: a VOP3P-MAI instruction has ONE bit for the register file of srcC and vdst together, the
+scores must land in ArchVGPRs (v_exp_f32 reads no AccVGPR), so an AccVGPR srcC cannot be encoded with them.  The 16 registers come
+out of the frame's share v[0:25]: the four V^T fragment addresses lv0..lv3 are dropped -- the V^T ring lies 32 KiB behind the K ring
+in one LDS block, and 32768 + slot * 8192 + half * 4096 still fits the 16-bit offset field of ds_read_b128 -- which leaves nine
+"v" operands (l, kvo0, vvo0, qvo, lk0..lk3, negm) for v[0:9].
 """
 import os
 
@@ -47,14 +60,17 @@ NO_NOP = os.environ.get("ATTN_PIPE_NO_NOP", "0") == "1"           # experiment k
 SUM16 = os.environ.get("ATTN_PIPE_SUM16", "0") == "1"             # experiment knob (round 5, TIMING ONLY -- wrong row sums): row sums on the matrix pipe
 LACC, ONES = 80, 84            # (SUM16) AccVGPRs: 16x16 row-sum accumulator, the selector A operand
 NW = 4                         # waves per workgroup (configure())
+OFFSET = False                 # offset mode (configure(8, offset=True)): -m as srcC of the first QK k-step
+NEGM, V_RING = 10, 32768       # offset mode: v[10:25] = -m of the lane's query; LDS distance K ring -> V^T ring
 
 
-def configure(nw):
+def configure(nw, offset=False):
     """4-wave form: ArchVGPRs v[64:165], O exchanged through 32 "+v" operands, two DMA pieces per wave, tile and operand.
     8-wave form (one 256-query unit per workgroup, half the L2 -> LDS traffic per MFMA): hipcc grants such a workgroup 128 + 128
     registers per lane, so the statement's ArchVGPRs are v[26:127] and O travels in 32 "+a" operands (v_accvgpr_mov)."""
-    global SA, SB, PA, PB, TS, E0, E1, E2, E3, SCR, NW, VBASE
-    NW = nw
+    global SA, SB, PA, PB, TS, E0, E1, E2, E3, SCR, NW, VBASE, OFFSET
+    assert nw == 8 or not offset
+    NW, OFFSET = nw, offset
     VBASE = 64 if nw == 4 else 26
     SA, SB, PA, PB = VBASE, VBASE + 32, VBASE + 64, VBASE + 80
     TS, E0, E1, E2, E3, SCR = (VBASE + 96 + i for i in range(6))
@@ -71,6 +87,8 @@ ar = lambda i, n: "a[%d:%d]" % (i, i + n - 1)
 def frag_read(buf, which, slot, half, kstep):
     """ds_read_b128 of one fragment: K (which = 'k') sub-tile `half` k-step `kstep`, or V^T d-tile `half` kv block `kstep`"""
     # address = lane part(kstep) (carries the ring base) + slot * TILE + half * 4096
+    if OFFSET and which == "v":     # no lv operands: the V^T ring through the K fragment address (same lane part) + 32 KiB
+        return "ds_read_b128 %s, %%[lk%d] offset:%d" % (ar(FR + 4 * buf, 4), kstep, V_RING + slot * TILE + half * 4096)
     return "ds_read_b128 %s, %%[l%s%d] offset:%d" % (ar(FR + 4 * buf, 4), which, kstep, slot * TILE + half * 4096)
 
 
@@ -169,7 +187,7 @@ def iteration(phase, X, Y, U, W, pv=True, softmax=True, qk=True, reads_in_flight
         fr = ar(FR + 4 * (j % 8), 4)
         if kind == "k":
             acc = vr(Y + 16 * half, 16)
-            c = acc if seen_first["k%d" % half] else "0"
+            c = acc if seen_first["k%d" % half] else (vr(NEGM, 16) if OFFSET else "0")
             seen_first["k%d" % half] = True
             lines.append("v_mfma_f32_32x32x16_bf16 %s, %s, %s, %s" % (acc, fr, ar(Q + 4 * kstep, 4), c))
         else:
@@ -224,6 +242,8 @@ def emit():
     # ---- warm-up at phase 1: top protocol, QK(t) alone into X = SA (K(t) sits in slot 1 = the "next" slot of phase 0) ----
     if SUM16:
         L += ["v_accvgpr_write_b32 a%d, 0" % (LACC + i) for i in range(4)] + ["v_mov_b32 %s, 0x3f803f80" % v(SCR)] + ["v_accvgpr_write_b32 a%d, %s" % (ONES + i, v(SCR)) for i in range(4)]
+    if OFFSET:
+        L += ["v_mov_b32 %s, %%[negm]" % v(NEGM + i) for i in range(16)]   # under the latency of the Q loads
     L += ["s_waitcnt vmcnt(0) lgkmcnt(0)"]   # Q (and, once, whatever the caller had in flight)
     L += top_protocol(1)
     X, Y, U, W = roles[1]
@@ -256,6 +276,19 @@ def emit():
     return L
 
 
+def write_form(f, tag):
+    lines = emit()
+    f.write("#define ALG_ATTN_PIPE%s_LOOP_ASM \\\n" % tag)
+    for ln in lines:
+        f.write('  "%s\\n\\t" \\\n' % ln)
+    f.write('  ""\n')
+    regs = ["a%d" % i for i in range(88 if SUM16 else 80)] + ["v%d" % i for i in range(NEGM if OFFSET else VBASE, VBASE + 102)]
+    f.write("#define ALG_ATTN_PIPE%s_CLOBBERS \\\n  " % tag + ", ".join('"%s"' % r for r in regs) + '\n')
+    f.write("#define ALG_ATTN_PIPE%s_O_OPERANDS(o) \\\n  " % tag +
+            ", ".join('[o%d] "+%s"(o[%d])' % (i, "v" if NW == 4 else "a", i) for i in range(32)) + '\n')
+    return lines
+
+
 def main():
     here = os.path.dirname(os.path.abspath(__file__))
     path = os.environ.get("ATTN_PIPE_OUT") or os.path.join(here, "..", "alg_amd", "csrc", "attn_pipe_loop.inc")
@@ -263,16 +296,15 @@ def main():
         f.write("// GENERATED by scripts/gen_attn_pipe.py -- do not edit.  Steady-state KV loop of the pipelined d = 64 attention.\n")
         for nw, tag in ((4, ""), (8, "8")):
             configure(nw)
-            lines = emit()
-            f.write("#define ALG_ATTN_PIPE%s_LOOP_ASM \\\n" % tag)
-            for ln in lines:
-                f.write('  "%s\\n\\t" \\\n' % ln)
-            f.write('  ""\n')
-            regs = ["a%d" % i for i in range(88 if SUM16 else 80)] + ["v%d" % i for i in range(VBASE, VBASE + 102)]
-            f.write("#define ALG_ATTN_PIPE%s_CLOBBERS \\\n  " % tag + ", ".join('"%s"' % r for r in regs) + '\n')
-            f.write("#define ALG_ATTN_PIPE%s_O_OPERANDS(o) \\\n  " % tag +
-                    ", ".join('[o%d] "+%s"(o[%d])' % (i, "v" if nw == 4 else "a", i) for i in range(32)) + '\n')
+            lines = write_form(f, tag)
             print("wrote", os.path.normpath(path), "form", nw, len(lines), "lines,", sum(1 for l in lines if l.startswith("v_mfma")), "MFMAs")
+    path = os.environ.get("ATTN_PIPE_OFF_OUT") or os.path.join(here, "..", "alg_amd", "csrc", "attn_pipe_off_loop.inc")
+    with open(path, "w") as f:
+        f.write("// GENERATED by scripts/gen_attn_pipe.py -- do not edit.  The 8-wave statement of the pipelined d = 64 attention for any\n"
+                "// running offset: -m is srcC of the first QK k-step (ALG_ATTN_PP=8).\n")
+        configure(8, offset=True)
+        lines = write_form(f, "8_OFF")
+        print("wrote", os.path.normpath(path), "offset form", len(lines), "lines,", sum(1 for l in lines if l.startswith("v_mfma")), "MFMAs")
     configure(4)
 
 
