@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <initializer_list>
 #include <stdio.h>
 
 #include "../../include/alg_hip.h"
@@ -51,6 +52,22 @@ inline bool device_done(const PerDeviceOnce& o, int slot) {
 }
 inline void device_mark(PerDeviceOnce& o, int slot) {
   if (slot >= 0) o.mask.fetch_or(1ull << slot, std::memory_order_release);
+}
+
+// The opt-in itself: `lds` bytes of dynamic LDS for every kernel of `fns` on the current device, once; `entry` names the C
+// entry in the message.
+inline int opt_in_lds(PerDeviceOnce& once, std::initializer_list<const void*> fns, int lds, const char* entry) {
+  const int slot = current_device_slot();
+  if (device_done(once, slot)) return ALG_OK;
+  for (const void* fn : fns) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) {
+      set_error("%s: hipFuncSetAttribute(%d B LDS): %s", entry, lds, hipGetErrorString(e));
+      return ALG_ELAUNCH;
+    }
+  }
+  device_mark(once, slot);
+  return ALG_OK;
 }
 
 // Compute units of the current device (256 on an MI355X; fewer in a partitioned mode or on another SKU), cached per device: the

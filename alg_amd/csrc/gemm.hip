@@ -1,39 +1,46 @@
-// C ABI entry of the bf16 GEMM: argument validation and schedule dispatch.  The kernel template lives in gemm_kernel.h; one
-// translation unit per schedule (gemm_p0.hip, gemm_p6.hip, gemm_p7.hip, gemm_p8.hip, gemm_p9.hip) instantiates it.
+// C ABI entry of the bf16 / e4m3 GEMM: argument check, route plan, launch.  The kernel template lives in gemm_kernel.h; one
+// translation unit per schedule and operand form (gemm_p6.hip, gemm_p6_fp8.hip, gemm_p6_conv.hip, gemm_p9.hip, gemm_p9_fp8.hip,
+// gemm_p10.hip, gemm_p11.hip) instantiates it.
 #include <stdlib.h>
 
 #include "common.h"
 
 namespace alg {
 constexpr int BM = 256, BN = 256;
-int launch_gemm_p6(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
-int launch_gemm_p9(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
-int launch_gemm_p9_pair(const alg_gemm_args* a, int m_tiles_a, int n_tiles_a, const alg_gemm_args* b, int m_tiles_b, int n_tiles_b,
-                        hipStream_t s);
-int launch_gemm_p9_pair_qk(const alg_gemm_args* a, int m_tiles_a, int n_tiles_a, const alg_gemm_args* b, int m_tiles_b, int n_tiles_b,
+typedef int launch_one_fn(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
+// two problems in one launch; e: the QK LayerNorm + rotary arguments of alg_gemm_bf16_pair_qk, null for the plain pair
+typedef int launch_pair_fn(const alg_gemm_args* a, int m_tiles_a, int n_tiles_a, const alg_gemm_args* b, int m_tiles_b, int n_tiles_b,
                            const alg_qk_norm_rope_args* e, hipStream_t s);
-int launch_gemm_p10(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
-int launch_gemm_p10_pair(const alg_gemm_args* a, int m_tiles_a, int n_tiles_a, const alg_gemm_args* b, int m_tiles_b, int n_tiles_b,
-                         hipStream_t s);
-int launch_gemm_p10_pair_qk(const alg_gemm_args* a, int m_tiles_a, int n_tiles_a, const alg_gemm_args* b, int m_tiles_b, int n_tiles_b,
-                            const alg_qk_norm_rope_args* e, hipStream_t s);
-int launch_gemm_p11(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
-int launch_gemm_p6_fp8(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
-int launch_gemm_p9_fp8(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
-int launch_gemm_p6_conv(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s);
+launch_one_fn launch_gemm_p6, launch_gemm_p6_conv, launch_gemm_p6_fp8, launch_gemm_p9, launch_gemm_p9_fp8, launch_gemm_p10, launch_gemm_p11;
+launch_pair_fn launch_gemm_p9_pair, launch_gemm_p10_pair;
 // ALG_GEMM_PIPE: 10 (default since round 6: schedule 9's 4-wave asm main loop on v_mfma_f32_16x16x32_bf16, the shape that
 // sustains ~10 % more under the package power cap; fp32 rounding points differ from 9 / 6: 32 products per instruction) | 9 (the
 // asm main loop on 32x32x16; round 3: faster than the 8-wave ping-pong on all five C2 shapes) | 6 (the 8-wave ping-pong;
-// bit-identical to 9).  Calls the asm loops cannot take (K < 128, byte offsets past 32 bits) and the convolution operands run
-// schedule 6; e4m3 operands run schedule 9's e4m3 loop under 9 and 10.  A packed B (ALG_GEMM_B_PACKED11) runs schedule 11 under
-// every ALG_GEMM_PIPE; the e4m3 and convolution forms refuse it.
+// bit-identical to 9).  Calls the asm loops cannot take (fewer than two k-tiles, byte offsets past 32 bits) and the convolution
+// operands run schedule 6; e4m3 operands run schedule 9's e4m3 loop under 9 and 10.  A packed B (ALG_GEMM_B_PACKED11) runs
+// schedule 11 under every ALG_GEMM_PIPE; the e4m3 and convolution forms refuse it.
 static int gemm_pipe() { return opt(OPT_GEMM_PIPE); }
-static bool asm_pipe() { return gemm_pipe() == 9 || gemm_pipe() == 10; }
+
+// What the asm main loops (schedules 9, 10, 11) need of an operand with row pitch ld and esz bytes per element: two k-tiles
+// of 128 bytes per row, and 32-bit byte offsets inside a 256-row panel.
+static bool asm_loop_takes(int K, int64_t ld, int64_t esz) {
+  return K * esz >= 256 && 256 * ld * esz + K * esz < (1ll << 32);
+}
+
+enum GemmRoute { ROUTE_P6, ROUTE_P6_CONV, ROUTE_P6_FP8, ROUTE_P9, ROUTE_P9_FP8, ROUTE_P10, ROUTE_P11 };
+struct GemmPlan {
+  GemmRoute route;
+  int m_tiles, n_tiles;
+  int64_t nwg;     // workgroups of a one-tile-per-workgroup grid
+  bool slabs;      // 32-bit epilogue offsets do not cover M rows: cut along M, one launch per slab
+  bool pairable;   // may ride in a pair launch (schedules 9 / 10)
+};
 }  // namespace alg
 
 using namespace alg;
 
-static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool validate_only = false) {
+// Every argument error of the GEMM entries.  Runs on the WHOLE call (and on both problems of a pair) before anything is launched.
+static int gemm_check(const alg_gemm_args* a, bool fp8) {
   if (!a || !a->A || !a->B || !a->C) {
     set_error("alg_gemm_bf16: null argument");
     return ALG_EINVAL;
@@ -98,8 +105,8 @@ static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool valid
     }
   }
   if (a->flags & ALG_GEMM_B_PACKED11) {
-    // the caller packed B for schedule 11 (alg_pack_b_p11): that schedule or nothing (B cannot be read any other way).  Checked
-    // here, before validate_only returns, so that a pair refuses a bad packed problem before it launches the other one.
+    // the caller packed B for schedule 11 (alg_pack_b_p11): that schedule or nothing (B cannot be read any other way).  Part of
+    // the check, so that a pair refuses a bad packed problem before it launches the other one.
     if (fp8) {
       set_error("alg_gemm_fp8: a packed B (ALG_GEMM_B_PACKED11) holds bf16 fragments for schedule 11; the e4m3 GEMM reads a row-major B");
       return ALG_EINVAL;
@@ -108,16 +115,41 @@ static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool valid
       set_error("alg_gemm_bf16: convolution addressing cannot be combined with a packed B (ALG_GEMM_B_PACKED11)");
       return ALG_EINVAL;
     }
-    if (a->K < 128 || 256 * a->lda * 2 + (int64_t)a->K * 2 >= (1ll << 32) || a->strideB != 0 ||
+    if (!asm_loop_takes(a->K, a->lda, 2) || a->strideB != 0 ||
         (a->flags & (ALG_GEMM_BIAS_PER_ROW | ALG_GEMM_PERMUTE_COLS)) || ((uintptr_t)a->B & 15)) {
       set_error("alg_gemm_bf16: a packed B (ALG_GEMM_B_PACKED11) needs K >= 128, 32-bit byte offsets inside a 256-row A panel, a B shared by "
                 "the batch (strideB = 0) and a plain column layout (no per-row bias / column permutation)");
       return ALG_EINVAL;
     }
   }
-  if (validate_only) return ALG_OK;
-  if ((int64_t)a->M * a->ldc >= (1ll << 31) || (a->R && (int64_t)a->M * a->ldr >= (1ll << 31))) {
-    // Every argument check above has run on the WHOLE call, so a slab can only fail at launch (no error after
+  return ALG_OK;
+}
+
+// The route of a checked call.  Pure: no HIP call, no error.
+static GemmPlan gemm_plan(const alg_gemm_args* a, bool fp8) {
+  GemmPlan p;
+  p.m_tiles = (a->M + BM - 1) / BM, p.n_tiles = (a->N + BN - 1) / BN;
+  p.nwg = (int64_t)p.m_tiles * p.n_tiles * a->batch;
+  // the epilogue addresses C / R with 32-bit element offsets inside one batch item
+  p.slabs = (int64_t)a->M * a->ldc >= (1ll << 31) || (a->R && (int64_t)a->M * a->ldr >= (1ll << 31));
+  const int esz = fp8 ? 1 : 2;
+  const bool asm_loop = (gemm_pipe() == 9 || gemm_pipe() == 10) && asm_loop_takes(a->K, a->lda, esz) && asm_loop_takes(a->K, a->ldb, esz);
+  if (fp8) p.route = asm_loop ? ROUTE_P9_FP8 : ROUTE_P6_FP8;   // (round 4: the asm loop on the block-scaled MFMA)
+  else if (a->conv_wp) p.route = ROUTE_P6_CONV;
+  else if (a->flags & ALG_GEMM_B_PACKED11) p.route = ROUTE_P11;   // (its own conditions are part of the check)
+  else if (asm_loop) p.route = gemm_pipe() == 10 ? ROUTE_P10 : ROUTE_P9;   // 4 waves, hand-written asm main loop
+  else p.route = ROUTE_P6;                                                  // 8-wave ping-pong over half-tiles
+  // the pair kernels are the plain schedule-9 / 10 kernels: row-major B, no residual / gate / activation, one launch
+  p.pairable = (p.route == ROUTE_P9 || p.route == ROUTE_P10) && !a->R && !a->gate && a->act == ALG_ACT_NONE && !p.slabs;
+  return p;
+}
+
+static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8);
+
+// Launches a checked and planned call.
+static int gemm_launch(const alg_gemm_args* a, const GemmPlan& p, void* stream, bool fp8) {
+  if (p.slabs) {
+    // The argument check has run on the WHOLE call, so a slab can only fail at launch (no error after
     // earlier slabs have already written C, which may alias R).  Per-row operands are A, C, R, a per-row bias, a_scale and
     // seg_split: each moves with the slab.  `gate` is per BATCH item (two segments), never per row: a caller that flattens
     // several samples into M shares one gate pair between them -- per-sample gates go through `batch` / strideGate.
@@ -140,70 +172,68 @@ static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8, bool valid
       if (a->bias && (a->flags & ALG_GEMM_BIAS_PER_ROW)) c.bias = (const char*)a->bias + m0 * 2;
       if (a->a_scale) c.a_scale = a->a_scale + m0;
       c.seg_split = a->seg_split > m0 ? (int32_t)(a->seg_split - m0) : 0;   // rows >= seg_split take gate[1]
-      const int rc = gemm_entry(&c, stream, fp8);
+      const int rc = gemm_entry(&c, stream, fp8);   // check, plan and launch per slab
       if (rc != ALG_OK) return rc;
     }
     return ALG_OK;
   }
-  const int m_tiles = (a->M + BM - 1) / BM, n_tiles = (a->N + BN - 1) / BN;
-  const int64_t nwg = (int64_t)m_tiles * n_tiles * a->batch;
-  if (nwg > 0x7fffffff) {
+  if (p.nwg > 0x7fffffff) {
     set_error("alg_gemm_bf16: grid too large");
     return ALG_ELIMIT;
   }
   hipStream_t s = (hipStream_t)stream;
-  if (fp8) {   // schedule 9 (round 4: the asm loop on the block-scaled MFMA) needs two k-tiles of 128 and 32-bit byte offsets
-    if (asm_pipe() && a->K >= 256 && 256 * a->lda + (int64_t)a->K < (1ll << 32) && 256 * a->ldb + (int64_t)a->K < (1ll << 32))
-      return launch_gemm_p9_fp8(a, m_tiles, n_tiles, nwg, s);
-    return launch_gemm_p6_fp8(a, m_tiles, n_tiles, nwg, s);
+  switch (p.route) {
+    case ROUTE_P6_CONV: return launch_gemm_p6_conv(a, p.m_tiles, p.n_tiles, p.nwg, s);
+    case ROUTE_P6_FP8: return launch_gemm_p6_fp8(a, p.m_tiles, p.n_tiles, p.nwg, s);
+    case ROUTE_P9: return launch_gemm_p9(a, p.m_tiles, p.n_tiles, p.nwg, s);
+    case ROUTE_P9_FP8: return launch_gemm_p9_fp8(a, p.m_tiles, p.n_tiles, p.nwg, s);
+    case ROUTE_P10: return launch_gemm_p10(a, p.m_tiles, p.n_tiles, p.nwg, s);
+    case ROUTE_P11: return launch_gemm_p11(a, p.m_tiles, p.n_tiles, p.nwg, s);
+    default: return launch_gemm_p6(a, p.m_tiles, p.n_tiles, p.nwg, s);
   }
-  if (a->conv_wp) return launch_gemm_p6_conv(a, m_tiles, n_tiles, nwg, s);
-  if (a->flags & ALG_GEMM_B_PACKED11) return launch_gemm_p11(a, m_tiles, n_tiles, nwg, s);   // (arguments checked above)
-  switch (gemm_pipe()) {
-    case 9:   // 4 waves, hand-written asm main loop; needs two k-tiles and 32-bit byte offsets inside a 256-row panel
-    case 10:
-      if (a->K >= 128 && 256 * a->lda * 2 + (int64_t)a->K * 2 < (1ll << 32) && 256 * a->ldb * 2 + (int64_t)a->K * 2 < (1ll << 32))
-        return gemm_pipe() == 10 ? launch_gemm_p10(a, m_tiles, n_tiles, nwg, s) : launch_gemm_p9(a, m_tiles, n_tiles, nwg, s);
-      return launch_gemm_p6(a, m_tiles, n_tiles, nwg, s);
-    default: return launch_gemm_p6(a, m_tiles, n_tiles, nwg, s);  // 8-wave ping-pong over half-tiles
-  }
+}
+
+static int gemm_entry(const alg_gemm_args* a, void* stream, bool fp8) {
+  const int rc = gemm_check(a, fp8);
+  return rc != ALG_OK ? rc : gemm_launch(a, gemm_plan(a, fp8), stream, fp8);
 }
 
 extern "C" int alg_gemm_bf16(const alg_gemm_args* a, void* stream) { return gemm_entry(a, stream, false); }
 
-// Two independent plain GEMMs in one persistent launch when schedule 9 can take both (no residual / activation / convolution,
-// row-major B, K >= 128, 32-bit offsets, no slab split); otherwise -- and always with ALG_GEMM_PIPE=6 -- simply one launch
-// after the other.  Either way every output element is computed exactly as alg_gemm_bf16 would compute it (bit-identical).
-// The pair kernels read B as a row-major [N][ldb] panel: a packed B (ALG_GEMM_B_PACKED11) sends its problem to schedule 11
-// through gemm_entry.
-static bool pair_eligible(const alg_gemm_args* a) {
-  return a && a->A && a->B && a->C && !(a->flags & ALG_GEMM_B_PACKED11) && !a->R && !a->gate && a->act == ALG_ACT_NONE &&
-         !a->conv_wp && a->M > 0 && a->N > 0 && a->batch > 0 && a->K >= 128 && a->K % 64 == 0 && 256 * a->lda * 2 + (int64_t)a->K * 2 < (1ll << 32) &&
-         256 * a->ldb * 2 + (int64_t)a->K * 2 < (1ll << 32) && (int64_t)a->M * a->ldc < (1ll << 31) &&
-         !(a->lda % 8 || a->ldb % 8 || a->strideA % 8 || a->strideB % 8 || ((uintptr_t)a->A & 15) || ((uintptr_t)a->B & 15)) &&
-         ((a->N & 3) != 0 || !((a->ldc & 3) || (a->strideC & 3) || ((uintptr_t)a->C & 7) ||
-                               (a->bias && !(a->flags & ALG_GEMM_BIAS_PER_ROW) && ((uintptr_t)a->bias & 7))));
+// Two independent plain GEMMs in one persistent launch when both plans are pairable (the plain bf16 asm route: no residual /
+// gate / activation / convolution, row-major B, no slab split); otherwise -- and always with ALG_GEMM_PIPE=6 -- simply one
+// launch after the other.  Either way every output element is computed exactly as alg_gemm_bf16 would compute it (bit-identical).
+// The pair kernels read B as a row-major [N][ldb] panel: a packed B (ALG_GEMM_B_PACKED11) sends its problem to schedule 11.
+// Every argument check of alg_gemm_bf16 runs on BOTH calls before anything is launched.
+struct PairPlan {
+  GemmPlan a, b;
+  bool one_launch;
+};
+static int pair_plan(const alg_gemm_args* a, const alg_gemm_args* b, PairPlan* pp) {
+  int rc = gemm_check(a, false);
+  if (rc == ALG_OK) rc = gemm_check(b, false);
+  if (rc != ALG_OK) return rc;
+  pp->a = gemm_plan(a, false), pp->b = gemm_plan(b, false);
+  pp->one_launch = pp->a.pairable && pp->b.pairable && pp->a.nwg + pp->b.nwg <= 0x7fffffff;
+  return ALG_OK;
+}
+static int pair_launch(const alg_gemm_args* a, const alg_gemm_args* b, const PairPlan& pp, const alg_qk_norm_rope_args* e, void* stream) {
+  return (pp.a.route == ROUTE_P10 ? launch_gemm_p10_pair : launch_gemm_p9_pair)(a, pp.a.m_tiles, pp.a.n_tiles, b, pp.b.m_tiles,
+                                                                                pp.b.n_tiles, e, (hipStream_t)stream);
 }
 
 extern "C" int alg_gemm_bf16_pair(const alg_gemm_args* a, const alg_gemm_args* b, void* stream) {
-  // every argument check of alg_gemm_bf16 runs on BOTH calls before anything is launched
-  int rc = gemm_entry(a, stream, false, true);
-  if (rc == ALG_OK) rc = gemm_entry(b, stream, false, true);
+  PairPlan pp;
+  int rc = pair_plan(a, b, &pp);
   if (rc != ALG_OK) return rc;
-  if (asm_pipe() && pair_eligible(a) && pair_eligible(b)) {
-    const int64_t ta = (int64_t)((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN) * a->batch;
-    const int64_t tb = (int64_t)((b->M + BM - 1) / BM) * ((b->N + BN - 1) / BN) * b->batch;
-    if (ta + tb <= 0x7fffffff)
-      return (gemm_pipe() == 10 ? launch_gemm_p10_pair : launch_gemm_p9_pair)(a, (a->M + BM - 1) / BM, (a->N + BN - 1) / BN, b, (b->M + BM - 1) / BM, (b->N + BN - 1) / BN,
-                                 (hipStream_t)stream);
-  }
-  rc = gemm_entry(a, stream, false);
-  return rc != ALG_OK ? rc : gemm_entry(b, stream, false);
+  if (pp.one_launch) return pair_launch(a, b, pp, nullptr, stream);
+  rc = gemm_launch(a, pp.a, stream, false);
+  return rc != ALG_OK ? rc : gemm_launch(b, pp.b, stream, false);
 }
 
 extern "C" int alg_gemm_bf16_pair_qk(const alg_gemm_args* a, const alg_gemm_args* b, const alg_qk_norm_rope_args* e, void* stream) {
-  int rc = gemm_entry(a, stream, false, true);
-  if (rc == ALG_OK) rc = gemm_entry(b, stream, false, true);
+  PairPlan pp;
+  int rc = pair_plan(a, b, &pp);
   if (rc != ALG_OK) return rc;
   if (!e || !e->wq || !e->bq || !e->wk || !e->bk || e->heads <= 0 || e->text_len < 0 || e->text_len > a->M ||
       (e->cos_tab == nullptr) != (e->sin_tab == nullptr)) {
@@ -223,16 +253,8 @@ extern "C" int alg_gemm_bf16_pair_qk(const alg_gemm_args* a, const alg_gemm_args
   }
   // the store loop owns whole head vectors and whole Q / K tiles: heads * 64 a multiple of the 256-column tile, staged epilogue
   // (N % 8 == 0 and 16-byte rows hold by the layout; a per-row bias would take the element-exact path).  A packed B in either
-  // problem takes the fallback (pair_eligible): its problem runs on schedule 11, the norm + rope as a launch of its own.
-  const bool fused = asm_pipe() && pair_eligible(a) && pair_eligible(b) && e->heads % 4 == 0 &&
-                     !(a->bias && (a->flags & ALG_GEMM_BIAS_PER_ROW));
-  if (fused) {
-    const int64_t ta = (int64_t)((a->M + BM - 1) / BM) * ((a->N + BN - 1) / BN) * a->batch;
-    const int64_t tb = (int64_t)((b->M + BM - 1) / BM) * ((b->N + BN - 1) / BN) * b->batch;
-    if (ta + tb <= 0x7fffffff)
-      return (gemm_pipe() == 10 ? launch_gemm_p10_pair_qk : launch_gemm_p9_pair_qk)(a, (a->M + BM - 1) / BM, (a->N + BN - 1) / BN, b, (b->M + BM - 1) / BM, (b->N + BN - 1) / BN, e,
-                                    (hipStream_t)stream);
-  }
+  // problem takes the fallback (not pairable): its problem runs on schedule 11, the norm + rope as a launch of its own.
+  if (pp.one_launch && e->heads % 4 == 0 && !(a->bias && (a->flags & ALG_GEMM_BIAS_PER_ROW))) return pair_launch(a, b, pp, e, stream);
   rc = alg_gemm_bf16_pair(a, b, stream);
   if (rc != ALG_OK) return rc;
   return alg_qk_norm_rope_scaled(a->C, e->wq, e->bq, e->wk, e->bk, e->cos_tab, e->sin_tab, a->batch, a->M, e->heads, e->text_len,
