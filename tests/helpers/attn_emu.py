@@ -241,7 +241,6 @@ def run_pipe8_statement(pb, lazy_reads, lazy_dma, t0=1, mutate=None):
     assert pb.d == 64 and pb.prescaled and not pb.ragged
     GP.configure(8)
     lines = GP.emit()
-    GP.configure(4)
     if mutate is not None:
         lines = mutate(lines)
     T, TILE, NW = pb.T, 8192, 8

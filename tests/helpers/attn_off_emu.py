@@ -62,7 +62,7 @@ def run_pipe8_off_statement(pb, m_run, lazy_reads, lazy_dma, t0=1, mutate=None, 
     GP.configure(8, offset=not zero_form)
     lines = GP.emit()
     regs = dict(SA=GP.SA, SB=GP.SB, PA=GP.PA, PB=GP.PB)
-    GP.configure(4)
+    GP.configure(8)
     if mutate is not None:
         lines = mutate(lines)
     m_run = np.asarray(m_run, dtype=np.float32)

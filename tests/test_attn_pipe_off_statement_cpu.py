@@ -50,7 +50,7 @@ def test_offset_text_differs_from_the_zero_offset_text_only_where_it_should():
     zero = GP.emit()
     GP.configure(8, offset=True)
     off = GP.emit()
-    GP.configure(4)
+    GP.configure(8)
     movs = [ln for ln in off if ln.startswith("v_mov_b32")]
     assert movs == ["v_mov_b32 v%d, %%[negm]" % (10 + i) for i in range(16)]
     rest = [ln for ln in off if not ln.startswith("v_mov_b32")]

@@ -299,7 +299,8 @@ def test_flash_attention_d64_m16_kernel(device, monkeypatch, Bn, S2, H2):
     tensors: ragged tails (the 16 x 16 layout's own key mask), tile counts that leave 0-3 tiles behind the statement's groups of
     four, rows whose first-tile max is beyond +-64 (non-zero offset: those waves never enter the statement) next to rows in the
     zero-offset form, late dominant keys (the statement refuses the tile, the exact path runs), query blocks ending mid-wave; 8 x 1
-    heads = enough units for the split-KV tail plan to engage next to the m16 main launch.  Run-to-run identical."""
+    heads = one head on every XCD (no split-KV tail at this size: 5 units per XCD, 19 KV tiles -- test_split_kv_tail_at_small_sizes
+    has the tail next to the m16 main launch).  Run-to-run identical."""
     g = torch.Generator().manual_seed(S2 + H2)
     c = 0.125 * 1.4426950408889634
     q, k, v = rnd((Bn, S2, H2, 64), g), rnd((Bn, S2, H2, 64), g), rnd((Bn, S2, H2, 64), g)
@@ -574,13 +575,14 @@ def test_attention_wide_score_ranges_against_fp64(device, std, monkeypatch):
 @pytest.mark.parametrize("Bn,S2,H2", [(1, 512, 2), (2, 1000, 3), (1, 513, 1), (1, 640, 1), (1, 832, 1), (1, 2050, 2), (1, 4097, 1),
                                        (8, 1200, 1)])
 def test_pipelined_attention_kernel(device, monkeypatch, Bn, S2, H2):
-    """flash_attn_d64_pipe_kernel (ALG_ATTN_PP=4, the default main launch of the pre-scaled call, and its 4-wave form 3): the asm steady-state loop
+    """flash_attn_d64_pipe_kernel (ALG_ATTN_PP=4, the default main launch of the pre-scaled call): the asm steady-state loop
     (entered at tile 1 by waves whose running offsets are all zero, whole groups of four tiles) inside its C++ frame, against
     fp32 SDPA and against the straight loop (ALG_ATTN_PP=0) on the same tensors.  Rows whose first-tile max is beyond +-64 keep a
     non-zero offset (those waves never enter the statement while their neighbours in the workgroup do: mixed mode under one
     barrier / DMA protocol); a late dominant key makes a row sum leave [0, 2^80) INSIDE the statement (it bails out, the tile is
-    redone on the exact path); ragged tails; S = 512 / 513 stay below the statement's minimum of eight tiles; 8 x 1 heads let
-    the split-KV tail plan engage next to the pipelined main launch.  Run-to-run identical."""
+    redone on the exact path); ragged tails; S = 512 / 513 stay below the statement's minimum of eight tiles; 8 x 1 heads put
+    one head on every XCD (no split-KV tail at this size: 5 units per XCD, 19 KV tiles -- test_split_kv_tail_at_small_sizes has
+    the tail).  Run-to-run identical."""
     g = torch.Generator().manual_seed(S2 + H2)
     c = 0.125 * 1.4426950408889634
     q, k, v = rnd((Bn, S2, H2, 64), g), rnd((Bn, S2, H2, 64), g), rnd((Bn, S2, H2, 64), g)
@@ -619,3 +621,67 @@ def test_pipelined_attention_kernel(device, monkeypatch, Bn, S2, H2):
             _lib.flash_attn_d64(qkb, qkb, vt, o2, Bn, H2, S2, S2 * 2 * D, 2 * D, D * S_pad, S_pad, S2 * D, D, 0.125, k_off=D,
                                 q_prescaled=True)
             assert torch.equal(o2, outs[pp]), pp
+
+
+@pytest.mark.parametrize("Bn,S2,H2,units,split", [(1, 4090, 40, 16, 8), (1, 16600, 8, 1, 16)])
+def test_split_kv_tail_at_small_sizes(device, monkeypatch, Bn, S2, H2, units, split):
+    """The split-KV tail (attention.hip: plan_tail -- the units of an XCD's last, at most quarter-full round of 64 are cut along KV
+    into chunk workgroups, then merged) at the two smallest kinds of shape that have one: 40 heads x 4,090 tokens = 80 units per
+    XCD, the last 16 (heads 32-39 whole) in 8 chunks of 8 tiles, exactly the minimum of 64 KV tiles; 8 heads x 16,600 tokens = 65
+    units per XCD, the last one (rows 16,384.. of every head) in 16 chunks of 17 tiles, the last chunk five tiles.  Both
+    ragged.  Every form of the call that can have a tail -- the default softmax un-pre-scaled, the pre-scaled call under
+    ALG_ATTN_PP 0, 4, 7, 8 -- with the tail and as a single launch (ALG_ATTN_SPLIT_TAIL=0), on test_pipelined_attention_kernel's
+    operands (a fifth of the rows at a non-zero offset, one late dominant key): against fp32 SDPA; rows outside the tail units
+    bit-equal between the two plans where the main launch is the straight loop; the tail run-to-run identical."""
+    lib = _lib.load_library()
+    g = torch.Generator().manual_seed(S2 + H2)
+    c = 0.125 * 1.4426950408889634
+    q, k, v = rnd((Bn, S2, H2, 64), g), rnd((Bn, S2, H2, 64), g), rnd((Bn, S2, H2, 64), g)
+    q[:, : S2 // 5] *= 9.0                       # scores ~ +-70 in log2 units: non-zero offsets for a fifth of the rows
+    k[:, (2 * S2) // 3] *= 6.0                   # one late key that dominates
+    D = H2 * 64
+    S_pad = (S2 + 127) // 128 * 128
+    qs = (q.float() * c).to(BF)                  # the un-pre-scaled call takes the same Q with scale = ln 2: scale * log2(e) = 1
+    qkb = torch.cat([qs.reshape(Bn, S2, D), k.reshape(Bn, S2, D)], dim=-1).contiguous().to(device)
+    vt = torch.zeros(Bn, D, S_pad, dtype=BF)
+    vt[:, :, torch.tensor([swap23(n) for n in range(S2)])] = v.reshape(Bn, S2, D).transpose(1, 2)
+    vt = vt.to(device)
+    # fp32 SDPA on the device, one (batch, head) at a time (a score matrix is up to 1.1 GB); scores in log2 units
+    ref = torch.empty(Bn, S2, H2, 64, device=device)
+    qd, kd, vd = qs.to(device).float(), k.to(device).float(), v.to(device).float()
+    for b in range(Bn):
+        for h in range(H2):
+            sc = (qd[b, :, h] @ kd[b, :, h].T) * math.log(2.0)
+            ref[b, :, h] = torch.softmax(sc, dim=-1) @ vd[b, :, h]
+    del sc
+    # rows of the tail units: unit idx of XCD x is (head slot idx / q_blocks) * 8 + x, query block idx % q_blocks
+    q_blocks, per_xcd = (S2 + 255) // 256, Bn * H2 // 8 * ((S2 + 255) // 256)
+    in_tail = torch.zeros(Bn * H2, q_blocks * 256, dtype=torch.bool)
+    for x in range(8):
+        for idx in range(per_xcd - units, per_xcd):
+            in_tail[idx // q_blocks * 8 + x, idx % q_blocks * 256: idx % q_blocks * 256 + 256] = True
+    main_rows = ~in_tail[:, :S2].reshape(Bn, H2, S2).transpose(1, 2).to(device)       # [Bn, S2, H2]
+    assert 0 < main_rows.sum().item() < Bn * S2 * H2
+
+    def run(prescaled):
+        o = torch.full((Bn, S2, D), 3.0, dtype=BF, device=device)
+        _lib.flash_attn_d64(qkb, qkb, vt, o, Bn, H2, S2, S2 * 2 * D, 2 * D, D * S_pad, S_pad, S2 * D, D,
+                            0.125 if prescaled else math.log(2.0), k_off=D, q_prescaled=prescaled)
+        return o.reshape(Bn, S2, H2, 64)
+
+    monkeypatch.setenv("ALG_ATTN_VARIANT", "33")
+    for prescaled, pp in ((False, "4"), (True, "0"), (True, "4"), (True, "7"), (True, "8")):
+        monkeypatch.setenv("ALG_ATTN_PP", pp)
+        outs = {}
+        for tail in ("1", "0"):
+            monkeypatch.setenv("ALG_ATTN_SPLIT_TAIL", tail)
+            wsb = lib.alg_flash_attn_d64_workspace_bytes(Bn, H2, S2, _lib.ATTN_Q_PRESCALED if prescaled else 0)
+            assert wsb == (8 * units * split * 256 * 66 * 4 if tail == "1" else 0), (prescaled, pp, tail, wsb)
+            outs[tail] = run(prescaled)
+            err = (outs[tail].float() - ref).abs()
+            assert torch.isfinite(outs[tail].float()).all(), (prescaled, pp, tail)
+            assert err.max().item() <= 3e-2 and err.mean().item() <= 2e-3, (prescaled, pp, tail, err.max().item(), err.mean().item())
+        if not prescaled or pp == "0":       # the straight loop as the main launch: the same workgroups do the same work in both plans
+            assert torch.equal(outs["1"][main_rows], outs["0"][main_rows]), (prescaled, pp)
+        monkeypatch.setenv("ALG_ATTN_SPLIT_TAIL", "1")
+        assert torch.equal(run(prescaled), outs["1"]), (prescaled, pp)
