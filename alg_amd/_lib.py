@@ -33,10 +33,11 @@ EXPORTS = (
     "alg_lowpass_tables_bytes", "alg_lowpass_tables_build", "alg_down_up_workspace_bytes", "alg_gaussian_blur_workspace_bytes",
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap", "alg_attn_path_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
-    "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched",
+    "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
-            "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes")
+            "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
+            "alg_step_cache_workspace_bytes")
 
 
 class AlgHipError(RuntimeError):
@@ -116,6 +117,8 @@ def load_library():
     lib.alg_cfg_combine.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_void_p]
     lib.alg_lincomb.argtypes = [POINTER(c_void_p), POINTER(c_float), POINTER(c_int), c_int, c_void_p, c_int, c_int64,
                                 c_void_p]
+    lib.alg_step_cache_workspace_bytes.argtypes = [c_int, c_int]
+    lib.alg_step_cache_probe.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3
     lib.alg_concat_cast.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_int] + [c_int64] * 7 + [
         c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d128.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p]
@@ -457,6 +460,30 @@ def lincomb(terms, out_dtype, out=None):
     _check(lib.alg_lincomb(arr, cf, dts, n, _ptr(out), ALG_F32 if out_dtype == torch.float32 else ALG_BF16,
                            out.numel(), _stream()), "alg_lincomb")
     return out
+
+
+def step_cache_workspace_bytes(rows, D):
+    """Bytes of the probe's partial-sum workspace for one [rows, D] sample (a host query)."""
+    n = load_library().alg_step_cache_workspace_bytes(int(rows), int(D))
+    _check(0 if n >= 0 else int(n), "alg_step_cache_workspace_bytes")
+    return int(n)
+
+
+def step_cache_probe(keep, x1, r, rows, D, tok0, tok_rows, workspace, sums):
+    """The step cache's probe on one sample (include/alg_hip.h): r <- bf16(x1 - keep), keep <- x1, and sums[0:2] (device
+    float64) = (sum |r - r_prev|, sum |r_prev|) over the token rows [tok0, tok0 + tok_rows).  keep, x1, r: contiguous bf16
+    tensors (views) of rows * D elements; workspace: at least step_cache_workspace_bytes(rows, D) bytes."""
+    lib = load_library()
+    for t, name in ((keep, "keep"), (x1, "x1"), (r, "r")):
+        _dev(t, name)
+        if t.dtype != torch.bfloat16 or not t.is_contiguous() or t.numel() != rows * D:
+            raise AlgHipError("step_cache_probe: %s must be a contiguous bfloat16 tensor of rows * D elements" % name)
+    if sums.dtype != torch.float64 or sums.numel() < 2 or not sums.is_cuda or not workspace.is_cuda:
+        raise AlgHipError("step_cache_probe: sums must be a device float64 tensor of 2 elements, workspace a device tensor")
+    if workspace.numel() * workspace.element_size() < step_cache_workspace_bytes(rows, D):
+        raise AlgHipError("step_cache_probe: the workspace is smaller than step_cache_workspace_bytes(rows, D)")
+    _check(lib.alg_step_cache_probe(_ptr(keep), _ptr(x1), _ptr(r), rows, D, tok0, tok_rows, _ptr(workspace), _ptr(sums),
+                                    _stream()), "alg_step_cache_probe")
 
 
 def concat_cast(src0, src1, O, A0, A1, R, s0_ostride, s1_ostride, a1_off, out_dtype):

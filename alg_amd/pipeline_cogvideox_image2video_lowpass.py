@@ -28,7 +28,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import _lib, lp_utils
+from . import _lib, lp_utils, step_cache
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler
 from .transformer_cogvideox import CogVideoXTransformer3DModel
 
@@ -129,12 +129,14 @@ class CogVideoXImageToVideoPipeline:
     # -- construction ---------------------------------------------------------------------------------
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
-                        scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False, **_):
+                        scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False,
+                        step_cache=0.0, **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
         `image_latents` and `output_type="latent"`.  `fp8=True` loads the transformer with e4m3 block linears
-        (CogVideoXTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in."""
+        (CogVideoXTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.  `step_cache` > 0
+        switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default)."""
         import os
 
         from .autoencoder_kl_cogvideox import AutoencoderKLCogVideoX
@@ -145,6 +147,8 @@ class CogVideoXImageToVideoPipeline:
         if transformer is None:
             transformer = CogVideoXTransformer3DModel.from_pretrained(model_path, torch_dtype=torch_dtype,
                                                                       device=device, fp8=fp8)
+        if step_cache:
+            transformer.step_cache = float(step_cache)
         if vae is None and has("vae"):
             vae = AutoencoderKLCogVideoX.from_pretrained(model_path, device=device)
         if text_encoder is None and has("text_encoder"):
@@ -543,6 +547,14 @@ class CogVideoXImageToVideoPipeline:
         old_pred_original_sample = None  # cog:998
 
         B = latents.shape[0]
+        # the transformer's opt-in step cache (alg_amd/step_cache.py): a new video starts from an empty cache, every forward names
+        # the roles of its passes, the last step is always computed.  Transformers without the switch are called as ever.
+        use_cache = step_cache.active(self.transformer)
+        if use_cache:
+            if cfg_split is not None:
+                raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
+                                       "passes and leave the single-GPU result; run one of the two")
+            self.transformer.reset_step_cache()
         # every timestep of the schedule on the device ONCE: a step takes a view of it (no host tensor + H2D copy per step)
         ts_dev = torch.as_tensor([int(t_) for t_ in timesteps], dtype=torch.float32).to(device)
         for i, t in enumerate(timesteps):
@@ -601,7 +613,8 @@ class CogVideoXImageToVideoPipeline:
                                                            ts[:len(rows)], image_rotary_emb, ofs=ofs_emb)
                 noise_pred = cfg_split.merge(local, n_pass, B)
             else:
-                noise_pred = self.transformer.forward_assembled(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb)
+                cache_kw = dict(cache_keys=step_cache.pass_keys(n_pass, B), cache_force=i == len(timesteps) - 1) if use_cache else {}
+                noise_pred = self.transformer.forward_assembled(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb, **cache_kw)
             gs = guidance_scale
             if do_cfg and not use_low_pass_guidance and use_dynamic_cfg:  # cog:1105-1108
                 gs = 1 + guidance_scale * (

@@ -30,7 +30,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, lp_utils
+from . import _lib, lp_utils, step_cache
 from .schedulers import UniPCMultistepScheduler
 
 
@@ -104,9 +104,10 @@ class WanImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, image_encoder=None, image_processor=None, device="cuda",
-                        fp8=False, fp8_attention=False, **_):
+                        fp8=False, fp8_attention=False, step_cache=0.0, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
-        (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan)."""
+        (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan).
+        `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default)."""
         import os
 
         from .image_encoder_clip import CLIPImageProcessor, CLIPVisionModel
@@ -118,6 +119,8 @@ class WanImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention)
+        if step_cache:
+            transformer.step_cache = float(step_cache)
         if text_encoder is None and has("text_encoder"):
             text_encoder = UMT5EncoderModel.from_pretrained(model_path, device=device)
         if tokenizer is None:
@@ -459,6 +462,14 @@ class WanImageToVideoPipeline:
         latents, condition = self.prepare_latents(image_condition, batch_size * num_videos_per_prompt, z_dim, height,
                                                   width, num_frames, torch.float32, device, generator, latents)
 
+        # the transformer's opt-in step cache (alg_amd/step_cache.py): a new video starts from an empty cache, every forward names
+        # the roles of its passes, the last step is always computed.  Transformers without the switch are called as ever.
+        use_cache = step_cache.active(self.transformer)
+        if use_cache:
+            if cfg_split is not None:
+                raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
+                                       "passes and leave the single-GPU result; run one of the two")
+            self.transformer.reset_step_cache()
         for i, t in enumerate(timesteps):
             if self._interrupt or i < self._first_step:
                 continue
@@ -510,9 +521,11 @@ class WanImageToVideoPipeline:
                                          attention_kwargs=attention_kwargs, return_dict=False)[0]
                 noise_pred = cfg_split.merge(local.contiguous(), len(groups), B_)
             else:
+                cache_kw = dict(cache_keys=step_cache.pass_keys(len(groups), latents.shape[0]),
+                                cache_force=i == len(timesteps) - 1) if use_cache else {}
                 noise_pred = self.transformer(
                     hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
-                    encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False)[0]
+                    encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False, **cache_kw)[0]
             # wan:919-924 keys the 3-chunk combine on shape[0] == 3, so the reference's 3-pass step only works for one
             # video per call (a [3B, ...] prediction would be chunked in two and fail in the scheduler)
             n_pass = 3 if noise_pred.shape[0] == 3 else 2

@@ -36,6 +36,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .step_cache import StepCacheHost
 
 
 @dataclass
@@ -79,7 +80,7 @@ def _bf(t, device):
     return t.to(device=device, dtype=torch.bfloat16).contiguous()
 
 
-class CogVideoXTransformer3DModel:
+class CogVideoXTransformer3DModel(StepCacheHost):
     dtype = torch.bfloat16
 
     # the block linears that fp8 mode quantises, per output channel: Q|K, V, attention out, feed-forward in / out
@@ -126,6 +127,11 @@ class CogVideoXTransformer3DModel:
         # The Q|K projection stays on the pair launch with V^T (whose B operand is the activation): on schedule 11 with V^T as its own
         # launch the step was 0.4 % slower (profiles/r6_bench_steps10_ab_packed_qk.json).
         self.packed_weights = True
+        # > 0 (opt-in, an extension: alg_amd/step_cache.py): a forward that is handed `cache_keys` probes block 0's residual and,
+        # while sum |r - r_prev| < step_cache * sum |r_prev| over the video tokens of every sample, replaces blocks 1 .. L-1 by the
+        # residual they produced on the last computed forward.  0.0: every forward is the plain one, launch for launch.
+        self.step_cache = 0.0
+        self.step_cache_max_consecutive = 0   # at most this many skipped forwards in a row (0: no cap)
         self._sincos = {}
         dev = self.device
         w = weights
@@ -403,12 +409,16 @@ class CogVideoXTransformer3DModel:
         return hit
 
     # ------------------------------------------------------------------------------------------------
-    def forward_assembled(self, latents, conds, encoder_hidden_states, timestep, image_rotary_emb=None, ofs=None):
+    def forward_assembled(self, latents, conds, encoder_hidden_states, timestep, image_rotary_emb=None, ofs=None,
+                          cache_keys=None, cache_force=False):
         """The loop's form of the forward, with the CFG batch assembly (cog:1060-1070) folded into the patch
         gather: sample n sees channels [latents | conds[n]].
 
         latents [1 or N, F, C, H, W] bf16; conds: list of N tensors [1, F, C, H, W] (or [F, C, H, W]) bf16;
         encoder_hidden_states [N, T, text_dim]; timestep [N].  Returns noise prediction [N, F, C_out, H, W] bf16.
+
+        cache_keys (one hashable per sample, naming the role of its pass) arms the step cache when `step_cache` > 0;
+        cache_force computes this forward whatever the probe says (the last step of a schedule).
         """
         cfg = self.config
         N = len(conds)
@@ -490,7 +500,10 @@ class CogVideoXTransformer3DModel:
         F4 = cfg.ff_inner_mult * D
         packed = self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         wo_k, wf1_k, wf2_k = ("pwo", "pwf1", "pwf2") if packed else ("wo", "wf1", "wf2")
+        sc = self._step_cache_begin(x, cache_keys, cache_force, T, P)   # None: off, nothing below differs from the plain forward
         for li, L in enumerate(self.layers):
+            if li == 1 and sc is not None and TM("step_cache", sc.after_block0, x):
+                break                 # hit: x = x1 + the cached tail, straight to the head
             m1 = li * 12 * D          # norm1: shift @+0, scale @+2D, gate @+4D (each [2][D])
             m2 = m1 + 6 * D           # norm2
             if fp8:
@@ -524,6 +537,11 @@ class CogVideoXTransformer3DModel:
             TM("gemm_ff2", G, h, L[wf2_k], x, S, D, F4, F4, F4, D, bias=L["bf2"], R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D,
               strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * F4, strideC=S * D, strideR=S * D)
 
+        if sc is not None:
+            if len(self.layers) == 1:  # no tail to skip: the probe and the rule run all the same (x + 0 on a hit)
+                TM("step_cache", sc.after_block0, x)
+            TM("step_cache", sc.end, x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
+
         # 4. norm_final over the joint sequence, AdaLayerNorm on the video tokens, proj_out, unpatchify
         _lib.layernorm_modulate(x, y, self.norm_final_w, self.norm_final_b, None, None, 0, N, S, D, T, cfg.norm_eps)
         mo = cfg.num_layers * 12 * D   # norm_out: shift pair @+0, scale pair @+2D
@@ -537,7 +555,7 @@ class CogVideoXTransformer3DModel:
         return out
 
     def __call__(self, hidden_states, encoder_hidden_states, timestep, timestep_cond=None, ofs=None,
-                 image_rotary_emb=None, attention_kwargs=None, return_dict=True):
+                 image_rotary_emb=None, attention_kwargs=None, return_dict=True, cache_keys=None, cache_force=False):
         """diffusers-style entry: hidden_states [N, F, 2C, H, W] (latents and condition already concatenated on
         the channel axis, cog:1068-1070)."""
         if timestep_cond is not None:
@@ -545,7 +563,8 @@ class CogVideoXTransformer3DModel:
         C = hidden_states.shape[2] // 2
         lat = hidden_states[:, :, :C].contiguous()
         conds = [hidden_states[n:n + 1, :, C:].contiguous() for n in range(hidden_states.shape[0])]
-        out = self.forward_assembled(lat, conds, encoder_hidden_states, timestep, image_rotary_emb, ofs=ofs)
+        out = self.forward_assembled(lat, conds, encoder_hidden_states, timestep, image_rotary_emb, ofs=ofs,
+                                     cache_keys=cache_keys, cache_force=cache_force)
         if not return_dict:
             return (out,)
         return TransformerOutput(sample=out)

@@ -31,6 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
 
@@ -151,7 +152,7 @@ def k_scale_bound(norm_weight, norm_dim, heads, rope):
     return (w * (1.02 * math.sqrt(norm_dim * (2.0 if rope else 1.0)) / 448.0)).contiguous()
 
 
-class WanTransformer3DModel:
+class WanTransformer3DModel(StepCacheHost):
     dtype = BF
 
     def __init__(self, config: WanTransformerConfig, weights: dict, device="cuda", fp8=False, fp8_attention=False):
@@ -172,6 +173,11 @@ class WanTransformer3DModel:
         # packed in MFMA-fragment order (alg_pack_b_p11) and run GEMM schedule 11 (bit-identical to schedule 10); False, or
         # ALG_GEMM_PIPE set to another schedule than 10: the row-major weights
         self.packed_weights = True
+        # > 0 (opt-in, an extension: alg_amd/step_cache.py): a forward that is handed `cache_keys` probes block 0's residual and,
+        # while it moved by less than this fraction since the last forward, replaces blocks 1 .. L-1 by the residual they produced
+        # on the last computed forward.  0.0: every forward is the plain one, launch for launch.
+        self.step_cache = 0.0
+        self.step_cache_max_consecutive = 0   # at most this many skipped forwards in a row (0: no cap)
         if config.qk_norm != "rms_norm_across_heads" or config.attention_head_dim != 128:
             raise NotImplementedError("the Wan DiT path is built for rms_norm_across_heads and head_dim 128")
         if tuple(config.patch_size)[0] != 1:
@@ -365,7 +371,9 @@ class WanTransformer3DModel:
 
     # ---- forward -----------------------------------------------------------------------------------------------------
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
-                 attention_kwargs=None, return_dict=True):
+                 attention_kwargs=None, return_dict=True, cache_keys=None, cache_force=False):
+        """cache_keys (one hashable per sample, naming the role of its pass) arms the step cache when `step_cache` > 0;
+        cache_force computes this forward whatever the probe says (the last step of a schedule)."""
         cfg, w, G, T = self.config, self.w, _lib.gemm, self._timed
         if hidden_states.device.type != "cuda":
             raise _lib.AlgHipError("WanTransformer3DModel needs device tensors; there is no CPU fallback")
@@ -444,7 +452,10 @@ class WanTransformer3DModel:
 
         use_packed = not self.fp8 and self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         packed = None
+        sc = self._step_cache_begin(ws.x, cache_keys, cache_force, 0, S)   # None: off, nothing below differs from the plain forward
         for li, L in enumerate(self.blocks):
+            if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
+                break                 # hit: x = x1 + the cached tail, straight to the head
             if use_packed:   # lin() looks the row-major weight up by identity
                 packed = {id(getattr(L, name)): pw for name, pw in L.packed.items()}
             m0 = li * N * 6 * D  # element offset of this block's [N, 6, D] modulation: shift, scale, gate, c_shift, c_scale, c_gate
@@ -512,6 +523,11 @@ class WanTransformer3DModel:
             lin("gemm_ff2", ws.h, L.f2_w, ws.x, S, D, Ff, Ff, D, bias=L.f2_b, R=ws.x, ldr=D, gate=ws.mod,
                 gate_off=m0 + 5 * D, strideGate=mod_bs, batch=N, strideA=S * Ff, strideC=S * D, strideR=S * D,
                 seg_split=1 << 30, flags=_lib.GEMM_GATE_F32)
+
+        if sc is not None:
+            if len(self.blocks) == 1:  # no tail to skip: the probe and the rule run all the same (x + 0 on a hit)
+                T("step_cache", sc.after_block0, ws.x)
+            T("step_cache", sc.end, ws.x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
 
         # ---- output head ----
         _lib.layernorm_mod_f32(ws.x, ws.y, None, None, ws.mod_out, ws.mod_out, 2 * D, N, S, D, cfg.eps, scale_off=D,

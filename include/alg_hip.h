@@ -111,6 +111,19 @@ int alg_cfg_combine(const void* pred, void* out, int dtype, int n_pass, int64_t 
 int alg_lincomb(const void* const* xs, const float* coefs, const int* dtypes, int n_terms, void* out, int out_dtype,
                 int64_t numel, void* stream);
 
+/* Step cache ("first-block cache", an extension: the reference has none) -- the probe behind block 0 of a DiT, one call per
+ * sample.  keep = the caller's copy of the hidden state in front of block 0 (x0), x1 = the hidden state behind it, r = the
+ * residual the last forward left (r_prev); all [rows][D] bf16, three distinct buffers, 16-byte aligned, D % 8 == 0.
+ *   r_new = bf16(float(x1) - float(x0))                                               every row
+ *   a = sum |float(r_new) - float(r_prev)|,  b = sum |float(r_prev)|                  rows [tok0, tok0 + tok_rows) only
+ * and in the same pass r <- r_new, keep <- x1 (the copy the cached tail is taken against).  sums[0] = a, sums[1] = b: DEVICE
+ * doubles, deterministic (no atomics: eight fp32 terms per 16-byte vector, everything above in double in a fixed order that
+ * depends on (rows, D) alone).  workspace: alg_step_cache_workspace_bytes(rows, D) bytes, 8-byte aligned.  rows == 0 writes
+ * zeros.  The decision (a < threshold * b) is the host's: alg_amd/step_cache.py. */
+int64_t alg_step_cache_workspace_bytes(int rows, int D);
+int alg_step_cache_probe(void* keep, const void* x1, void* r, int rows, int D, int tok0, int tok_rows, void* workspace,
+                         double* sums, void* stream);
+
 /* wan:877-889, hy:1146-1160, 1230  CFG batch assembly in one launch (replaces cat([latents]*n) + cat(dim) + .to()):
  *   out[i, o, a, r] = a < A0 ? src0[i][o*s0_ostride + a*R + r] : src1[i][o*s1_ostride + (a1_off + a - A0)*R + r]
  * for i < n (<= 16), o < O, a < A0 + A1, r < R, cast to out_dtype.  src0 / src1 are HOST arrays of n device pointers
