@@ -34,6 +34,7 @@ EXPORTS = (
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap", "alg_attn_path_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
+    "alg_flash_attn_d128_ranges",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -122,6 +123,7 @@ def load_library():
     lib.alg_concat_cast.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_int] + [c_int64] * 7 + [
         c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d128.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p]
+    lib.alg_flash_attn_d128_ranges.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d128_ex.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
     lib.alg_flash_attn_d128_dual.argtypes = ([c_void_p] * 3 + [c_int] + [c_int64] * 4 + [c_void_p] * 2 + [c_int] + [c_int64] * 4 +
                                              [c_void_p] + [c_int] * 3 + [c_int64] * 4 + [c_float, c_void_p])
@@ -539,6 +541,28 @@ def flash_attn_d128(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, 
         return o
     _check(lib.alg_flash_attn_d128(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale),
                                    _stream()), "alg_flash_attn_d128")
+    return o
+
+
+def flash_attn_d128_ranges(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, scale, kv_ranges,
+                           q_off=0, k_off=0, vt_off=0, o_off=0):
+    """flash_attn_d128 (non-causal, ungrouped) in which each block of 256 queries attends to the key ranges of its row of
+    kv_ranges, an attn_window.KvRanges built for this (Sq, Skv): only that type is taken, so every table that reaches the kernel
+    from Python has been validated (include/alg_hip.h: alg_flash_attn_d128_ranges)."""
+    from .attn_window import KvRanges
+    if not isinstance(kv_ranges, KvRanges):
+        raise AlgHipError("flash_attn_d128_ranges takes an attn_window.KvRanges, got %s" % type(kv_ranges).__name__)
+    if kv_ranges.Sq != Sq or kv_ranges.Skv != Skv:
+        raise AlgHipError("flash_attn_d128_ranges: the table was built for Sq=%d Skv=%d, the call has Sq=%d Skv=%d"
+                          % (kv_ranges.Sq, kv_ranges.Skv, Sq, Skv))
+    lib = load_library()
+    for t in (q, k, vt, o):
+        _dev(t, "attention operand")
+    table = kv_ranges.on(q.device)
+    at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
+    _check(lib.alg_flash_attn_d128_ranges(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv, q_bs, q_rs,
+                                          k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale), _ptr(table), kv_ranges.max_ranges,
+                                          _stream()), "alg_flash_attn_d128_ranges")
     return o
 
 

@@ -21,6 +21,10 @@
 // so the waves of a workgroup may be inside or outside the statement independently.  A wave that left the statement RE-ENTERS
 // it at the next t = 1 (mod 4) (round 4's single-statement kernels stayed outside for good).
 //
+// The same frame serves alg_flash_attn_d128_ranges (opt-in frame-window attention, alg_amd/attn_window.py): there a workgroup runs
+// the key ranges of its row of a device table one after the other, each as a panel of its own, with one drain of the ring between
+// two of them.
+//
 // DEFAULT for non-causal, ungrouped attention over at least POLICY_TILES KV tiles; ALG_ATTN128_Q64=0 switches it off (the
 // 32-query pipelined kernel takes over), =2 takes every call of at least MIN_TILES tiles (tests).
 #include <stdlib.h>
@@ -53,8 +57,15 @@ struct P {
   uint64_t* clk;   // clock tap (calibrate.hip: alg_attn_clock_tap) or NULL
   int clk_slots;
   int use_statement;   // 0: every tile through the C++ tile body (ALG_ATTN128_Q64=3: tests of the frame on its own)
+  const int32_t* ranges;   // RANGES: device table [q_blocks][max_ranges][2] of (begin, end) key indices (alg_flash_attn_d128_ranges)
+  int max_ranges;
 };
 
+// RANGES = false: every key of the panel, ONE segment [0, Skv) -- the dense kernel.  RANGES = true: the workgroup's 256 queries
+// visit the key ranges of their row of p.ranges one after the other; each range is a SEGMENT the frame runs exactly as the dense
+// kernel runs a panel of that length whose K / V^T start at `begin` (prime the ring, tile 0 in C++, the statement from t = 1, the
+// tail in C++), with O, the running max and the row sum carried from segment to segment.
+template <bool RANGES>
 __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const k_ring = smem;
@@ -71,7 +82,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
     if (bh >= nbh) return;
   }
   const int b = bh / p.heads, h = bh - b * p.heads;
-  const int Sq = p.Sq, Skv = p.Skv;
+  const int Sq = p.Sq;
   const bool tap = p.clk != nullptr && (blockIdx.x & 63) == 0 && (int)(blockIdx.x >> 6) < p.clk_slots && wave == 0;   // clock tap: see attention.hip
   uint64_t tap_c0 = 0, tap_r0 = 0;
   if (tap) {
@@ -79,10 +90,16 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
     tap_r0 = wall_clock64();
   }
   const bf16_t* Q = p.q + (int64_t)b * p.q_bs + h * 128;
-  const bf16_t* K = p.k + (int64_t)b * p.k_bs + h * 128;
-  const bf16_t* VT = p.vt + (int64_t)b * p.vt_bs + (int64_t)h * 128 * p.vt_rs;
-  const int T = (Skv + KVB - 1) / KVB;
-  const bool ragged = (Skv & (KVB - 1)) != 0;
+  const bf16_t* const K0 = p.k + (int64_t)b * p.k_bs + h * 128;
+  const bf16_t* const VT0 = p.vt + (int64_t)b * p.vt_bs + (int64_t)h * 128 * p.vt_rs;
+  // the segment in hand: its first key's K row / V^T column, its length, and what follows from the length.  Everything below that
+  // says Skv, T, ragged or tend means the SEGMENT's (RANGES = false: the panel's, set once)
+  const bf16_t* K = K0;
+  const bf16_t* VT = VT0;
+  int Skv = p.Skv;
+  int seg_begin = 0;   // the segment's first key: what the V^T rows have left behind a column is counted from the row's start
+  int T = (Skv + KVB - 1) / KVB;
+  bool ragged = (Skv & (KVB - 1)) != 0;
   const float c = p.scale_log2;
   // O^T of the wave's two query halves: tile (qh, dt) = oa[4 qh + dt], lane (q = l31, h2) register e <-> d = 32 dt + (e & 3) + 8 (e >> 2) + 4 h2
   f32x16 oa[8];
@@ -210,6 +227,28 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
     }
   };
 
+  bool visited = !RANGES;   // a segment has run: the ring holds its tiles and its clamped prefetches may still be in flight
+  for (int seg = 0; seg < (RANGES ? p.max_ranges : 1); ++seg) {
+  if constexpr (RANGES) {
+    // defensive read: whatever the table holds, the segment lies inside the panel and starts on the dense kernel's tile grid
+    // (the bit-2/3 column permutation and the 16-byte alignment of the V^T DMA hold for begin % 64 == 0 only)
+    const int32_t* r = p.ranges + ((int64_t)qb * p.max_ranges + seg) * 2;
+    const int begin = __builtin_amdgcn_readfirstlane(min(max(r[0], 0), p.Skv)) & ~(KVB - 1);
+    const int end = __builtin_amdgcn_readfirstlane(min(max(r[1], 0), p.Skv));
+    if (end <= begin) continue;
+    if (visited) {
+      // hand-over of the ring: this wave's DMAs of the previous segment have landed, and no wave still reads its last tiles
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    visited = true;
+    K = K0 + (int64_t)begin * p.k_rs;
+    VT = VT0 + begin;
+    Skv = end - begin;
+    seg_begin = begin;
+    T = (Skv + KVB - 1) / KVB;
+    ragged = (Skv & (KVB - 1)) != 0;
+  }
   // the statement runs iterations t < tend: QK(t + 1) must not touch the masked (ragged) last tile.  Its DMA of K(t + 3) / V^T(t + 2)
   // reaches past the end in the last iterations: the buffer descriptors' num_records end the panel, such pieces fetch nothing
   const int tend = ragged ? T - 2 : T - 1;
@@ -251,7 +290,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
       }
       const int64_t k_tile_bytes = (int64_t)KVB * p.k_rs * 2;
       const int64_t k_left = ((int64_t)(Skv - 1) * p.k_rs + 128) * 2 - (int64_t)(t + 3) * k_tile_bytes;
-      const int64_t v_left = (int64_t)128 * p.vt_rs * 2 - (int64_t)(t + 2) * KVB * 2;
+      const int64_t v_left = (int64_t)128 * p.vt_rs * 2 - ((int64_t)seg_begin + (int64_t)(t + 2) * KVB) * 2;
       const uint64_t kt = uniform64((const char*)K + (int64_t)(t + 3) * k_tile_bytes);
       const uint64_t vtb = uniform64((const char*)VT + (int64_t)(t + 2) * KVB * 2);
       const int kd0 = sreg((int)(uint32_t)kt), kd1 = sreg((int)(uint32_t)(kt >> 32) & 0xffff), kd2 = sreg((int)(uint32_t)(k_left > 0 ? k_left : 0));
@@ -284,12 +323,13 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
     top_done = false;
     ++t;
   }
+  }   // segments
 
   const LaneCtx x = make_ctx(fresh_lane());
 #pragma unroll
   for (int qh = 0; qh < 2; ++qh) {
     const float l_tot = l_run[qh] + __shfl_xor(l_run[qh], 32, 64);
-    const float inv = 1.0f / l_tot;
+    const float inv = visited ? 1.0f / l_tot : 0.0f;   // (a block the table leaves without a key writes zeros)
     const int q_row = x.q_row + 32 * qh;
     if (q_row < Sq) {
       bf16_t* op = p.o + (int64_t)b * p.o_bs + (int64_t)q_row * p.o_rs + h * 128;
@@ -313,16 +353,12 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
 
 }  // namespace a128q
 
-// Returns ALG_OK when launched, 1 when this call is not covered (the caller goes on to attention128_pipe.hip / attention128.hip).
-int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                        int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs,
-                        int64_t o_rs, float scale, hipStream_t stream) {
+// Fills P and launches; 1 when the operands are beyond what the kernel addresses (31-bit byte offsets inside one (batch, head)).
+template <bool RANGES>
+static int launch_q64(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                      int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs, int64_t o_rs,
+                      float scale, const int32_t* ranges, int max_ranges, int use_statement, hipStream_t stream) {
   using namespace a128q;
-  // ALG_ATTN128_Q64: 1 (default) = calls over at least POLICY_TILES KV tiles; 2 = every call the kernel can take; 3 = as 2 with the
-  // statement switched off (every tile through the frame's C++ body: tests); 0 = off.
-  const int enabled = opt(OPT_ATTN128_Q64);
-  const int n_tiles = (Skv + KVB - 1) / KVB;
-  if (!enabled || n_tiles < (enabled == 1 ? POLICY_TILES : MIN_TILES)) return 1;
   // 31-bit BYTE offsets inside one (batch, head) for the DMA's lane offsets; V^T rows cover whole 64-key tiles
   if ((int64_t)(Skv + 64) * k_rs * 2 >= (1ll << 31) || (int64_t)129 * vt_rs * 2 >= (1ll << 31) ||
       (int64_t)Sq * q_rs * 2 >= (1ll << 31))
@@ -331,8 +367,8 @@ int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, i
   static PerDeviceOnce attr_set;
   const int dev_slot = current_device_slot();
   if (!device_done(attr_set, dev_slot)) {
-    if (hipFuncSetAttribute((const void*)flash_attn_d128_q64_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-        hipSuccess)
+    if (hipFuncSetAttribute((const void*)flash_attn_d128_q64_kernel<RANGES>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            LDS_BYTES) != hipSuccess)
       return 1;
     device_mark(attr_set, dev_slot);
   }
@@ -343,11 +379,65 @@ int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, i
   p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs; p.vt_bs = vt_bs; p.vt_rs = vt_rs; p.o_bs = o_bs; p.o_rs = o_rs;
   p.scale_log2 = scale * 1.4426950408889634f;
   p.clk = clock_tap_for((hipStream_t)stream, &p.clk_slots);
-  p.use_statement = enabled != 3;
+  p.use_statement = use_statement;
+  p.ranges = ranges;
+  p.max_ranges = max_ranges;
   const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
   if (grid > 0x7fffffff) return 1;
-  hipLaunchKernelGGL(flash_attn_d128_q64_kernel, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
-  return check_launch("alg_flash_attn_d128");
+  hipLaunchKernelGGL(flash_attn_d128_q64_kernel<RANGES>, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
+  return check_launch(what);
+}
+
+// Returns ALG_OK when launched, 1 when this call is not covered (the caller goes on to attention128_pipe.hip / attention128.hip).
+int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                        int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs,
+                        int64_t o_rs, float scale, hipStream_t stream) {
+  using namespace a128q;
+  // ALG_ATTN128_Q64: 1 (default) = calls over at least POLICY_TILES KV tiles; 2 = every call the kernel can take; 3 = as 2 with the
+  // statement switched off (every tile through the frame's C++ body: tests of the frame on its own); 0 = off.
+  const int enabled = opt(OPT_ATTN128_Q64);
+  const int n_tiles = (Skv + KVB - 1) / KVB;
+  if (!enabled || n_tiles < (enabled == 1 ? POLICY_TILES : MIN_TILES)) return 1;
+  return launch_q64<false>("alg_flash_attn_d128", q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs,
+                           o_rs, scale, nullptr, 0, enabled != 3, stream);
 }
 
 }  // namespace alg
+
+using namespace alg;
+
+// Each block of 256 queries attends to its row of a table of key ranges (include/alg_hip.h).  This kernel is the only one that
+// takes a table: ALG_ATTN128_Q64 routes this entry nowhere else, and only its value 3 (statement off) is honoured here.
+extern "C" int alg_flash_attn_d128_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
+                                          int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
+                                          int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
+                                          float scale, const int32_t* kv_ranges, int max_ranges, void* stream) {
+  if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
+    set_error("alg_flash_attn_d128_ranges: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", batch, heads, Sq, Skv);
+    return ALG_EINVAL;
+  }
+  if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > 4) {
+    set_error("alg_flash_attn_d128_ranges: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)",
+              (const void*)kv_ranges, max_ranges);
+    return ALG_EINVAL;
+  }
+  if (q_rstride % 8 || q_bstride % 8 || k_rstride % 8 || k_bstride % 8 || vt_rstride % 8 || vt_bstride % 8 ||
+      o_rstride % 4 || o_bstride % 4 || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) ||
+      ((uintptr_t)o & 7)) {
+    set_error("alg_flash_attn_d128_ranges: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned");
+    return ALG_EINVAL;
+  }
+  if (vt_rstride < (int64_t)((Skv + a128q::KVB - 1) / a128q::KVB) * a128q::KVB) {
+    set_error("alg_flash_attn_d128_ranges: vt row stride %lld must cover Skv rounded up to %d", (long long)vt_rstride,
+              a128q::KVB);
+    return ALG_EINVAL;
+  }
+  const int rc = launch_q64<true>("alg_flash_attn_d128_ranges", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
+                                  k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges,
+                                  opt(OPT_ATTN128_Q64) != 3, (hipStream_t)stream);
+  if (rc == 1) {
+    set_error("alg_flash_attn_d128_ranges: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large");
+    return ALG_ELIMIT;
+  }
+  return rc;
+}

@@ -29,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from . import _lib, lp_utils
+from . import _lib, attn_window, lp_utils
 from .pipeline_cogvideox_image2video_lowpass import retrieve_timesteps
 from .schedulers import FlowMatchEulerDiscreteScheduler
 
@@ -120,11 +120,13 @@ class HunyuanVideoImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, text_encoder_2=None, tokenizer_2=None, image_processor=None,
-                        device="cuda", fp8_attention=False, fp8=False, **_):
+                        device="cuda", fp8_attention=False, fp8=False, attn_window=0, **_):
         """Local-disk loader of a diffusers-format HunyuanVideo-I2V directory (`run.py:68-90`): `transformer/`,
         `text_encoder/` (Llava-Llama-3) + `tokenizer/` + `image_processor/`, `text_encoder_2/` (CLIP-L text tower) +
         `tokenizer_2/`, `vae/`, `scheduler/`.  `fp8=True` loads the transformer with e4m3 block linears
-        (HunyuanVideoTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in."""
+        (HunyuanVideoTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.
+        `attn_window` > 0 switches the transformer's frame-window joint attention on with that many latent frames on each side
+        (alg_amd/attn_window.py; off by default)."""
         import os
 
         from .schedulers import FlowMatchEulerDiscreteScheduler
@@ -136,6 +138,8 @@ class HunyuanVideoImageToVideoPipeline:
         if transformer is None:
             transformer = HunyuanVideoTransformer3DModel.from_pretrained(model_path, device=device, fp8_attention=fp8_attention,
                                                                          fp8=fp8)
+        if attn_window:
+            transformer.attn_window = int(attn_window)
         if text_encoder is None and has("text_encoder"):
             from .text_encoder_llava import LlavaForConditionalGeneration
             text_encoder = LlavaForConditionalGeneration.from_pretrained(model_path, device=device)
@@ -428,6 +432,7 @@ class HunyuanVideoImageToVideoPipeline:
         step_trace: Optional[list] = None,
         clip_prompt: Optional[Union[str, List[str]]] = None,
         negative_clip_prompt: Optional[Union[str, List[str]]] = None,
+        attn_window_dense_steps: int = 0,
     ):
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds, callback_on_step_end_tensor_inputs,
                           prompt_template, true_cfg_scale, guidance_scale)
@@ -570,8 +575,9 @@ class HunyuanVideoImageToVideoPipeline:
                 mask = cat(negative_prompt_attention_mask, prompt_attention_mask)
             n = latent_model_input.shape[0]
             timestep = t.expand(n).to(device=device, dtype=tdtype)  # hy:1230 (the timestep itself is cast to bf16)
-            noise_pred = self.transformer(
-                hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
+            # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
+            noise_pred = attn_window.call_transformer(
+                self.transformer, i < attn_window_dense_steps, hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
                 encoder_attention_mask=mask, pooled_projections=pooled, guidance=guidance,
                 attention_kwargs=attention_kwargs, return_dict=False)[0]
             # hy:1254-1261 keys the combine on shape[0] (3 -> three chunks, 2 -> two chunks, anything else: none)

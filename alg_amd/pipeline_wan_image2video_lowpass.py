@@ -25,12 +25,13 @@ condition video EVERY step with a freshly sampled posterior) is available.
 """
 from __future__ import annotations
 
+import functools
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, lp_utils, step_cache
+from . import _lib, attn_window, lp_utils, step_cache
 from .schedulers import UniPCMultistepScheduler
 
 
@@ -104,10 +105,12 @@ class WanImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, image_encoder=None, image_processor=None, device="cuda",
-                        fp8=False, fp8_attention=False, step_cache=0.0, **_):
+                        fp8=False, fp8_attention=False, step_cache=0.0, attn_window=0, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
         (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan).
-        `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default)."""
+        `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default);
+        `attn_window` > 0 its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by
+        default)."""
         import os
 
         from .image_encoder_clip import CLIPImageProcessor, CLIPVisionModel
@@ -121,6 +124,8 @@ class WanImageToVideoPipeline:
             transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention)
         if step_cache:
             transformer.step_cache = float(step_cache)
+        if attn_window:
+            transformer.attn_window = int(attn_window)
         if text_encoder is None and has("text_encoder"):
             text_encoder = UMT5EncoderModel.from_pretrained(model_path, device=device)
         if tokenizer is None:
@@ -398,6 +403,7 @@ class WanImageToVideoPipeline:
         latent_condition: Optional[torch.Tensor] = None,
         step_trace: Optional[list] = None,
         cfg_split=None,
+        attn_window_dense_steps: int = 0,
     ):
         self.check_inputs(prompt, negative_prompt, image, height, width, prompt_embeds, negative_prompt_embeds,
                           image_embeds, callback_on_step_end_tensor_inputs)
@@ -507,6 +513,8 @@ class WanImageToVideoPipeline:
                 raise UnboundLocalError("local variable 'latent_model_input' referenced before assignment "
                                         "(the Wan ALG loop needs guidance_scale > 1)")
             latent_model_input = assemble_channel_concat(latents, groups, tdtype)
+            # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
+            dit = functools.partial(attn_window.call_transformer, self.transformer, i < attn_window_dense_steps)
             n = latent_model_input.shape[0]
             timestep = t.expand(n).to(device)
             ehs = torch.cat(embeds, dim=0)
@@ -515,15 +523,14 @@ class WanImageToVideoPipeline:
                 # alg_amd.parallel.CFGPairSplit: this rank's share of the CFG passes, one all-gather merges the predictions
                 B_ = latents.shape[0]
                 rows = [p_ * B_ + b for p_ in cfg_split.my_passes(len(groups)) for b in range(B_)]
-                local = self.transformer(hidden_states=latent_model_input[rows].contiguous(), timestep=timestep[:len(rows)],
-                                         encoder_hidden_states=ehs[rows].contiguous(),
-                                         encoder_hidden_states_image=ehs_img[rows].contiguous(),
-                                         attention_kwargs=attention_kwargs, return_dict=False)[0]
+                local = dit(hidden_states=latent_model_input[rows].contiguous(), timestep=timestep[:len(rows)],
+                            encoder_hidden_states=ehs[rows].contiguous(), encoder_hidden_states_image=ehs_img[rows].contiguous(),
+                            attention_kwargs=attention_kwargs, return_dict=False)[0]
                 noise_pred = cfg_split.merge(local.contiguous(), len(groups), B_)
             else:
                 cache_kw = dict(cache_keys=step_cache.pass_keys(len(groups), latents.shape[0]),
                                 cache_force=i == len(timesteps) - 1) if use_cache else {}
-                noise_pred = self.transformer(
+                noise_pred = dit(
                     hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
                     encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False, **cache_kw)[0]
             # wan:919-924 keys the 3-chunk combine on shape[0] == 3, so the reference's 3-pass step only works for one

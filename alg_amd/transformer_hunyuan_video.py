@@ -36,6 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .attn_window import frame_window_ranges
 from .transformer_wan import k_scale_bound
 
 BF = torch.bfloat16
@@ -173,6 +174,13 @@ class HunyuanVideoTransformer3DModel:
         (one scale per head, transformer_wan.k_scale_bound) as e4m3 itself, V^T is quantised per row behind its GEMMs.  The token
         refiner stays bf16.  Off, the forward is the bf16 one bit for bit."""
         self.fp8_attention = bool(fp8_attention)
+        # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): in the joint attention of the dual-
+        # and single-stream blocks a block of latent queries attends to the conditioning frames (attn_sink_frames), to the latent
+        # frames within attn_window of its own and to the sample's valid prompt keys; prompt queries see everything.  The launches
+        # stay per sample (alg_flash_attn_d128_ranges).  0: today's launches, nothing allocated
+        self.attn_window = 0
+        self.attn_sink_frames = 1
+        self._attn_ranges = {}    # (F, hw, valid, J, window, sink) -> KvRanges, or None where the window covers the whole video
         self.fp8 = bool(fp8)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
@@ -398,6 +406,23 @@ class HunyuanVideoTransformer3DModel:
             for L in self.single:
                 self._quantize_block(L, self.FP8_SINGLE, drop_bf16=False)
 
+    def _window_ranges(self, frames, hw, valid, J):
+        """The frame-window table of one sample of this video shape (device-resident, built once per key: before any capture that
+        replays it), or None where the window is the dense attention.  Keys: frames * hw latent tokens, then `valid` prompt keys."""
+        window, sink = int(self.attn_window), int(self.attn_sink_frames)
+        if window < 0 or sink < 0:
+            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
+        if self.fp8_attention:
+            raise ValueError("attn_window does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges")
+        key = (frames, hw, valid, J, window, sink)
+        if key not in self._attn_ranges:
+            S = frames * hw
+            r = frame_window_ranges(frames, hw, window, sink_frames=sink, tail=(S, S + valid), rows=J)
+            if r is not None:
+                r.on(self.device)   # uploaded here, once
+            self._attn_ranges[key] = r
+        return self._attn_ranges[key]
+
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask, pooled_projections,
                  guidance=None, attention_kwargs=None, return_dict=True):
         cfg, w, G, T = self.config, self.w, _lib.gemm, self._timed
@@ -503,6 +528,7 @@ class HunyuanVideoTransformer3DModel:
 
         f8 = self.fp8_attention
         H8 = _lib.headnorm_rope_fp8
+        kvr = [self._window_ranges(F_, first, valid[b], J) for b in range(N)] if self.attn_window else [None] * N   # None: dense
 
         def attention(bi=0):
             """bi: index of the block in dual + single order (its K scales, fp8_attention)."""
@@ -519,6 +545,12 @@ class HunyuanVideoTransformer3DModel:
                                              q_off=b * J * 2 * D, qs_off=b * J * heads, k_off=b * J * 2 * D + D,
                                              ks_off=(bi * N + b) * heads, vt_off=b * D * ws.J_pad, vts_off=b * D,
                                              o_off=b * J * (D + M))
+                    continue
+                if kvr[b] is not None:
+                    _lib.flash_attn_d128_ranges(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D,
+                                                2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kvr[b],
+                                                q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
+                                                o_off=b * J * (D + M))
                     continue
                 _lib.flash_attn_d128(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D,
                                      D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, q_off=b * J * 2 * D,

@@ -31,6 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .attn_window import frame_window_ranges
 from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
@@ -178,6 +179,12 @@ class WanTransformer3DModel(StepCacheHost):
         # on the last computed forward.  0.0: every forward is the plain one, launch for launch.
         self.step_cache = 0.0
         self.step_cache_max_consecutive = 0   # at most this many skipped forwards in a row (0: no cap)
+        # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): the self-attention of every block
+        # attends to the conditioning frames (attn_sink_frames) and to the latent frames within attn_window of the query block's
+        # own, as ONE alg_flash_attn_d128_ranges launch for the whole batch.  0: today's launches, nothing allocated
+        self.attn_window = 0
+        self.attn_sink_frames = 1
+        self._attn_ranges = {}    # (F, hw, window, sink) -> KvRanges, or None where the window covers the whole video
         if config.qk_norm != "rms_norm_across_heads" or config.attention_head_dim != 128:
             raise NotImplementedError("the Wan DiT path is built for rms_norm_across_heads and head_dim 128")
         if tuple(config.patch_size)[0] != 1:
@@ -369,6 +376,22 @@ class WanTransformer3DModel(StepCacheHost):
             ws.vt8s = torch.empty(N, D, dtype=torch.float32, device=dev)
         return ws
 
+    def _window_ranges(self, frames, hw):
+        """The frame-window table of this video shape (device-resident, built once per (F, hw, window, sink): before any capture
+        that replays it), or None where the window is the dense attention."""
+        window, sink = int(self.attn_window), int(self.attn_sink_frames)
+        if window < 0 or sink < 0:
+            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
+        if self.fp8_attention:
+            raise ValueError("attn_window does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges")
+        key = (frames, hw, window, sink)
+        if key not in self._attn_ranges:
+            r = frame_window_ranges(frames, hw, window, sink_frames=sink)
+            if r is not None:
+                r.on(self.device)   # uploaded here, once
+            self._attn_ranges[key] = r
+        return self._attn_ranges[key]
+
     # ---- forward -----------------------------------------------------------------------------------------------------
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
                  attention_kwargs=None, return_dict=True, cache_keys=None, cache_force=False):
@@ -453,6 +476,7 @@ class WanTransformer3DModel(StepCacheHost):
         use_packed = not self.fp8 and self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         packed = None
         sc = self._step_cache_begin(ws.x, cache_keys, cache_force, 0, S)   # None: off, nothing below differs from the plain forward
+        kvr = self._window_ranges(F_, S // F_) if self.attn_window else None    # None: the dense launch
         for li, L in enumerate(self.blocks):
             if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
                 break                 # hit: x = x1 + the cached tail, straight to the head
@@ -482,8 +506,12 @@ class WanTransformer3DModel(StepCacheHost):
             else:
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
-                T("attn_self", _lib.flash_attn_d128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
-                  S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D)
+                if kvr is not None:
+                    T("attn_self", _lib.flash_attn_d128_ranges, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
+                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, k_off=D)
+                else:
+                    T("attn_self", _lib.flash_attn_d128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
+                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D)
             lin("gemm_out", ws.att, L.wo, ws.x, S, D, D, D, D, bias=L.bo, R=ws.x, ldr=D, gate=ws.mod,
                 gate_off=m0 + 2 * D, strideGate=mod_bs, batch=N, strideA=S * D, strideC=S * D, strideR=S * D,
                 seg_split=1 << 30, flags=_lib.GEMM_GATE_F32)

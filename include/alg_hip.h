@@ -282,6 +282,26 @@ int alg_flash_attn_d128_ex(const void* q, const void* k, const void* vt, void* o
                            int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, int kv_group, int causal,
                            void* stream);
 
+/* alg_flash_attn_d128 (non-causal, ungrouped, bf16; the same layouts, strides and alignment) in which each block of 256 queries
+ * attends to a short list of key ranges instead of to all keys: the primitive under the opt-in frame window of the Wan and
+ * HunyuanVideo self-attention (alg_amd/attn_window.py).  Always the 64-queries-per-wave kernel (attention128_q64.hip), any Skv.
+ *   kv_ranges : DEVICE table int32 [q_blocks][max_ranges][2] of (begin, end) key indices, q_blocks = ceil(Sq / 256); one table
+ *               serves every batch item and head of the launch.  max_ranges is 1..4.
+ *   A table is valid when in each block the used entries come first, sorted and disjoint, begin % 64 == 0, begin < end <= Skv,
+ *   unused trailing entries are (0, 0), and every block has at least one key.
+ * o[q] = softmax(scale * q k^T restricted to the union of the ranges of q's block) v, with the numerics of alg_flash_attn_d128: a
+ * range [begin, end) is computed exactly as that entry computes a panel of end - begin keys whose k / vt start at key `begin`, with
+ * the running max, the row sum and the fp32 accumulator carried from range to range.  vt's padding rule holds per range: the
+ * columns up to the next multiple of 64 behind `end` are read and multiplied by p = 0 (finite values).
+ * The kernel reads the table defensively -- begin / end clamped into [0, Skv], begin rounded down to a multiple of 64, empty
+ * entries skipped, a block left without a key writes zeros -- so no table content makes it read outside the panels; a null or
+ * misaligned table and max_ranges outside 1..4 are ALG_EINVAL before any launch.  ALG_ATTN128_Q64=3 runs it with the generated
+ * statement switched off (tests); the other values of that variable do not route this entry anywhere else. */
+int alg_flash_attn_d128_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                               int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride, int64_t vt_bstride,
+                               int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, const int32_t* kv_ranges,
+                               int max_ranges, void* stream);
+
 /* Opt-in e4m3 form of alg_flash_attn_d128 on v_mfma_scale_f32_32x32x64_f8f6f4 (attention128_fp8.hip): non-causal, ungrouped
  * (kv_group != 1 or causal != 0 is ALG_EINVAL), separate Sq / Skv, ragged last tile, bf16 output; strides in elements = bytes.
  *   q  : OCP e4m3, element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d;  q_scale: float32 [batch][Sq][heads]

@@ -1,0 +1,280 @@
+"""Measurements of the opt-in frame-window self-attention on one GPU, written as one JSON file (profiles/attn_window_ab.json is a
+run of this).  One job, arms alternated, package power and shader clock sampled per arm (bench.SmiSampler).
+
+    python scripts/attn_window_ab.py --out profiles/attn_window_ab.json [--only kernel|steps|accuracy]
+
+  kernel    alg_flash_attn_d128 against alg_flash_attn_d128_ranges at the three launch shapes (C3 32,760 x 40 heads, C5 75,600 x 40,
+            C4 119,056 queries x 118,848 keys x 24 heads): the dense entry (first and last arm: their distance is the job's spread),
+            the ranged entry with the one-full-range table, and with the frame windows whose coverage is closest to 3/4, 1/2 and
+            1/4 -- milliseconds, coverage, and ms / dense ms
+  steps     the C3 / C4 / C5 workloads of bench.py (what `bench.py --workload cX --steps 2 --warmup 1 --set attn_window=W` times:
+            loop iterations 0-1 through the pipeline's __call__ behind one warm-up step), attn_window = 0 first and last and the
+            1/2-coverage window between them, in one process per workload
+  accuracy  4-step ALG samplers on the trained-like Wan and HunyuanVideo models of tests/helpers/trained_like_cases.py at 9 latent
+            frames: relative L2 of the final latents with attn_window = 1, 2, 4 against the dense run, next
+            to the dense run's distance to the fp32 loop oracle (the bf16-to-fp32 floor of that run)
+
+Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
+import argparse
+import gc
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
+
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from alg_amd import _lib  # noqa: E402
+from alg_amd.attn_window import frame_window_ranges, full_ranges  # noqa: E402
+
+BF = torch.bfloat16
+DEV = torch.device("cuda:0")
+
+# (frames, tokens per frame, prompt keys, prompt rows, heads)
+SHAPES = {"c3_32760x40": (21, 1560, 0, 0, 40), "c5_75600x40": (21, 3600, 0, 0, 40), "c4_119056x24": (33, 3600, 48, 256, 24)}
+
+
+def table_for(F, hw, valid, rows, window):
+    S = F * hw
+    return frame_window_ranges(F, hw, window, tail=(S, S + valid) if valid else None, rows=S + rows if rows else None)
+
+
+def window_for(F, hw, valid, rows, coverage):
+    """The window whose table's coverage is closest to `coverage`."""
+    best = None
+    for w in range(1, F):          # (attn_window = 0 is the models' "off")
+        t = table_for(F, hw, valid, rows, w)
+        if t is not None and (best is None or abs(t.coverage - coverage) < abs(best[1].coverage - coverage)):
+            best = (w, t)
+    return best
+
+
+def timed(fn, iters, warm=1):
+    for _ in range(warm):
+        fn()
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(iters)]
+    with bench.SmiSampler(0, period=0.05) as smi:
+        for e0, e1 in ev:
+            e0.record()
+            fn()
+            e1.record()
+        torch.cuda.synchronize()
+    t = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+    s = smi.summary() or {}
+    return {"median_ms": statistics.median(t), "min_ms": t[0], "max_ms": t[-1], "iters": iters,
+            "power_w": (s.get("power_w") or {}).get("mean"), "sclk_mhz": (s.get("sclk_mhz") or {}).get("mean")}
+
+
+def kernel_arms(name, iters):
+    F, hw, valid, rows, heads = SHAPES[name]
+    S, D = F * hw, heads * 128
+    Sq, Skv = S + rows, S + valid
+    pad = (Sq + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(Sq, 2 * D, generator=g, device=DEV, dtype=BF)          # the models' layout: Q | K rows, V^T apart
+    vt = torch.randn(D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(Sq, D, dtype=BF, device=DEV)
+    scale = 1.0 / 128 ** 0.5
+    args = (qk, qk, vt, o, 1, heads, Sq, Skv, Sq * 2 * D, 2 * D, Sq * 2 * D, 2 * D, D * pad, pad, Sq * D, D, scale)
+    dense = lambda: _lib.flash_attn_d128(*args, k_off=D)
+    ranged = lambda t: (lambda: _lib.flash_attn_d128_ranges(*args, t, k_off=D))
+    arms = [("dense_first", dense, 1.0, None), ("full_range", ranged(full_ranges(Sq, Skv)), 1.0, None)]
+    for label, cov in (("three_quarters", 0.75), ("half", 0.5), ("quarter", 0.25)):
+        w, t = window_for(F, hw, valid, rows, cov)
+        t.device_table
+        arms.append((label, ranged(t), t.coverage, w))
+    arms.append(("dense_last", dense, 1.0, None))
+    out = {"queries": Sq, "keys": Skv, "heads": heads, "frames": F, "tokens_per_frame": hw, "arms": {}}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        dense()
+        torch.cuda.synchronize()
+    for label, fn, cov, w in arms:
+        r = timed(fn, iters)
+        r.update(coverage=cov, attn_window=w)
+        out["arms"][label] = r
+    a, b = out["arms"]["dense_first"]["median_ms"], out["arms"]["dense_last"]["median_ms"]
+    d = out["dense_ms_mean"] = (a + b) / 2
+    out["dense_spread_ms"] = abs(a - b)
+    for r in out["arms"].values():
+        r["ms_over_dense"] = r["median_ms"] / d
+    out["full_range_minus_dense_ms"] = out["arms"]["full_range"]["median_ms"] - d
+    out["full_range_within_dense_spread"] = out["full_range_minus_dense_ms"] <= out["dense_spread_ms"]
+    del qk, vt, o
+    torch.cuda.empty_cache()
+    return out
+
+
+def step_arms(workload):
+    F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
+    w_half = window_for(F, hw, valid, rows, 0.5)[0]
+    args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
+    wl.build()
+    torch.cuda.synchronize()
+    out = {"attn_window_half": w_half, "arms": {}}
+    outs = {}
+    for label, w in (("off_first", 0), ("window_half", w_half), ("off_last", 0)):
+        wl.model.attn_window = w
+        bench.run_steps(wl, 1)
+        torch.cuda.synchronize()
+        with bench.SmiSampler(0) as smi:
+            t0 = time.perf_counter()
+            bench.run_steps(wl, 2)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+        sm = smi.summary() or {}
+        outs[label] = wl.last_out.float().cpu()
+        out["arms"][label] = {"attn_window": w, "seconds": s, "ms_per_step": s / 2 * 1e3, "frames_per_s": wl.frames * 2 / wl.steps_per_video / s,
+                              "finite": bool(torch.isfinite(wl.last_out.float()).all().item()),
+                              "power_w": (sm.get("power_w") or {}).get("mean"), "sclk_mhz": (sm.get("sclk_mhz") or {}).get("mean")}
+    a, b = out["arms"]["off_first"]["ms_per_step"], out["arms"]["off_last"]["ms_per_step"]
+    out["off_ms_per_step_mean"], out["off_spread_ms"] = (a + b) / 2, abs(a - b)
+    out["window_half_over_off"] = out["arms"]["window_half"]["ms_per_step"] / out["off_ms_per_step_mean"]
+    # (C4 draws fresh latents from its generator on every call: its two dense runs are different videos)
+    out["off_first_equals_off_last"] = bool(torch.equal(outs["off_first"], outs["off_last"])) if "latents" in wl.kwargs else None
+    kvr = [t for t in wl.model._attn_ranges.values() if t is not None]
+    out["coverage"] = kvr[0].coverage if kvr else None
+    wl.model.attn_window = 0
+    del wl, outs
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def _rel(a, b):
+    return ((a.double() - b.double()).norm() / b.double().norm()).item()
+
+
+def _window_arms(model, call, frames, dense):
+    arms = {}
+    for w in (1, 2, 4):
+        model.attn_window = w
+        model._attn_ranges.clear()
+        got = call()
+        kvr = [t for t in model._attn_ranges.values() if t is not None]
+        arms["attn_window_%d" % w] = {"rel_l2_vs_dense": _rel(got, dense), "coverage": min((t.coverage for t in kvr), default=1.0)}
+    model.attn_window = 0
+    return arms
+
+
+def accuracy_wan(frames=9, steps=4):
+    """A 4-step ALG sampler on the trained-like medium Wan model (tests/helpers/trained_like_cases.py: 4 heads x 128, 2 blocks) at
+    `frames` latent frames of 384 tokens."""
+    from alg_amd.pipeline_wan_image2video_lowpass import WanImageToVideoPipeline
+    from alg_amd.schedulers import UniPCMultistepScheduler
+    from alg_amd.transformer_wan import WanTransformer3DModel, WanTransformerConfig
+    from helpers.trained_like_cases import wan_case
+    from oracle import loop_oracle, wan_oracle
+    from oracle.sched_oracle import UniPCOracle
+    kw, ocfg, sd, _ = wan_case("medium")
+    model = WanTransformer3DModel(WanTransformerConfig(**kw), sd, device=DEV)
+    g = torch.Generator().manual_seed(8)
+    H, W = 32, 48
+    lat, cond = torch.randn(1, 16, frames, H, W, generator=g), torch.randn(1, 20, frames, H, W, generator=g)
+    pe, ne = torch.randn(1, 512, 64, generator=g).to(BF), torch.randn(1, 512, 64, generator=g).to(BF)
+    ie = torch.randn(1, 257, 64, generator=g).to(BF)
+    alg = dict(lp_filter_type="down_up", lp_resize_factor=0.4, lp_strength_schedule_type="interval",
+               schedule_interval_start_time=0.0, schedule_interval_end_time=0.3)
+    pipe = WanImageToVideoPipeline(transformer=model, scheduler=UniPCMultistepScheduler(flow_shift=3.0)).to(DEV)
+
+    def call():
+        return pipe(prompt_embeds=pe.to(DEV), negative_prompt_embeds=ne.to(DEV), image_embeds=ie.to(DEV), image_condition=cond.to(DEV),
+                    latents=lat.to(DEV), height=H * 8, width=W * 8, num_frames=4 * (frames - 1) + 1, num_inference_steps=steps,
+                    guidance_scale=5.0, output_type="latent", use_low_pass_guidance=True, lp_filter_in_latent=True,
+                    **alg).frames.float().cpu()
+
+    dense = call()
+    sd32 = {k: v.float() for k, v in sd.items()}
+    want = loop_oracle.wan_denoise_loop(lambda x, ts, e, ei: wan_oracle.wan_forward(ocfg, sd32, x.float(), ts.float(), e.float(), ei.float()).to(BF),
+                                        UniPCOracle(flow_shift=3.0), lat, cond, pe, ne, ie, steps, guidance_scale=5.0,
+                                        use_low_pass_guidance=True, **alg)
+    return {"model": "trained-like Wan medium (4 heads x 128, 2 blocks), %d latent frames x 384 tokens" % frames, "steps": steps,
+            "bf16_to_fp32_floor_rel_l2": _rel(dense, want.float()), "arms": _window_arms(model, call, frames, dense)}
+
+
+def accuracy_hunyuan(frames=9, steps=4):
+    """A 4-step true-CFG ALG sampler on the trained-like small HunyuanVideo model (1 dual + 1 single block, 4 heads x 128) at `frames`
+    latent frames of 256 tokens, prompts of 20 tokens (17 / 9 valid)."""
+    from alg_amd import FlowMatchEulerDiscreteScheduler, HunyuanVideoImageToVideoPipeline
+    from alg_amd.transformer_hunyuan_video import HunyuanVideoTransformer3DModel, HunyuanVideoTransformerConfig
+    from helpers.trained_like_cases import hy_case
+    from oracle import hy_oracle, loop_oracle
+    from oracle.sched_oracle import FlowMatchEulerOracle
+    kw, ocfg, sd, _ = hy_case("token_replace")
+    sd32 = {k: v.float() for k, v in sd.items()}
+    model = HunyuanVideoTransformer3DModel(HunyuanVideoTransformerConfig(**kw), sd, device=DEV)
+    g = torch.Generator().manual_seed(8)
+    H = W = 32
+    lat, img = torch.randn(1, 16, frames, H, W, generator=g), torch.randn(1, 16, 1, H, W, generator=g)
+    mk = lambda v: (torch.randn(1, 20, 64, generator=g).to(BF), torch.randn(1, 64, generator=g).to(BF),
+                    torch.cat([torch.ones(1, v), torch.zeros(1, 20 - v)], dim=1).to(BF))
+    pos, neg = mk(17), mk(9)
+    alg = dict(lp_filter_type="down_up", lp_resize_factor=0.625, lp_strength_schedule_type="interval",
+               schedule_interval_start_time=0.0, schedule_interval_end_time=0.3)
+    pipe = HunyuanVideoImageToVideoPipeline(transformer=model, scheduler=FlowMatchEulerDiscreteScheduler(shift=7.0)).to(DEV)
+    d = lambda t_: t_.to(DEV)
+
+    def call():
+        return pipe(prompt_embeds=d(pos[0]), pooled_prompt_embeds=d(pos[1]), prompt_attention_mask=d(pos[2]),
+                    negative_prompt_embeds=d(neg[0]), negative_pooled_prompt_embeds=d(neg[1]),
+                    negative_prompt_attention_mask=d(neg[2]), negative_prompt=None, image_latents=d(img), latents=d(lat),
+                    height=H * 8, width=W * 8, num_frames=4 * (frames - 1) + 1, num_inference_steps=steps, true_cfg_scale=6.0,
+                    guidance_scale=1.0, output_type="latent", use_low_pass_guidance=True, lp_filter_in_latent=True,
+                    **alg).frames[:, :, 1:].float().cpu()
+
+    dense = call()
+    want = loop_oracle.hunyuan_denoise_loop(
+        lambda x, ts, e, m, p_, g_: hy_oracle.hy_forward(ocfg, sd32, x.float(), ts.float(), e.float(), m.float(), p_.float(), None).to(BF),
+        FlowMatchEulerOracle(shift=7.0), lat, img, pos, neg, steps, true_cfg_scale=6.0, guidance_scale=1.0,
+        use_low_pass_guidance=True, guidance_embeds=False, **alg)[:, :, 1:]
+    return {"model": "trained-like HunyuanVideo small config (4 heads x 128, 1 dual + 1 single block), %d latent frames x 256 tokens"
+                     % frames, "steps": steps, "bf16_to_fp32_floor_rel_l2": _rel(dense, want.float()),
+            "arms": _window_arms(model, call, frames, dense)}
+
+
+def accuracy():
+    return {"wan": accuracy_wan(), "hunyuan": accuracy_hunyuan()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
+    ap.add_argument("--iters", type=int, default=5)
+    a = ap.parse_args()
+    parts = a.only or ["kernel", "accuracy", "steps"]
+    res = {}
+    if os.path.exists(a.out):
+        res = json.load(open(a.out))
+    res["device"] = torch.cuda.get_device_name(0)
+    res["weights"] = "synthetic; the accuracy arms bound nothing on a trained checkpoint and visual quality is unmeasured"
+
+    def save():
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+    if "kernel" in parts:
+        res["kernel"] = {}
+        for name in SHAPES:
+            res["kernel"][name] = kernel_arms(name, a.iters)
+            save()
+    if "accuracy" in parts:
+        res["accuracy"] = accuracy()
+        save()
+    if "steps" in parts:
+        res["steps"] = {}
+        for wlname in ("c3", "c5", "c4"):
+            res["steps"][wlname] = step_arms(wlname)
+            save()
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
