@@ -407,6 +407,9 @@ int alg_mul_bf16(const void* a, const void* b, void* out, int64_t numel, void* s
  *   x : padded input [frames + kt - 1][Hp][Wp][Cin], readable for 2*Wp + 2 rows past its end
  *   w : [Cout][kt*9][Cin] bf16 (tap-major (dt, dy, dx), channels innermost);  bias: [Cout] or NULL
  *   y : virtual output [frames][Hp][Wp][Cout];  res: optional residual in y's layout, y = res + conv (may alias y)
+ * Output row r of frame t is the sum over (dt, dy, dx, c) of x[(t + dt)*Hp*Wp + r + dy*Wp + dx][c] * w[o][(dt, dy, dx)][c],
+ * accumulated in fp32; y = bf16(sum + bias), and with a residual y = bf16(res + bf16(sum + bias)) -- the convolution's bf16
+ * result, then the add, as two torch ops round.  Rows with y < H and x < W never read x's slack or res's don't-care rows.
  * Cin a power of two >= 64 (pad thinner inputs with zero channels), Cout % 4 == 0.
  * mode ALG_CONV_PAIR (Cout <= 128; the GEMM tile is 256 columns wide): one GEMM row produces TWO neighbouring voxels, so a
  * 128-channel convolution fills the tile: w is then [2*Cout][kt*3*4][Cin] with rows [0, Cout) = the kernel at dx 0..2

@@ -7,6 +7,7 @@ import torch.nn.functional as F
 
 from alg_amd import _lib
 from alg_amd.autoencoder_kl_cogvideox import AutoencoderKLCogVideoX, AutoencoderKLCogVideoXConfig, _Level
+from helpers import conv_cl_ref
 from oracle import vae_oracle
 
 pytestmark = pytest.mark.gpu
@@ -18,22 +19,15 @@ def _dev():
 
 def _padded(x, time_pad):
     """NCTHW fp32 (B = 1) -> padded channels-last bf16 flat buffer [T + time_pad][H + 2][W + 2][C] (+ slack)."""
-    _, C, T, H, W = x.shape
-    if time_pad:
-        x = torch.cat([x[:, :, :1]] * time_pad + [x], dim=2)
-    x = F.pad(x, (1, 1, 1, 1))
-    flat = x[0].permute(1, 2, 3, 0).contiguous().bfloat16().reshape(-1)
-    return torch.cat([flat, torch.zeros((2 * (W + 2) + 4) * C, dtype=torch.bfloat16)]).to(_dev())
+    return conv_cl_ref.padded(x, time_pad).to(_dev())
 
 
 def _virtual(x, fill=7.0):
     """NCTHW (B = 1) -> virtual layout [T][H + 2][W + 2][C] with a sentinel in the don't-care rows."""
-    x = F.pad(x, (0, 2, 0, 2), value=fill)
-    return x[0].permute(1, 2, 3, 0).contiguous().bfloat16().reshape(-1).to(_dev())
+    return conv_cl_ref.virtual(x, fill).to(_dev())
 
 
-def _from_virtual(buf, T, H, W, C):
-    return buf.reshape(T, H + 2, W + 2, C)[:, :H, :W].permute(3, 0, 1, 2).float().cpu()
+_from_virtual = conv_cl_ref.from_virtual
 
 
 @pytest.mark.parametrize("Cin,Cout,kt,res,pair", [
@@ -51,7 +45,7 @@ def test_conv_cl_matches_conv3d(Cin, Cout, kt, res, pair):
     want = F.conv3d(xin, w, b, padding=(0, 1, 1))
     if res:
         want = want + r
-    wp = w.reshape(Cout, Cin, -1).permute(0, 2, 1).reshape(Cout, -1).contiguous().bfloat16().to(_dev())
+    wp = conv_cl_ref.weight_layout(w).to(_dev())
     bp = b.bfloat16().to(_dev())
     if pair:
         wp, bp = _lib.pack_conv_pair(wp, bp, kt)
@@ -245,8 +239,8 @@ def test_stride2_conv_and_repitch(Cin, Cout):
     b = torch.randn(Cout, generator=g).bfloat16().float()
     xp = F.pad(x[0].permute(1, 0, 2, 3), (0, 1, 0, 1))
     want = F.conv2d(xp, w, b, stride=2).permute(1, 0, 2, 3)                       # [Cout, T, H/2, W/2]
-    wp = w.reshape(Cout, Cin, 9).permute(0, 2, 1).reshape(Cout, -1).contiguous().bfloat16().to(_dev())
-    m = H // 2 * (W + 2)
+    wp = conv_cl_ref.weight_layout(w).to(_dev())
+    m = conv_cl_ref.stride2_rows(H, W + 2)
     wide = torch.full((T * m * Cout,), 3.0, dtype=torch.bfloat16, device=_dev())
     _lib.conv_cl(_padded(x, 0), wp, b.bfloat16().to(_dev()), None, wide, T, H + 2, W + 2, Cin, Cout, 1, stride2=True)
     out = torch.full((T * (H // 2 + 2) * (W // 2 + 2) * Cout,), 5.0, dtype=torch.bfloat16, device=_dev())
