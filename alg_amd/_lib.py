@@ -34,7 +34,7 @@ EXPORTS = (
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap", "alg_attn_path_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
-    "alg_flash_attn_d128_ranges",
+    "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -186,6 +186,7 @@ def load_library():
     lib.alg_qk_norm_rope_scaled.argtypes = [c_void_p] * 7 + [c_int, c_int, c_int, c_int, c_float, c_float, c_void_p]
     lib.alg_flash_attn_d64_ex.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64,
                                           c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p]
+    lib.alg_flash_attn_d64_ranges.argtypes = [c_void_p] * 4 + [c_int] * 3 + [c_int64] * 6 + [c_void_p, c_int, c_void_p]
     lib.alg_patchify.argtypes = [c_void_p, c_int64, POINTER(c_void_p), c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_void_p]
     lib.alg_unpatchify.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
@@ -983,6 +984,27 @@ def flash_attn_d64(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstrid
                                      _ptr(o), batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride,
                                      o_rstride, float(scale), flags, _ptr(ws), wsb, _stream()),
            "alg_flash_attn_d64")
+
+
+def flash_attn_d64_ranges(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride,
+                          kv_ranges, q_off=0, k_off=0):
+    """flash_attn_d64(q_prescaled=True) in which each block of 256 queries attends to the key ranges of its row of kv_ranges, an
+    attn_window.KvRanges built for Sq == Skv == S: only that type is taken, so every table that reaches the kernel from Python has
+    been validated (include/alg_hip.h: alg_flash_attn_d64_ranges).  One launch: no split-KV tail, no workspace."""
+    from .attn_window import KvRanges
+    if not isinstance(kv_ranges, KvRanges):
+        raise AlgHipError("flash_attn_d64_ranges takes an attn_window.KvRanges, got %s" % type(kv_ranges).__name__)
+    if kv_ranges.Sq != S or kv_ranges.Skv != S:
+        raise AlgHipError("flash_attn_d64_ranges: the table was built for Sq=%d Skv=%d, the call has Sq=Skv=%d"
+                          % (kv_ranges.Sq, kv_ranges.Skv, S))
+    lib = load_library()
+    for t in (q, k, vt, o):
+        _dev(t, "attention operand")
+    table = kv_ranges.on(q.device)
+    _check(lib.alg_flash_attn_d64_ranges(c_void_p(q.data_ptr() + 2 * q_off), c_void_p(k.data_ptr() + 2 * k_off), _ptr(vt), _ptr(o),
+                                         batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride,
+                                         _ptr(table), kv_ranges.max_ranges, _stream()), "alg_flash_attn_d64_ranges")
+    return o
 
 
 def layernorm_modulate(x, y, weight, bias, scale, shift, mod_bstride, batch, rows, D, seg_split, eps,

@@ -1,11 +1,12 @@
-"""Frame-window self-attention for the head_dim 128 video DiTs (opt-in, an extension of this port: the reference attends to all keys).
+"""Frame-window self-attention for the video DiTs (opt-in, an extension of this port: the reference attends to all keys).
 
-The primitive is alg_flash_attn_d128_ranges (include/alg_hip.h, attention128_q64.hip): each block of 256 queries attends to a
-short list of key ranges, exactly (a masked softmax with the dense kernel's numerics).  The tokens of a video latent are laid out
-frame by frame, so "the frames f - W .. f + W" is ONE contiguous run of keys, and the frame window is a host-side policy on top
-of the primitive:
+The primitives are alg_flash_attn_d128_ranges (Wan, HunyuanVideo; attention128_q64.hip) and alg_flash_attn_d64_ranges (CogVideoX;
+attention.hip), both in include/alg_hip.h: each block of 256 queries attends to a short list of key ranges, exactly (a masked
+softmax with the dense kernel's numerics).  The tokens of a video latent are laid out frame by frame, so "the frames f - W ..
+f + W" is ONE contiguous run of keys, and the frame window is a host-side policy on top of the primitives:
 
-    KvRanges             a validated table of key ranges, uploaded once; the only thing _lib.flash_attn_d128_ranges takes
+    KvRanges             a validated table of key ranges, uploaded once; the only thing _lib.flash_attn_d128_ranges and
+                         _lib.flash_attn_d64_ranges take
     frame_window_ranges  the policy: conditioning frames (sink) + the frames within `window` of the block's own + the prompt
     ranges_to_mask       the table as a boolean [Sq, Skv] mask (tests, records)
 
@@ -14,8 +15,8 @@ Only the policy is an approximation; its visual quality on a trained checkpoint 
 import numpy as np
 import torch
 
-Q_BLOCK = 256      # queries per workgroup of attention128_q64.hip
-KV_ALIGN = 64      # its key tile: a range begins on the dense kernel's tile grid
+Q_BLOCK = 256      # queries per workgroup of attention128_q64.hip and of attention.hip
+KV_ALIGN = 64      # their key tile: a range begins on the dense kernel's tile grid
 MAX_RANGES = 4
 
 
@@ -95,7 +96,7 @@ def full_ranges(Sq, Skv):
     return KvRanges(t, Skv, Sq)
 
 
-def frame_window_ranges(frames, tokens_per_frame, window, sink_frames=1, tail=None, rows=None):
+def frame_window_ranges(frames, tokens_per_frame, window, sink_frames=1, tail=None, rows=None, prefix=0):
     """The frame-window policy as a KvRanges, or None when it is the dense attention (every block sees every key).
 
     The keys are `frames` latent frames of `tokens_per_frame` (hw) tokens, frame by frame, optionally followed by other keys of
@@ -106,10 +107,18 @@ def frame_window_ranges(frames, tokens_per_frame, window, sink_frames=1, tail=No
         the window  [(fa - window) * hw, (fb + window + 1) * hw) clipped to the video,
         the tail,
     begins rounded DOWN to a multiple of 64 (a superset: always safe), touching or overlapping ranges merged.  A block that
-    holds any row >= frames * hw (prompt queries, and the block that straddles the boundary) gets the single full range."""
+    holds any row >= frames * hw (prompt queries, and the block that straddles the boundary) gets the single full range.
+
+    prefix > 0 (CogVideoX: the prompt tokens come FIRST, [text; frame 0; frame 1; ...]): the keys and the queries are `prefix`
+    rows followed by the frames, frame f's keys are [prefix + f * hw, prefix + (f + 1) * hw), every block sees the keys
+    [0, prefix), and a block that holds any row < prefix gets the single full range.  It excludes `tail`."""
     F, hw, W, sink = int(frames), int(tokens_per_frame), int(window), int(sink_frames)
     if F < 1 or hw < 1 or W < 0 or sink < 0:
         raise ValueError("frame_window_ranges: frames=%d tokens_per_frame=%d window=%d sink_frames=%d" % (F, hw, W, sink))
+    if int(prefix):
+        if tail is not None:
+            raise ValueError("frame_window_ranges: prefix and tail exclude each other (the prompt keys lie in front or behind)")
+        return _prefixed_ranges(F, hw, W, sink, int(prefix), rows)
     S = F * hw
     Sq = S if rows is None else int(rows)
     if tail is not None:
@@ -133,33 +142,66 @@ def frame_window_ranges(frames, tokens_per_frame, window, sink_frames=1, tail=No
         want.append((max(fa - W, 0) * hw, min(fb + W + 1, F) * hw))
         if tail is not None:
             want.append((tb, te))
-        want = sorted((b - b % KV_ALIGN, e) for b, e in want)
-        merged = [list(want[0])]
-        for b, e in want[1:]:
-            if b <= merged[-1][1]:
-                merged[-1][1] = max(merged[-1][1], e)
-            else:
-                merged.append([b, e])
-        per_block.append([tuple(m) for m in merged])
+        per_block.append(_merged(want))
+    return _table(per_block, Skv, Sq)
+
+
+def _merged(want):
+    """The wanted (begin, end) runs of one block: begins rounded down to the tile grid, sorted, touching or overlapping ones merged."""
+    want = sorted((b - b % KV_ALIGN, e) for b, e in want)
+    merged = [list(want[0])]
+    for b, e in want[1:]:
+        if b <= merged[-1][1]:
+            merged[-1][1] = max(merged[-1][1], e)
+        else:
+            merged.append([b, e])
+    return [tuple(m) for m in merged]
+
+
+def _table(per_block, Skv, Sq):
+    """The blocks' range lists as a KvRanges; None when every block has the single full range."""
     if all(r == [(0, Skv)] for r in per_block):
         return None
     max_ranges = max(len(r) for r in per_block)
-    t = torch.zeros(q_blocks, max_ranges, 2, dtype=torch.int32)
+    t = torch.zeros(len(per_block), max_ranges, 2, dtype=torch.int32)
     for j, r in enumerate(per_block):
         for i, (b, e) in enumerate(r):
             t[j, i, 0], t[j, i, 1] = b, e
     return KvRanges(t, Skv, Sq)
 
 
-def call_transformer(transformer, dense, **kw):
-    """transformer(**kw), with its frame window switched off for this one forward when `dense` (the samplers' dense early
-    steps, `attn_window_dense_steps`); the attribute is restored whatever the forward does."""
+def _prefixed_ranges(F, hw, W, sink, prefix, rows):
+    """frame_window_ranges for the layout [prefix; frame 0; frame 1; ...]."""
+    if prefix < 0:
+        raise ValueError("frame_window_ranges: prefix=%d" % prefix)
+    Skv = prefix + F * hw
+    Sq = Skv if rows is None else int(rows)
+    if Sq > Skv:
+        raise ValueError("frame_window_ranges: rows=%d beyond the %d prefix and video rows" % (Sq, Skv))
+    q_blocks = (Sq + Q_BLOCK - 1) // Q_BLOCK
+    per_block = []
+    for j in range(q_blocks):
+        r0, r1 = j * Q_BLOCK, min((j + 1) * Q_BLOCK, Sq) - 1
+        if r0 < prefix:
+            per_block.append([(0, Skv)])
+            continue
+        fa, fb = (r0 - prefix) // hw, (r1 - prefix) // hw
+        want = [(0, prefix + min(sink, F) * hw), (prefix + max(fa - W, 0) * hw, prefix + min(fb + W + 1, F) * hw)]
+        per_block.append(_merged(want))
+    return _table(per_block, Skv, Sq)
+
+
+def call_transformer(transformer, dense, *args, forward=None, **kw):
+    """transformer(*args, **kw) -- or forward(*args, **kw), a bound method of it (CogVideoX: forward_assembled) -- with its frame
+    window switched off for this one forward when `dense` (the samplers' dense early steps, `attn_window_dense_steps`); the
+    attribute is restored whatever the forward does."""
+    fn = transformer if forward is None else forward
     if not dense or not getattr(transformer, "attn_window", 0):
-        return transformer(**kw)
+        return fn(*args, **kw)
     saved = transformer.attn_window
     transformer.attn_window = 0
     try:
-        return transformer(**kw)
+        return fn(*args, **kw)
     finally:
         transformer.attn_window = saved
 

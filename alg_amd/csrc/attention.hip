@@ -15,7 +15,7 @@
 // Workgroups are ordered so that one XCD works on one head at a time (K/V of a head = 4.5 MB, re-read by the
 // 70 query blocks of that head out of the XCD's L2).
 //
-// Eight kernels are built from this file:
+// Ten kernels are built from this file:
 //   flash_attn_d64_kernel<SM>               the straight loop (QK^T -> softmax -> PV per tile), SM = one of three softmax forms:
 //       Softmax::EXACT      exact running max; the O / l rescale is skipped (exactly: alpha == 1) when no lane's max grew;
 //                           fp32 row sums of the unrounded probabilities.  ALG_ATTN_VARIANT=1: the reference of the parity tests
@@ -27,9 +27,11 @@
 //                           first tile's max allows it, p = exp2(s) with no per-score fma (softmax_tile_zero); ALG_ATTN_PP=0
 //   flash_attn_d64_kernel<LAZY | PRESCALED, SPLIT>   the same loops over one KV chunk of a split-KV tail unit (plan_tail)
 //   flash_attn_d64_merge_kernel             merges the chunk results of the tail
-//   flash_attn_d64_pipe_kernel<OFF>         PRESCALED with the steady-state loop as one generated asm statement: OFF = false
+//   flash_attn_d64_pipe_kernel<OFF, false>  PRESCALED with the steady-state loop as one generated asm statement: OFF = false
 //                                           (DEFAULT, ALG_ATTN_PP=4) for waves whose offsets are zero, OFF = true (ALG_ATTN_PP=8)
 //                                           for any offset.  (ALG_ATTN_PP=7 is attention64_m16.hip.)
+//   flash_attn_d64_pipe_kernel<OFF, true>   the same two frames over the key ranges of a table, one range after the other
+//                                           (alg_flash_attn_d64_ranges: the opt-in frame window, off by default)
 //
 // Measured and removed (the sources are in the history, the records in profiles/r1_*, profiles/r3_attention_d64_pingpong.txt,
 // profiles/r3_attention_pipe_bench_ab.txt and docs/lab_notebook_r*.md).  MI355X, C2 shape (2 x 48 heads x 17,776 tokens),
@@ -79,6 +81,10 @@ struct AttnP {
   uint64_t* clk;   // clock tap (calibrate.hip: alg_attn_clock_tap) or NULL: {cycles, wall} at start / end of every 64th workgroup
   int clk_slots;
   uint64_t* path;  // path counters (calibrate.hip: alg_attn_path_tap) or NULL: {statement entries, tiles inside, tiles straight}
+  // flash_attn_d64_pipe_kernel<OFF, RANGES = true> only (alg_flash_attn_d64_ranges); the dense instantiations read none of them
+  const int32_t* ranges;   // device table [q_blocks][max_ranges][2] of (begin, end) key indices
+  int max_ranges;
+  int use_statement;       // 0: every tile through the C++ tile body (ALG_ATTN_PP=0: the frame on its own)
 };
 
 struct Frag {
@@ -475,7 +481,19 @@ __global__ __launch_bounds__(256) void flash_attn_d64_merge_kernel(const AttnP p
 //
 // One 256-query unit per 8-wave workgroup, as in flash_attn_d64_kernel.  hipcc grants such a workgroup 128 + 128 registers per
 // lane: the statement lives in v[26:127] (OFF: v[10:127]) and a[0:79] and takes O in AccVGPR operands.
-template <bool OFF>
+//
+// RANGES (alg_flash_attn_d64_ranges, the opt-in frame-window attention of alg_amd/attn_window.py; as in attention128_q64.hip):
+// false = every key of the panel, ONE segment [0, S) known when the kernel starts -- the dense kernel, the segment loop folds away.
+// true = the workgroup's 256 queries attend to the key ranges of their row of p.ranges, one after the other.  A segment
+// [begin, end) is a panel of its own: K and V^T advanced to its first key, the six priming DMAs, tile 0 in C++, the statement
+// under the frame's own entry rule, the tail in C++ -- with O, the running offset and the row sum carried from segment to segment
+// and nothing else.  softmax_tile_zero treats a finite offset on a segment's tile 0 like any later tile (it snaps only while the
+// offset is -inf), and the statements only run iterations whose K(t + 3) is a whole tile of the SEGMENT, so with the frame's
+// clamps no DMA leaves [begin, round_up(end, 64)): inside the V^T pitch attn64_check demands.  Between segments the ring is
+// handed over by s_waitcnt vmcnt(0) + one workgroup barrier; inside a segment the DMA count per iteration stays constant (the
+// counted vmcnt(2) wait relies on it).  Everything a segment adds is wave-uniform and lives in SGPRs: nothing new is live across
+// the statement in vector registers (LaneCtx below).
+template <bool OFF, bool RANGES>
 __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const AttnP p) {
   __shared__ __attribute__((aligned(16))) char smem[8 * ATT_TILE];
   char* const k_ring = smem;
@@ -493,12 +511,15 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
     if (bh >= nbh) return;
   }
   const int b = bh / p.heads, h = bh - b * p.heads;
-  const int S = p.S;
+  const int Sq = p.S;   // the panel's rows: what the query clamp and the store mean by S
   const bf16_t* Q = p.q + (int64_t)b * p.q_bs + h * 64;
+  // the segment in hand: its first key's K row / V^T column, its length, and what follows from the length.  Everything below
+  // that says K, VT, S, T or ragged means the SEGMENT's (RANGES = false: the panel's, set once)
   const bf16_t* K = p.k + (int64_t)b * p.q_bs + h * 64;
   const bf16_t* VT = p.vt + (int64_t)b * p.vt_bs + (int64_t)h * 64 * p.vt_rs;
-  const int T = (S + KVB - 1) / KVB;
-  const bool ragged = (S & (KVB - 1)) != 0;
+  int S = p.S;
+  int T = (S + KVB - 1) / KVB;
+  bool ragged = (S & (KVB - 1)) != 0;
   // clock tap (bench.py: the shader clock THIS kernel ran at): scalar reads of two counters, wave 0 of every 64th workgroup
   const bool tap = p.clk != nullptr && (blockIdx.x & 63) == 0 && (int)(blockIdx.x >> 6) < p.clk_slots && wave == 0;
   uint64_t tap_c0 = 0, tap_r0 = 0;
@@ -549,7 +570,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
   // iterations [t, t_end) in the straight form: protocol (unless the first one's is already done), QK(t) -> softmax -> PV(t)
   auto straight = [&](const LaneCtx& c, int t, int t_end, bool top_done) {
     bf16x8 qf[4];
-    const bf16_t* qp = Q + (int64_t)min(c.q_row, S - 1) * p.q_rs + c.h2 * 8;
+    const bf16_t* qp = Q + (int64_t)min(c.q_row, Sq - 1) * p.q_rs + c.h2 * 8;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(qp + ks * 16);
     for (; t < t_end; ++t) {
@@ -569,6 +590,33 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
     }
   };
 
+  int n_ent = 0, n_in = 0;   // path counters: statement entries, tiles run inside the statement
+  int n_tiles = 0;           // ... and the tiles of the segments run
+  bool visited = !RANGES;    // a segment has run: the ring holds its tiles and its clamped prefetches may still be in flight
+  LaneCtx c;                 // the context of the last C++ loop, which the finish shares
+  // (a do-while: its condition is a constant for RANGES = false, and the dense kernels are compiled as if there were no loop)
+  int seg = 0;
+  do {
+  if constexpr (RANGES) {
+    // defensive read: whatever the table holds, the segment lies inside the panel and starts on the dense kernel's tile grid
+    // (the bit-2/3 column permutation and the 16-byte alignment of the V^T DMA hold for begin % 64 == 0 only)
+    const int32_t* r = p.ranges + ((int64_t)qb * p.max_ranges + seg) * 2;
+    const int begin = __builtin_amdgcn_readfirstlane(min(max(r[0], 0), Sq)) & ~(KVB - 1);
+    const int end = __builtin_amdgcn_readfirstlane(min(max(r[1], 0), Sq));
+    if (end <= begin) continue;
+    if (visited) {
+      // hand-over of the ring: this wave's DMAs of the previous segment have landed, and no wave still reads its last tiles
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
+    visited = true;
+    K = p.k + (int64_t)b * p.q_bs + h * 64 + (int64_t)begin * p.q_rs;
+    VT = p.vt + (int64_t)b * p.vt_bs + (int64_t)h * 64 * p.vt_rs + begin;
+    S = end - begin;
+    T = (S + KVB - 1) / KVB;
+    ragged = (S & (KVB - 1)) != 0;
+  }
+  n_tiles += T;
   // the statement only runs iterations t whose DMA target K(t + 3) is a whole tile (its sources are not clamped) and whose
   // tile t + 1 needs no mask
   const int tend = ragged ? T - 4 : T - 3;
@@ -583,7 +631,6 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
   };
   int t = OFF ? 0 : 1;
   bool top_done = false;
-  int n_ent = 0, n_in = 0;   // path counters: statement entries, tiles run inside the statement
   {
     const LaneCtx c = make_ctx(fresh_lane());
     stage_k(c, 0);
@@ -614,7 +661,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
       const int lk2 = kl + c.f.row_off + (((4 + c.h2) ^ c.f.sw) * 16), lk3 = kl + c.f.row_off + (((6 + c.h2) ^ c.f.sw) * 16);
       int kvo0 = (int)(((int64_t)((t + 3) * KVB + c.srow) * p.q_rs + c.sslot * 8) * 2);
       int vvo0 = (int)(((int64_t)c.srow * p.vt_rs + c.sslot * 8 + (t + 2) * KVB) * 2);
-      const int qvo = (int)(((int64_t)min(c.q_row, S - 1) * p.q_rs + c.h2 * 8) * 2);
+      const int qvo = (int)(((int64_t)min(c.q_row, Sq - 1) * p.q_rs + c.h2 * 8) * 2);
       const uint64_t kb = uniform64(K), vb = uniform64(VT), qbs = uniform64(Q);
       const int kstep = sreg((int)(KVB * p.q_rs * 2)), tend_s = sreg(tend);
       const int wk = sreg((int)kl + wave * 1024), wv = sreg((int)vl + wave * 1024);
@@ -636,7 +683,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
       t = ts;
       top_done = code != 0;   // 1: iteration t's protocol is done, softmax(t) is not: tile t is redone at the top of the loop
     }
-  } else if (1 + 4 <= tend && __all(m_run == 0.0f)) {
+  } else if ((!RANGES || p.use_statement) && 1 + 4 <= tend && __all(m_run == 0.0f)) {
     const LaneCtx c = make_ctx(fresh_lane());
     const uint32_t kl = (uint32_t)(uintptr_t)(lptr_t)k_ring, vl = (uint32_t)(uintptr_t)(lptr_t)v_ring;
     const int fl0 = c.f.row_off + (((0 + c.h2) ^ c.f.sw) * 16), fl1 = c.f.row_off + (((2 + c.h2) ^ c.f.sw) * 16);
@@ -645,7 +692,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
     const int lv0 = vl + fl0, lv1 = vl + fl1, lv2 = vl + fl2, lv3 = vl + fl3;
     int kvo0 = (int)(((int64_t)((t + 3) * KVB + c.srow) * p.q_rs + c.sslot * 8) * 2);
     int vvo0 = (int)(((int64_t)c.srow * p.vt_rs + c.sslot * 8 + (t + 2) * KVB) * 2);
-    const int qvo = (int)(((int64_t)min(c.q_row, S - 1) * p.q_rs + c.h2 * 8) * 2);
+    const int qvo = (int)(((int64_t)min(c.q_row, Sq - 1) * p.q_rs + c.h2 * 8) * 2);
     const uint64_t kb = uniform64(K), vb = uniform64(VT), qbs = uniform64(Q);
     const int kstep = sreg((int)(KVB * p.q_rs * 2)), tend_s = sreg(tend);
     const int wk = sreg((int)kl + wave * 1024), wv = sreg((int)vl + wave * 1024);
@@ -662,16 +709,20 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
                  : "memory", "vcc", "scc", ALG_ATTN_PIPE8_CLOBBERS);
 #pragma unroll
     for (int i = 0; i < 32; ++i) oa[i >> 4][i & 15] = o[i];
-    n_ent = 1, n_in = ts - t;
+    n_ent += 1, n_in += ts - t;
     t = ts;
     top_done = code != 0;   // 1: iteration t's protocol is done, softmax(t) is not: tile t is redone below
   }
-  LaneCtx c = make_ctx(fresh_lane());
-  if constexpr (!OFF) straight(c, t, T, top_done);   // the tiles behind the statement (or all of them but tile 0)
+  if constexpr (!OFF) {
+    c = make_ctx(fresh_lane());
+    straight(c, t, T, top_done);   // the tiles behind the statement (or all of them but tile 0)
+  }
+  } while (RANGES && ++seg < p.max_ranges);   // segments
+  if constexpr (OFF || RANGES) c = make_ctx(fresh_lane());
 
   const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
-  const float inv = 1.0f / l_tot;
-  if (c.q_row < S) {
+  const float inv = !RANGES || visited ? 1.0f / l_tot : 0.0f;   // (a block the table leaves without a key writes zeros)
+  if (c.q_row < Sq) {
     bf16_t* op = p.o + (int64_t)b * p.o_bs + (int64_t)c.q_row * p.o_rs + h * 64;
 #pragma unroll
     for (int dt = 0; dt < 2; ++dt)
@@ -693,7 +744,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
       unsigned long long* pc = (unsigned long long*)p.path;
       atomicAdd(pc + 0, (unsigned long long)n_ent);
       atomicAdd(pc + 1, (unsigned long long)n_in);
-      atomicAdd(pc + 2, (unsigned long long)(T - n_in));
+      atomicAdd(pc + 2, (unsigned long long)(n_tiles - n_in));
     }
   }
 }
@@ -783,8 +834,8 @@ static int attn64_launch(Softmax form, unsigned blocks, const AttnP& p, hipStrea
   if (pp >= 3 && ((int64_t)(p.S + 4 * KVB) * p.q_rs * 2 >= (1ll << 31) || (int64_t)65 * p.vt_rs * 2 >= (1ll << 31))) pp = 0;
   switch (pp) {
     case 4:
-    case 7: hipLaunchKernelGGL(flash_attn_d64_pipe_kernel<false>, dim3(blocks), dim3(ATT_THREADS), 0, s, p); break;
-    case 8: hipLaunchKernelGGL(flash_attn_d64_pipe_kernel<true>, dim3(blocks), dim3(ATT_THREADS), 0, s, p); break;
+    case 7: hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<false, false>), dim3(blocks), dim3(ATT_THREADS), 0, s, p); break;
+    case 8: hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<true, false>), dim3(blocks), dim3(ATT_THREADS), 0, s, p); break;
     default: attn64_launch_straight(form, false, blocks, p, s); break;
   }
   return ALG_OK;
@@ -805,6 +856,18 @@ static void attn64_launch_straight(Softmax form, bool split, unsigned blocks, co
       hipLaunchKernelGGL(flash_attn_d64_kernel<Softmax::EXACT>, g, blk, 0, s, p);
       break;
   }
+}
+
+// The ranged launch (alg_flash_attn_d64_ranges): pre-scaled Q, one launch over whole units in the dense grid order.  ALG_ATTN_PP
+// picks the frame: 4 and 7 the zero-offset statement, 8 the any-offset one; 0, or operands beyond the statements' 31-bit byte
+// offsets (the rule of attn64_launch), the zero-offset frame with the statement switched off -- every tile through the C++ tile
+// body.  (Named behind the seven dense instantiations: the code object keeps their order.)
+static void attn64_launch_ranges(unsigned blocks, AttnP& p, hipStream_t s) {
+  int pp = opt(OPT_ATTN_PP);
+  if (pp >= 3 && ((int64_t)(p.S + 4 * KVB) * p.q_rs * 2 >= (1ll << 31) || (int64_t)65 * p.vt_rs * 2 >= (1ll << 31))) pp = 0;
+  p.use_statement = pp >= 3;
+  if (pp == 8) hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<true, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
+  else hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<false, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
 }
 
 }  // namespace alg
@@ -844,6 +907,7 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
   p.path = path_tap_for(s);
   p.unit0 = p.tail_units = p.tail_split = p.tail_tiles = 0;
   p.ws_o = p.ws_ml = nullptr;
+  p.ranges = nullptr, p.max_ranges = 0, p.use_statement = 1;
   const int nbh = batch * heads;
   // the split-KV tail runs only in a caller-provided workspace (alg_flash_attn_d64_workspace_bytes); without one the whole
   // problem is a single launch (same rows up to fp32 summation order in the tail units)
@@ -861,4 +925,44 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
   const int64_t merge = (int64_t)8 * tp.units * QB * 16;
   hipLaunchKernelGGL(flash_attn_d64_merge_kernel, dim3((unsigned)((merge + 255) / 256)), dim3(256), 0, s, p);
   return check_launch("alg_flash_attn_d64");
+}
+
+// Each block of 256 queries attends to its row of a table of key ranges (include/alg_hip.h): pre-scaled Q only (the
+// ALG_ATTN_Q_PRESCALED form of alg_flash_attn_d64_ex), ONE launch -- no split-KV tail, no workspace.
+extern "C" int alg_flash_attn_d64_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                                         int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                                         int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
+                                         void* stream) {
+  const int rc = attn64_check(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride);
+  if (rc != ALG_OK) {
+    set_error("alg_flash_attn_d64_ranges: the operands fail the checks of alg_flash_attn_d64 (batch=%d heads=%d S=%d; q/k/vt "
+              "16-byte aligned rows, o 8-byte aligned, vt row stride %lld covering S rounded up to %d)",
+              batch, heads, S, (long long)vt_rstride, KVB);
+    return rc;
+  }
+  if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > 4) {
+    set_error("alg_flash_attn_d64_ranges: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)",
+              (const void*)kv_ranges, max_ranges);
+    return ALG_EINVAL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  AttnP p;
+  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (bf16_t*)o;
+  p.batch = batch; p.heads = heads; p.S = S; p.q_blocks = (S + QB - 1) / QB;
+  p.q_bs = q_bstride; p.q_rs = q_rstride; p.vt_bs = vt_bstride; p.vt_rs = vt_rstride;
+  p.o_bs = o_bstride; p.o_rs = o_rstride;
+  p.scale_log2 = 1.0f;
+  p.prio = 0;
+  p.clk = clock_tap_for(s, &p.clk_slots);
+  p.path = path_tap_for(s);
+  p.unit0 = p.tail_units = p.tail_split = p.tail_tiles = 0;
+  p.ws_o = p.ws_ml = nullptr;
+  p.ranges = kv_ranges, p.max_ranges = max_ranges;
+  const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
+  if (grid > 0x7fffffff) {
+    set_error("alg_flash_attn_d64_ranges: grid too large (batch=%d heads=%d S=%d)", batch, heads, S);
+    return ALG_EINVAL;
+  }
+  attn64_launch_ranges((unsigned)grid, p, s);
+  return check_launch("alg_flash_attn_d64_ranges");
 }

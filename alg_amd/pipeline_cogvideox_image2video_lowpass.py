@@ -21,6 +21,7 @@ they are absent the caller passes ``prompt_embeds`` / ``negative_prompt_embeds``
 """
 from __future__ import annotations
 
+import functools
 import inspect
 import math
 from dataclasses import dataclass
@@ -28,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import _lib, lp_utils, step_cache
+from . import _lib, attn_window, lp_utils, step_cache
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler
 from .transformer_cogvideox import CogVideoXTransformer3DModel
 
@@ -130,13 +131,14 @@ class CogVideoXImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
                         scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False,
-                        step_cache=0.0, **_):
+                        step_cache=0.0, attn_window=0, **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
         `image_latents` and `output_type="latent"`.  `fp8=True` loads the transformer with e4m3 block linears
         (CogVideoXTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.  `step_cache` > 0
-        switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default)."""
+        switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default), `attn_window` > 0
+        its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by default)."""
         import os
 
         from .autoencoder_kl_cogvideox import AutoencoderKLCogVideoX
@@ -149,6 +151,8 @@ class CogVideoXImageToVideoPipeline:
                                                                       device=device, fp8=fp8)
         if step_cache:
             transformer.step_cache = float(step_cache)
+        if attn_window:
+            transformer.attn_window = int(attn_window)
         if vae is None and has("vae"):
             vae = AutoencoderKLCogVideoX.from_pretrained(model_path, device=device)
         if text_encoder is None and has("text_encoder"):
@@ -469,9 +473,11 @@ class CogVideoXImageToVideoPipeline:
         image_latents: Optional[torch.Tensor] = None,
         step_trace: Optional[list] = None,
         cfg_split=None,
+        attn_window_dense_steps: int = 0,
     ) -> Union[CogVideoXPipelineOutput, Tuple]:
         """Keyword-compatible with the reference ``__call__`` (cog:727-774); ``image_latents`` and ``step_trace``
-        are extensions (VAE bypass; per-step (strength, two_pass, n_forward) log for tests)."""
+        are extensions (VAE bypass; per-step (strength, two_pass, n_forward) log for tests), and so is
+        ``attn_window_dense_steps``: the first that many steps run the transformer's opt-in frame window dense."""
         tcfg = self.transformer.config
         if hasattr(callback_on_step_end, "tensor_inputs"):
             callback_on_step_end_tensor_inputs = callback_on_step_end.tensor_inputs
@@ -604,17 +610,19 @@ class CogVideoXImageToVideoPipeline:
             conds = [g[b:b + 1] for g in cond_groups for b in range(B)]
             lat_in = latents if B == 1 else torch.cat([latents] * n_pass, dim=0)
             ts = ts_dev[i:i + 1].expand(n_pass * B)
+            # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
+            dit = functools.partial(attn_window.call_transformer, self.transformer, i < attn_window_dense_steps,
+                                    forward=self.transformer.forward_assembled)
             if cfg_split is not None and n_pass > 1:
                 # alg_amd.parallel.CFGPairSplit: this rank evaluates its share of the CFG passes, one all-gather merges
                 # the predictions; combine + step below run identically on both ranks of the pair
                 rows = [p_ * B + b for p_ in cfg_split.my_passes(n_pass) for b in range(B)]
                 lat_l = latents if B == 1 else torch.cat([latents] * (len(rows) // B), dim=0)
-                local = self.transformer.forward_assembled(lat_l, [conds[r] for r in rows], embeds[rows].contiguous(),
-                                                           ts[:len(rows)], image_rotary_emb, ofs=ofs_emb)
+                local = dit(lat_l, [conds[r] for r in rows], embeds[rows].contiguous(), ts[:len(rows)], image_rotary_emb, ofs=ofs_emb)
                 noise_pred = cfg_split.merge(local, n_pass, B)
             else:
                 cache_kw = dict(cache_keys=step_cache.pass_keys(n_pass, B), cache_force=i == len(timesteps) - 1) if use_cache else {}
-                noise_pred = self.transformer.forward_assembled(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb, **cache_kw)
+                noise_pred = dit(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb, **cache_kw)
             gs = guidance_scale
             if do_cfg and not use_low_pass_guidance and use_dynamic_cfg:  # cog:1105-1108
                 gs = 1 + guidance_scale * (

@@ -36,6 +36,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .attn_window import frame_window_ranges
 from .step_cache import StepCacheHost
 
 
@@ -132,6 +133,13 @@ class CogVideoXTransformer3DModel(StepCacheHost):
         # residual they produced on the last computed forward.  0.0: every forward is the plain one, launch for launch.
         self.step_cache = 0.0
         self.step_cache_max_consecutive = 0   # at most this many skipped forwards in a row (0: no cap)
+        # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): in the joint attention of every block a
+        # block of latent queries attends to the prompt keys, to the conditioning frames (attn_sink_frames) and to the latent frames
+        # within attn_window of its own; prompt queries see everything.  ONE alg_flash_attn_d64_ranges launch for the whole batch.
+        # 0: today's launches, nothing allocated
+        self.attn_window = 0
+        self.attn_sink_frames = 1
+        self._attn_ranges = {}    # (frames, hw, T, window, sink) -> KvRanges, or None where the window covers the whole video
         self._sincos = {}
         dev = self.device
         w = weights
@@ -345,7 +353,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
                 self._quantize_layer(L, drop_bf16=False)
         return ws["q8"], ws["q8s"]
 
-    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale):
+    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr=None):
         """One transformer block with e4m3 operands on its five linears: the launch order of the bf16 block, each GEMM input
         quantised per token into q8 / q8s first (by the LayerNorm itself where a norm produces it)."""
         cfg, G, TM = self.config, _lib.gemm, self._timed
@@ -385,8 +393,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
            bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
         TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
            cfg.qk_norm_eps, q_scale=q_scale)
-        TM("attn", _lib.flash_attn_d64, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale,
-           k_off=D, q_prescaled=prescale)
+        self._attention(ws, kvr, N, S, scale, prescale)
         quant(att, D)
         lin("gemm_out", L["wo8"], x, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
@@ -395,6 +402,35 @@ class CogVideoXTransformer3DModel(StepCacheHost):
         quant(h, F4)
         lin("gemm_ff2", L["wf28"], x, D, F4, D, bias=L["bf2"], R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
+
+    def _window_ranges(self, frames, hw, T):
+        """The frame-window table of this sequence shape -- T prompt tokens, then `frames` latent frames of hw tokens -- device-
+        resident, built once per (frames, hw, T, window, sink): before any capture that replays it.  None: the window covers the
+        video, the launches are the dense ones."""
+        window, sink = int(self.attn_window), int(self.attn_sink_frames)
+        if window < 0 or sink < 0:
+            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
+        if not self.attn_prescale:
+            raise ValueError("attn_window needs attn_prescale = True: alg_flash_attn_d64_ranges has one softmax form (pre-scaled Q)")
+        key = (frames, hw, T, window, sink)
+        if key not in self._attn_ranges:
+            r = frame_window_ranges(frames, hw, window, sink_frames=sink, prefix=T)
+            if r is not None:
+                r.on(self.device)
+            self._attn_ranges[key] = r
+        return self._attn_ranges[key]
+
+    def _attention(self, ws, kvr, N, S, scale, prescale):
+        """softmax(q k^T * scale) v of the joint sequence from qk / vt into att: the dense launch, or (kvr: the frame-window table)
+        the ranged one."""
+        cfg = self.config
+        D, Hn = cfg.inner_dim, cfg.num_attention_heads
+        qk, vt, att, S_pad = ws["qk"], ws["vt"], ws["att"], ws["S_pad"]
+        if kvr is not None:
+            return self._timed("attn", _lib.flash_attn_d64_ranges, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad,
+                               S * D, D, kvr, k_off=D)
+        return self._timed("attn", _lib.flash_attn_d64, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D,
+                           scale, k_off=D, q_prescaled=prescale)
 
     def _rope(self, image_rotary_emb):
         if image_rotary_emb is None:
@@ -500,6 +536,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
         F4 = cfg.ff_inner_mult * D
         packed = self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         wo_k, wf1_k, wf2_k = ("pwo", "pwf1", "pwf2") if packed else ("wo", "wf1", "wf2")
+        kvr = self._window_ranges(Fr // p_t, (Hh // p) * (Ww // p), T) if self.attn_window else None   # None: the dense launch
         sc = self._step_cache_begin(x, cache_keys, cache_force, T, P)   # None: off, nothing below differs from the plain forward
         for li, L in enumerate(self.layers):
             if li == 1 and sc is not None and TM("step_cache", sc.after_block0, x):
@@ -507,7 +544,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
             m1 = li * 12 * D          # norm1: shift @+0, scale @+2D, gate @+4D (each [2][D])
             m2 = m1 + 6 * D           # norm2
             if fp8:
-                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale)
+                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr)
                 continue
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
                T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
@@ -526,8 +563,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
                     TM("gemm_vt", G, *vt_call[0], **vt_call[1])
                 TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
                                    cfg.qk_norm_eps, q_scale=q_scale)
-            TM("attn", _lib.flash_attn_d64, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale,
-                                k_off=D, q_prescaled=prescale)
+            self._attention(ws, kvr, N, S, scale, prescale)
             TM("gemm_out", G, att, L[wo_k], x, S, D, D, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
               strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * D, strideC=S * D, strideR=S * D)
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm2_w"], L["norm2_b"], mod, mod, self.mod_cols, N, S, D,

@@ -262,6 +262,27 @@ int alg_flash_attn_d64_ex(const void* q, const void* k, const void* vt, void* o,
                           int64_t workspace_bytes, void* stream);
 int64_t alg_flash_attn_d64_workspace_bytes(int batch, int heads, int S, int flags);
 
+/* alg_flash_attn_d64_ex(ALG_ATTN_Q_PRESCALED) (the same layouts, strides and alignment; q carries scale * log2(e)) in which each
+ * block of 256 queries attends to a short list of key ranges instead of to all keys: the primitive under the opt-in frame window
+ * of the CogVideoX self-attention (alg_amd/attn_window.py).  One launch in the dense grid order: no split-KV tail, no workspace.
+ *   kv_ranges : DEVICE table int32 [q_blocks][max_ranges][2] of (begin, end) key indices, q_blocks = ceil(S / 256); one table
+ *               serves every batch item and head of the launch.  max_ranges is 1..4.
+ *   A table is valid when in each block the used entries come first, sorted and disjoint, begin % 64 == 0, begin < end <= S,
+ *   unused trailing entries are (0, 0), and every block has at least one key.
+ * o[q] = softmax of the log2-unit scores restricted to the union of the ranges of q's block, times v, with the numerics of the
+ * dense entry's single launch: a range [begin, end) is computed exactly as that launch computes a panel of end - begin keys whose
+ * k / vt start at key `begin`, with the running offset, the row sum and the fp32 accumulator carried from range to range.  vt's
+ * padding rule holds per range: the columns up to the next multiple of 64 behind `end` are read and multiplied by p = 0 (finite
+ * values).
+ * The kernel reads the table defensively -- begin / end clamped into [0, S], begin rounded down to a multiple of 64, empty
+ * entries skipped, a block left without a key writes zeros -- so no table content makes it read outside the panels; a null or
+ * misaligned table and max_ranges outside 1..4 are ALG_EINVAL before any launch.  ALG_ATTN_PP picks the kernel as it does for
+ * the dense entry: 4 and 7 the zero-offset statement, 8 the any-offset one, 0 (or operands beyond the statements' 31-bit byte
+ * offsets) the same frame with the statement switched off. */
+int alg_flash_attn_d64_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                              int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                              int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, void* stream);
+
 /* wan:910-917 (WanTransformer3DModel self- and cross-attention, head_dim 128; diffusers WanAttnProcessor SDPA)
  * Same contract as alg_flash_attn_d64 with head_dim 128 and separate query / key lengths:
  *   q : element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d,  s < Sq

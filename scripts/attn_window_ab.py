@@ -2,6 +2,7 @@
 run of this).  One job, arms alternated, package power and shader clock sampled per arm (bench.SmiSampler).
 
     python scripts/attn_window_ab.py --out profiles/attn_window_ab.json [--only kernel|steps|accuracy]
+    python scripts/attn_window_ab.py --family d64 --out profiles/attn_window_d64_ab.json [--only kernel|steps|accuracy]
 
   kernel    alg_flash_attn_d128 against alg_flash_attn_d128_ranges at the three launch shapes (C3 32,760 x 40 heads, C5 75,600 x 40,
             C4 119,056 queries x 118,848 keys x 24 heads): the dense entry (first and last arm: their distance is the job's spread),
@@ -13,6 +14,11 @@ run of this).  One job, arms alternated, package power and shader clock sampled 
   accuracy  4-step ALG samplers on the trained-like Wan and HunyuanVideo models of tests/helpers/trained_like_cases.py at 9 latent
             frames: relative L2 of the final latents with attn_window = 1, 2, 4 against the dense run, next
             to the dense run's distance to the fp32 loop oracle (the bf16-to-fp32 floor of that run)
+
+--family d64 is CogVideoX (profiles/attn_window_d64_ab.json): the kernel arms at the C2 launch shape (2 x 48 heads x 17,776,
+d = 64) -- alg_flash_attn_d64_ex in its default form (pre-scaled Q, split-KV tail on) against alg_flash_attn_d64_ranges (one launch,
+no tail) with the full-range table and the windows 1 / 2 / 4 --, the C2 steps with attn_window = 2 between two dense runs, and the
+accuracy arms on the trained-like CogVideoX model at the medium grid (8 heads x 64, 4 blocks, 9 latent frames of 384 tokens).
 
 Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
 import argparse
@@ -110,9 +116,96 @@ def kernel_arms(name, iters):
     return out
 
 
-def step_arms(workload):
-    F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
-    w_half = window_for(F, hw, valid, rows, 0.5)[0]
+# CogVideoX C2: 226 prompt tokens in front of 13 latent frames of 1,350 tokens, 2 samples x 48 heads
+C2_F, C2_HW, C2_T, C2_HEADS, C2_N = 13, 1350, 226, 48, 2
+
+
+def kernel_arms_d64(iters):
+    S, D, N = C2_T + C2_F * C2_HW, C2_HEADS * 64, C2_N
+    pad = (S + 127) // 128 * 128
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(N, S, 2 * D, generator=g, device=DEV, dtype=BF)          # the model's layout: Q | K rows, V^T apart
+    qk[:, :, :D] *= 0.125 * 1.4426950408889634                                # Q pre-scaled: the scores are in log2 units
+    vt = torch.randn(N, D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(N, S, D, dtype=BF, device=DEV)
+    args = (qk, qk, vt, o, N, C2_HEADS, S, S * 2 * D, 2 * D, D * pad, pad, S * D, D)
+    dense = lambda: _lib.flash_attn_d64(*args, 0.125, k_off=D, q_prescaled=True)
+    ranged = lambda t: (lambda: _lib.flash_attn_d64_ranges(*args, t, k_off=D))
+    arms = [("dense_first", dense, 1.0, None), ("full_range", ranged(full_ranges(S, S)), 1.0, None)]
+    for w in (1, 2, 4):
+        t = frame_window_ranges(C2_F, C2_HW, w, prefix=C2_T)
+        t.device_table
+        arms.append(("attn_window_%d" % w, ranged(t), t.coverage, w))
+    arms.append(("dense_last", dense, 1.0, None))
+    out = {"samples": N, "tokens": S, "heads": C2_HEADS, "frames": C2_F, "tokens_per_frame": C2_HW, "prompt_tokens": C2_T,
+           "dense_form": "alg_flash_attn_d64_ex, ALG_ATTN_Q_PRESCALED, split-KV tail on (workspace %d bytes)"
+                         % int(_lib.load_library().alg_flash_attn_d64_workspace_bytes(N, C2_HEADS, S, 1)), "arms": {}}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        dense()
+        torch.cuda.synchronize()
+    for label, fn, cov, w in arms:
+        r = timed(fn, iters)
+        r.update(coverage=cov, attn_window=w)
+        out["arms"][label] = r
+    a, b = out["arms"]["dense_first"]["median_ms"], out["arms"]["dense_last"]["median_ms"]
+    d = out["dense_ms_mean"] = (a + b) / 2
+    out["dense_spread_ms"] = abs(a - b)
+    for r in out["arms"].values():
+        r["ms_over_dense"] = r["median_ms"] / d
+        r["ms_over_dense_minus_coverage"] = r["ms_over_dense"] - r["coverage"]
+    out["full_range_minus_dense_ms"] = out["arms"]["full_range"]["median_ms"] - d
+    out["full_range_over_dense"] = out["arms"]["full_range"]["median_ms"] / d    # (no split-KV tail: 1.5-5 % expected, attention.hip)
+    out["full_range_within_dense_spread"] = out["full_range_minus_dense_ms"] <= out["dense_spread_ms"]
+    del qk, vt, o
+    torch.cuda.empty_cache()
+    return out
+
+
+def accuracy_cog(frames=9, steps=4, layers=4):
+    """A 4-step ALG sampler on the trained-like CogVideoX model at the medium grid (tests/helpers/trained_like_cases.py: 8 heads x
+    64) with `layers` blocks, `frames` latent frames of 384 tokens behind 10 prompt tokens."""
+    from alg_amd import CogVideoXDDIMScheduler, CogVideoXImageToVideoPipeline, CogVideoXTransformer3DModel, CogVideoXTransformerConfig
+    from helpers.trained_like import trained_like
+    from helpers.trained_like_cases import COG_SMALL
+    from oracle import ddim_oracle, dit_oracle, loop_oracle
+    H, W, C = 32, 48, 8
+    kw = dict(COG_SMALL, sample_width=W, sample_height=H, sample_frames=4 * (frames - 1) + 1, num_layers=layers)
+    ocfg = dit_oracle.DiTConfig(**kw)
+    wbf = {k: v.to(BF) for k, v in trained_like(dit_oracle.init_weights(ocfg, seed=3, std=0.05, randomize_affine=True)).items()}
+    model = CogVideoXTransformer3DModel(CogVideoXTransformerConfig(**kw), wbf, device=DEV)
+    pipe = CogVideoXImageToVideoPipeline(transformer=model, scheduler=CogVideoXDDIMScheduler()).to(DEV)
+    g = torch.Generator().manual_seed(8)
+    lat = torch.randn(1, frames, C, H, W, generator=g).to(BF)
+    first = (torch.randn(1, 1, C, H, W, generator=g) * 0.7).to(BF)
+    pe, ne = torch.randn(1, 10, 128, generator=g).to(BF), torch.randn(1, 10, 128, generator=g).to(BF)
+    alg = dict(num_inference_steps=steps, guidance_scale=6.0, use_low_pass_guidance=True, lp_filter_type="down_up",
+               lp_resize_factor=0.25, lp_strength_schedule_type="interval", schedule_interval_start_time=0.0,
+               schedule_interval_end_time=0.3)
+
+    def call():
+        return pipe(image=None, image_latents=first, latents=lat, prompt_embeds=pe, negative_prompt_embeds=ne, height=H * 8,
+                    width=W * 8, num_frames=4 * (frames - 1) + 1, output_type="latent", lp_filter_in_latent=True,
+                    **alg).frames.float().cpu()
+
+    dense = call()
+    w32 = {k: v.float() for k, v in wbf.items()}
+    cond = torch.zeros(1, frames, C, H, W)
+    cond[:, :1] = first.float()
+    rope = dit_oracle.rope_tables(ocfg, H * 8, W * 8, frames)
+    want = loop_oracle.alg_denoise_loop(lambda x, e, ts, r: dit_oracle.dit_forward(ocfg, w32, x, e, ts, r), ddim_oracle.DDIMOracle(),
+                                        lat.float(), cond, pe.float(), ne.float(), image_rotary_emb=rope, **alg)
+    return {"model": "trained-like CogVideoX, medium grid (8 heads x 64, %d blocks), 10 prompt tokens + %d latent frames x 384 tokens"
+                     % (layers, frames), "steps": steps, "bf16_to_fp32_floor_rel_l2": _rel(dense, want.float()),
+            "arms": _window_arms(model, call, frames, dense)}
+
+
+def step_arms(workload, window=None):
+    if workload == "c2":
+        w_half = window        # (CogVideoX: the window is given; 2 has a coverage of 0.44 at C2)
+    else:
+        F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
+        w_half = window_for(F, hw, valid, rows, 0.5)[0]
     args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
     wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
     wl.build()
@@ -247,6 +340,7 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--family", choices=["d128", "d64"], default="d128", help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2)")
     a = ap.parse_args()
     parts = a.only or ["kernel", "accuracy", "steps"]
     res = {}
@@ -260,6 +354,18 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
 
+    if a.family == "d64":
+        if "kernel" in parts:
+            res["kernel"] = {"c2_2x48x17776": kernel_arms_d64(a.iters)}
+            save()
+        if "accuracy" in parts:
+            res["accuracy"] = {"cogvideox": accuracy_cog()}
+            save()
+        if "steps" in parts:
+            res["steps"] = {"c2": step_arms("c2", window=2)}
+            save()
+        print(json.dumps(res))
+        return
     if "kernel" in parts:
         res["kernel"] = {}
         for name in SHAPES:
