@@ -34,7 +34,7 @@ EXPORTS = (
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap", "alg_attn_path_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
-    "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges",
+    "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -124,6 +124,9 @@ def load_library():
         c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d128.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p]
     lib.alg_flash_attn_d128_ranges.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p, c_int, c_void_p]
+    lib.alg_flash_attn_d128_ranges_heads.argtypes = ([c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 +
+                                                     [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p])
+    lib.alg_attn_lse_recall.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p]
     lib.alg_flash_attn_d128_ex.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
     lib.alg_flash_attn_d128_dual.argtypes = ([c_void_p] * 3 + [c_int] + [c_int64] * 4 + [c_void_p] * 2 + [c_int] + [c_int64] * 4 +
                                              [c_void_p] + [c_int] * 3 + [c_int64] * 4 + [c_float, c_void_p])
@@ -565,6 +568,55 @@ def flash_attn_d128_ranges(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs,
                                           k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale), _ptr(table), kv_ranges.max_ranges,
                                           _stream()), "alg_flash_attn_d128_ranges")
     return o
+
+
+def flash_attn_d128_ranges_heads(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, scale, kv_ranges,
+                                 lse=None, q_off=0, k_off=0, vt_off=0, o_off=0, lse_off=0):
+    """flash_attn_d128_ranges with a table per head (kv_ranges: an attn_window.KvRangesHeads built for these heads) or one for all
+    (a KvRanges), and, when `lse` is given (fp32, contiguous, batch * heads * Sq elements from lse_off), the log2-domain
+    log-sum-exp of the scaled scores over the keys each query visited (include/alg_hip.h: alg_flash_attn_d128_ranges_heads)."""
+    from .attn_window import KvRanges, KvRangesHeads
+    if not isinstance(kv_ranges, (KvRanges, KvRangesHeads)):
+        raise AlgHipError("flash_attn_d128_ranges_heads takes an attn_window.KvRanges or KvRangesHeads, got %s"
+                          % type(kv_ranges).__name__)
+    if kv_ranges.Sq != Sq or kv_ranges.Skv != Skv:
+        raise AlgHipError("flash_attn_d128_ranges_heads: the table was built for Sq=%d Skv=%d, the call has Sq=%d Skv=%d"
+                          % (kv_ranges.Sq, kv_ranges.Skv, Sq, Skv))
+    table_heads = kv_ranges.heads if isinstance(kv_ranges, KvRangesHeads) else 1
+    if table_heads not in (1, heads):
+        raise AlgHipError("flash_attn_d128_ranges_heads: the table was built for %d heads, the call has %d" % (table_heads, heads))
+    lib = load_library()
+    for t in (q, k, vt, o):
+        _dev(t, "attention operand")
+    lse_p = c_void_p(0)
+    if lse is not None:
+        _dev(lse, "lse")
+        if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < lse_off + batch * heads * Sq:
+            raise AlgHipError("flash_attn_d128_ranges_heads: lse must be contiguous fp32 with room for [batch][heads][Sq]")
+        lse_p = c_void_p(lse.data_ptr() + 4 * lse_off)
+    table = kv_ranges.on(q.device)
+    at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
+    _check(lib.alg_flash_attn_d128_ranges_heads(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv,
+                                                q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale), _ptr(table),
+                                                kv_ranges.max_ranges, table_heads, lse_p, _stream()),
+           "alg_flash_attn_d128_ranges_heads")
+    return o
+
+
+def attn_lse_recall(lse_part, lse_full, out, panels, Sq, row0=0, rows=None, part_off=0, full_off=0, out_off=0):
+    """out[p] (float64, device) = mean over the rows [row0, row0 + rows) of exp2(lse_part[p] - lse_full[p]) for the `panels` panels
+    of Sq rows each: the softmax mass the queries keep on the keys lse_part was taken over (include/alg_hip.h:
+    alg_attn_lse_recall).  Offsets in elements."""
+    rows = Sq - row0 if rows is None else rows
+    for t, dt, n, off, name in ((lse_part, torch.float32, panels * Sq, part_off, "lse_part"),
+                                (lse_full, torch.float32, panels * Sq, full_off, "lse_full"), (out, torch.float64, panels, out_off, "out")):
+        _dev(t, name)
+        if t.dtype != dt or not t.is_contiguous() or t.numel() < off + n:
+            raise AlgHipError("attn_lse_recall: %s must be contiguous %s with at least %d elements behind offset %d" % (name, dt, n, off))
+    _check(load_library().alg_attn_lse_recall(c_void_p(lse_part.data_ptr() + 4 * part_off), c_void_p(lse_full.data_ptr() + 4 * full_off),
+                                              c_void_p(out.data_ptr() + 8 * out_off), panels, Sq, row0, rows, _stream()),
+           "alg_attn_lse_recall")
+    return out
 
 
 def flash_attn_d128_fp8(q8, q_scale, k8, k_scale, vt8, vt_scale, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs,

@@ -10,8 +10,20 @@ f + W" is ONE contiguous run of keys, and the frame window is a host-side policy
     frame_window_ranges  the policy: conditioning frames (sink) + the frames within `window` of the block's own + the prompt
     ranges_to_mask       the table as a boolean [Sq, Skv] mask (tests, records)
 
+Per-head windows chosen by recall (head_dim 128: alg_flash_attn_d128_ranges_heads, alg_attn_lse_recall).  A frame window is nearly
+exact for a head whose softmax mass lies in neighbouring frames and wrong for one that spreads it over the video, so with
+`attn_window_recall` > 0 the models measure, on one forward of each video, the RECALL of every (layer, head) -- the fraction of
+softmax mass its latent queries keep inside the window -- and only the heads that reach the threshold keep the window:
+
+    KvRangesHeads        one validated KvRanges per head, as ONE device table [heads][q_blocks][max_ranges][2]
+    head_window_ranges   the window's rows for the windowed heads, the one full range for the others
+    decide_heads         recall [samples][heads] -> windowed [heads]: the minimum over the samples reaches the threshold
+
 Only the policy is an approximation; its visual quality on a trained checkpoint is unmeasured (README), so it is off by default.
 """
+import math
+from types import SimpleNamespace
+
 import numpy as np
 import torch
 
@@ -86,6 +98,67 @@ class KvRanges:
     def is_full(self):
         a = self.table
         return bool((a[:, 0, 0] == 0).all() and (a[:, 0, 1] == self.Skv).all())
+
+
+class KvRangesHeads:
+    """A table int32 [heads][q_blocks][max_ranges][2]: head h's slice is a KvRanges table for (Sq, Skv) and is validated as one
+    (ValueError names the head in front of KvRanges' message).  What _lib.flash_attn_d128_ranges_heads takes for table_heads =
+    heads."""
+
+    def __init__(self, table, Skv, Sq):
+        t = torch.as_tensor(table)
+        if t.dtype != torch.int32 or t.dim() != 4 or t.shape[0] < 1 or t.device.type != "cpu":
+            raise ValueError("KvRangesHeads takes a CPU int32 table [heads][q_blocks][max_ranges][2], got %s %s"
+                             % (t.dtype, tuple(t.shape)))
+        per_head = []
+        for h in range(t.shape[0]):
+            try:
+                per_head.append(KvRanges(t[h], Skv, Sq))
+            except ValueError as e:
+                raise ValueError("head %d: %s" % (h, e)) from None
+        self.per_head = tuple(per_head)
+        self.table = t.clone().contiguous()
+        self.heads = int(t.shape[0])
+        self.Skv, self.Sq = per_head[0].Skv, per_head[0].Sq
+        self.q_blocks, self.max_ranges = per_head[0].q_blocks, per_head[0].max_ranges
+        self.coverage = sum(r.coverage for r in per_head) / self.heads
+        self._device = {}
+
+    on = KvRanges.on
+    device_table = KvRanges.device_table
+
+
+def head_window_ranges(base, windowed):
+    """The per-head table of a layer: head h gets `base`'s rows where windowed[h], else the one full range [(0, Skv)] (zero-padded
+    to base.max_ranges).  `base` itself when every head is windowed (the shared-table launch), None when no head is (the dense
+    launch)."""
+    if not isinstance(base, KvRanges):
+        raise ValueError("head_window_ranges takes a KvRanges, got %s" % type(base).__name__)
+    windowed = [bool(w) for w in windowed]
+    if not windowed:
+        raise ValueError("head_window_ranges: no head")
+    if all(windowed):
+        return base
+    if not any(windowed):
+        return None
+    full = torch.zeros_like(base.table)
+    full[:, 0, 1] = base.Skv
+    return KvRangesHeads(torch.stack([base.table if w else full for w in windowed]), base.Skv, base.Sq)
+
+
+def decide_heads(recall, threshold):
+    """recall[sample][head] (Python floats: the softmax mass head h's queries keep inside the window, per sample) -> [bool per
+    head]: a head keeps the window iff its recall reaches `threshold` on EVERY sample (min over the samples >= threshold).  NaN is
+    not windowed."""
+    rows = [list(r) for r in recall]
+    if not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows):
+        raise ValueError("decide_heads takes recall[samples][heads] with at least one sample and one head")
+    thr = float(threshold)
+    out = []
+    for h in range(len(rows[0])):
+        vals = [float(r[h]) for r in rows]
+        out.append(not any(math.isnan(v) for v in vals) and min(vals) >= thr)
+    return out
 
 
 def full_ranges(Sq, Skv):
@@ -191,11 +264,133 @@ def _prefixed_ranges(F, hw, W, sink, prefix, rows):
     return _table(per_block, Skv, Sq)
 
 
-def call_transformer(transformer, dense, *args, forward=None, **kw):
+class HeadWindowHost:
+    """What a DiT with `attn_window` needs for per-head windows chosen by recall (mixed into WanTransformer3DModel and
+    HunyuanVideoTransformer3DModel).
+
+        attn_window_recall   0.0: off -- the forward is the shared-window one, launch for launch.  > 0 (with attn_window > 0): a head
+                             keeps the window only where its measured recall reaches this value
+        attn_window_stats    after a calibration forward one record per layer:
+                             {"layer", "recall": [[per head] per sample], "windowed": [bool per head]}
+        reset_attn_window_heads()   forgets the decisions (the samplers call it at the start of a video)
+
+    With attn_window > 0 and attn_window_recall > 0 a forward is dense until the model is calibrated; the calibration forward is the
+    one call_transformer(..., calibrate=True) marks.  Its self-attention output is the dense one (the ranged entry with the one
+    full range, which also writes lse_full); a second launch with the window table writes a scratch output and lse_part, and
+    alg_attn_lse_recall reduces the two over the latent-query rows into row `layer` of a device buffer [layers][samples][heads].
+    One copy to pinned host memory and one stream synchronisation end the forward; decide_heads then runs per layer on the host.
+    Later forwards launch, per layer, the dense entry (no head windowed), today's shared-table entry (every head) or
+    alg_flash_attn_d128_ranges_heads with the layer's device-resident table: nothing on the host depends on the GPU any more, so
+    they can be captured."""
+
+    def _head_window_init(self):
+        self.attn_window_recall = 0.0
+        self.attn_window_stats = []
+        self._attn_calibrate = False     # set around one forward by call_transformer(calibrate=True)
+        self._attn_decided = None        # (key, [windowed per head] per layer)
+        self._attn_head_tables = {}      # (base table id, windowed) -> KvRanges | KvRangesHeads | None
+        self._attn_cal = None            # the calibration buffers, allocated on the first calibration forward only
+        self._attn_full = {}             # (Sq, Skv) -> the one-full-range table of the calibration forward's dense launch
+
+    @property
+    def attn_window_calibrated(self):
+        return self._attn_decided is not None
+
+    def reset_attn_window_heads(self):
+        self._attn_decided = None
+        self._attn_head_tables = {}
+        self.attn_window_stats = []
+
+    def _head_window_mode(self, key, layers, samples, heads, rows, o_shape):
+        """How this forward's self-attention launches: None (attn_window_recall is 0: the shared window, nothing else happens),
+        "dense" (not calibrated, not asked to), "tables" (calibrated for `key`), or the calibration buffers (this IS the
+        calibration forward).  `key`: what the decisions depend on (video shape, window, sink)."""
+        thr = float(self.attn_window_recall)
+        if not thr > 0.0:
+            return None
+        key = (key, thr)
+        if self._attn_decided is not None and self._attn_decided[0] != key:
+            self.reset_attn_window_heads()       # another video shape, window, sink or threshold: the decisions do not carry over
+        if self._attn_decided is not None:
+            return "tables"
+        if not self._attn_calibrate:
+            return "dense"
+        c = self._attn_cal
+        shape = (layers, samples, heads, rows, tuple(o_shape))
+        if c is None or c.shape != shape:
+            c = self._attn_cal = SimpleNamespace(shape=shape)
+            dev = self.device
+            c.lse_full = torch.empty(samples, heads, rows, dtype=torch.float32, device=dev)
+            c.lse_part = torch.empty(samples, heads, rows, dtype=torch.float32, device=dev)
+            c.o = torch.empty(*o_shape, dtype=torch.bfloat16, device=dev)   # the windowed launch's output: not used
+            c.recall = torch.zeros(layers, samples, heads, dtype=torch.float64, device=dev)
+            c.host = torch.zeros(layers, samples, heads, dtype=torch.float64).pin_memory()
+        c.key = key
+        return c
+
+    def _head_window_finish(self, c, bases):
+        """End of the calibration forward: the recalls to the host (one copy, one synchronisation), decide_heads per layer, and
+        the per-head tables of `bases` (the window tables this forward used) built and uploaded."""
+        c.host.copy_(c.recall, non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        decided, stats = [], []
+        for li, rec in enumerate(c.host.tolist()):
+            # a recall is a fraction of softmax mass: where the window holds all of it, the two fp32 LSEs may differ by an ulp
+            # the wrong way round (1 + 2e-7 seen), which is clipped here; NaN stays NaN
+            rec = [[min(x, 1.0) for x in row] for row in rec]
+            windowed = decide_heads(rec, self.attn_window_recall)
+            decided.append(tuple(windowed))
+            stats.append({"layer": li, "recall": rec, "windowed": windowed})
+        self._attn_decided = (c.key, decided)
+        self.attn_window_stats = stats
+        for base in bases:
+            for windowed in set(decided):
+                self._head_table(base, windowed)
+
+    def _head_full(self, Sq, Skv):
+        if (Sq, Skv) not in self._attn_full:
+            self._attn_full[(Sq, Skv)] = full_ranges(Sq, Skv)
+        return self._attn_full[(Sq, Skv)]
+
+    def _head_table(self, base, windowed):
+        """head_window_ranges(base, windowed), built and uploaded once."""
+        k = (id(base), windowed)
+        if k not in self._attn_head_tables:
+            t = head_window_ranges(base, windowed)
+            if t is not None:
+                t.on(self.device)
+            self._attn_head_tables[k] = (base, t)     # (base is held: its id stays its own)
+        return self._attn_head_tables[k][1]
+
+    def _layer_table(self, base, layer):
+        """The table layer `layer` launches with once calibrated."""
+        return self._head_table(base, self._attn_decided[1][layer])
+
+
+def call_transformer(transformer, dense, *args, forward=None, calibrate=False, **kw):
     """transformer(*args, **kw) -- or forward(*args, **kw), a bound method of it (CogVideoX: forward_assembled) -- with its frame
     window switched off for this one forward when `dense` (the samplers' dense early steps, `attn_window_dense_steps`); the
-    attribute is restored whatever the forward does."""
+    attribute is restored whatever the forward does.
+
+    calibrate (the samplers: the step max(attn_window_dense_steps, 1) - 1): with attn_window > 0 and attn_window_recall > 0 this
+    forward is the CALIBRATION forward of an uncalibrated transformer -- dense in output, it measures the recall of every (layer,
+    head) and decides the per-head tables the later forwards use; an active step cache is forced to compute it (a hit would skip
+    the layers that have to be measured).  Otherwise, and for every other forward, nothing changes."""
     fn = transformer if forward is None else forward
+    if (calibrate and getattr(transformer, "attn_window", 0) and getattr(transformer, "attn_window_recall", 0.0) > 0.0
+            and not transformer.attn_window_calibrated):
+        from . import _lib
+        if _lib._capturing():   # refused before anything is launched
+            raise _lib.AlgHipError("attn window: the calibration forward (attn_window_recall > 0, heads not decided yet) cannot be "
+                                   "captured into a graph -- the windowed heads are decided on the host from recalls the GPU has "
+                                   "just written; run it eagerly (later forwards replay device-resident tables and can be captured)")
+        transformer._attn_calibrate = True
+        if "cache_keys" in kw:
+            kw["cache_force"] = True
+        try:
+            return fn(*args, **kw)
+        finally:
+            transformer._attn_calibrate = False
     if not dense or not getattr(transformer, "attn_window", 0):
         return fn(*args, **kw)
     saved = transformer.attn_window
@@ -206,8 +401,15 @@ def call_transformer(transformer, dense, *args, forward=None, **kw):
         transformer.attn_window = saved
 
 
+def calibration_step(dense_steps):
+    """The sampler step whose forwards calibrate the per-head windows: the last dense one, or step 0 when there is none."""
+    return max(int(dense_steps), 1) - 1
+
+
 def ranges_to_mask(kv_ranges):
-    """bool [Sq, Skv]: True where the query's block visits the key."""
+    """bool [Sq, Skv]: True where the query's block visits the key; [H, Sq, Skv] for a per-head table."""
+    if isinstance(kv_ranges, KvRangesHeads):
+        return torch.stack([ranges_to_mask(r) for r in kv_ranges.per_head])
     m = torch.zeros(kv_ranges.Sq, kv_ranges.Skv, dtype=torch.bool)
     a = kv_ranges.table
     for j in range(kv_ranges.q_blocks):

@@ -23,7 +23,8 @@
 //
 // The same frame serves alg_flash_attn_d128_ranges (opt-in frame-window attention, alg_amd/attn_window.py): there a workgroup runs
 // the key ranges of its row of a device table one after the other, each as a panel of its own, with one drain of the ring between
-// two of them.
+// two of them.  alg_flash_attn_d128_ranges_heads is the same instantiation with a table row per (head, q
+// block) and an optional output of the log2-domain log-sum-exp of the visited keys (the recall policy of attn_window.py).
 //
 // DEFAULT for non-causal, ungrouped attention over at least POLICY_TILES KV tiles; ALG_ATTN128_Q64=0 switches it off (the
 // 32-query pipelined kernel takes over), =2 takes every call of at least MIN_TILES tiles (tests).
@@ -59,6 +60,9 @@ struct P {
   int use_statement;   // 0: every tile through the C++ tile body (ALG_ATTN128_Q64=3: tests of the frame on its own)
   const int32_t* ranges;   // RANGES: device table [q_blocks][max_ranges][2] of (begin, end) key indices (alg_flash_attn_d128_ranges)
   int max_ranges;
+  // RANGES, alg_flash_attn_d128_ranges_heads only (0 and NULL from the other entries; the dense instantiation reads neither)
+  int head_rows;           // q_blocks when the table has a leading head dimension ([heads][q_blocks][max_ranges][2]), else 0
+  float* lse;              // fp32 [batch][heads][Sq]: log2-domain log-sum-exp of the scaled scores over the visited keys, or NULL
 };
 
 // RANGES = false: every key of the panel, ONE segment [0, Skv) -- the dense kernel.  RANGES = true: the workgroup's 256 queries
@@ -232,7 +236,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
   if constexpr (RANGES) {
     // defensive read: whatever the table holds, the segment lies inside the panel and starts on the dense kernel's tile grid
     // (the bit-2/3 column permutation and the 16-byte alignment of the V^T DMA hold for begin % 64 == 0 only)
-    const int32_t* r = p.ranges + ((int64_t)qb * p.max_ranges + seg) * 2;
+    const int32_t* r = p.ranges + ((int64_t)(h * p.head_rows + qb) * p.max_ranges + seg) * 2;   // (h, head_rows: wave-uniform)
     const int begin = __builtin_amdgcn_readfirstlane(min(max(r[0], 0), p.Skv)) & ~(KVB - 1);
     const int end = __builtin_amdgcn_readfirstlane(min(max(r[1], 0), p.Skv));
     if (end <= begin) continue;
@@ -344,6 +348,11 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
           *(uint2*)(op + d) = v;
         }
     }
+    if constexpr (RANGES) {
+      // sum over the visited keys of 2^(c s) = 2^(c m_run) l_tot: once per query (both h2 lanes hold l_tot and the same m_run)
+      if (p.lse != nullptr && q_row < Sq && x.h2 == 0)
+        p.lse[(int64_t)bh * Sq + q_row] = visited ? m_run[qh] * c + __builtin_amdgcn_logf(l_tot) : -INFINITY;
+    }
   }
   if (tap && x.l31 == 0 && x.h2 == 0) {
     uint64_t* cp = p.clk + (size_t)(blockIdx.x >> 6) * 4;   // one workgroup owns a slot (block / 64 < slots)
@@ -357,7 +366,8 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
 template <bool RANGES>
 static int launch_q64(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
                       int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs, int64_t o_rs,
-                      float scale, const int32_t* ranges, int max_ranges, int use_statement, hipStream_t stream) {
+                      float scale, const int32_t* ranges, int max_ranges, int use_statement, hipStream_t stream,
+                      int table_heads = 1, float* lse = nullptr) {
   using namespace a128q;
   // 31-bit BYTE offsets inside one (batch, head) for the DMA's lane offsets; V^T rows cover whole 64-key tiles
   if ((int64_t)(Skv + 64) * k_rs * 2 >= (1ll << 31) || (int64_t)129 * vt_rs * 2 >= (1ll << 31) ||
@@ -382,6 +392,8 @@ static int launch_q64(const char* what, const void* q, const void* k, const void
   p.use_statement = use_statement;
   p.ranges = ranges;
   p.max_ranges = max_ranges;
+  p.head_rows = table_heads == 1 ? 0 : p.q_blocks;
+  p.lse = lse;
   const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
   if (grid > 0x7fffffff) return 1;
   hipLaunchKernelGGL(flash_attn_d128_q64_kernel<RANGES>, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
@@ -407,37 +419,120 @@ int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, i
 using namespace alg;
 
 // Each block of 256 queries attends to its row of a table of key ranges (include/alg_hip.h).  This kernel is the only one that
-// takes a table: ALG_ATTN128_Q64 routes this entry nowhere else, and only its value 3 (statement off) is honoured here.
-extern "C" int alg_flash_attn_d128_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
-                                          int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
-                                          int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
-                                          float scale, const int32_t* kv_ranges, int max_ranges, void* stream) {
+// takes a table: ALG_ATTN128_Q64 routes these entries nowhere else, and only its value 3 (statement off) is honoured here.
+static int ranges_entry(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                        int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride, int64_t vt_bstride,
+                        int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, const int32_t* kv_ranges,
+                        int max_ranges, int table_heads, float* lse, void* stream) {
   if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
-    set_error("alg_flash_attn_d128_ranges: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", batch, heads, Sq, Skv);
+    set_error("%s: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", what, batch, heads, Sq, Skv);
     return ALG_EINVAL;
   }
   if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > 4) {
-    set_error("alg_flash_attn_d128_ranges: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)",
+    set_error("%s: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)", what,
               (const void*)kv_ranges, max_ranges);
+    return ALG_EINVAL;
+  }
+  if (table_heads != 1 && table_heads != heads) {
+    set_error("%s: table_heads must be 1 (one table for every head) or heads = %d, got %d", what, heads, table_heads);
+    return ALG_EINVAL;
+  }
+  if ((uintptr_t)lse & 3) {
+    set_error("%s: lse must be 4-byte aligned (got %p)", what, (const void*)lse);
     return ALG_EINVAL;
   }
   if (q_rstride % 8 || q_bstride % 8 || k_rstride % 8 || k_bstride % 8 || vt_rstride % 8 || vt_bstride % 8 ||
       o_rstride % 4 || o_bstride % 4 || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) ||
       ((uintptr_t)o & 7)) {
-    set_error("alg_flash_attn_d128_ranges: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned");
+    set_error("%s: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned", what);
     return ALG_EINVAL;
   }
   if (vt_rstride < (int64_t)((Skv + a128q::KVB - 1) / a128q::KVB) * a128q::KVB) {
-    set_error("alg_flash_attn_d128_ranges: vt row stride %lld must cover Skv rounded up to %d", (long long)vt_rstride,
-              a128q::KVB);
+    set_error("%s: vt row stride %lld must cover Skv rounded up to %d", what, (long long)vt_rstride, a128q::KVB);
     return ALG_EINVAL;
   }
-  const int rc = launch_q64<true>("alg_flash_attn_d128_ranges", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
-                                  k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges,
-                                  opt(OPT_ATTN128_Q64) != 3, (hipStream_t)stream);
+  const int rc = launch_q64<true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
+                                  vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
+                                  (hipStream_t)stream, table_heads, lse);
   if (rc == 1) {
-    set_error("alg_flash_attn_d128_ranges: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large");
+    set_error("%s: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large", what);
     return ALG_ELIMIT;
   }
   return rc;
+}
+
+extern "C" int alg_flash_attn_d128_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
+                                          int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
+                                          int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
+                                          float scale, const int32_t* kv_ranges, int max_ranges, void* stream) {
+  return ranges_entry("alg_flash_attn_d128_ranges", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride,
+                      vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, 1, nullptr, stream);
+}
+
+// The same launch with a table row per (head, q block) when table_heads == heads, and the log-sum-exp output (include/alg_hip.h).
+extern "C" int alg_flash_attn_d128_ranges_heads(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
+                                                int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride,
+                                                int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
+                                                int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_ranges,
+                                                int table_heads, float* lse, void* stream) {
+  return ranges_entry("alg_flash_attn_d128_ranges_heads", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
+                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, stream);
+}
+
+namespace alg {
+namespace a128q {
+
+// Recall of a window (alg_attn_lse_recall): per panel the mean over the rows [row0, row0 + rows) of 2^(lse_part - lse_full), the
+// fraction of a query's softmax mass that lies on the keys `lse_part` was taken over.  One workgroup per panel, two levels, both
+// in a fixed order and in double: each lane sums its rows (stride 4 x 1024), then the lanes are summed (as vae.hip: gn_final).
+constexpr int RECALL_THREADS = 1024;
+
+__device__ inline float recall_term(float part, float full) {
+  return part == -INFINITY ? 0.0f : __builtin_amdgcn_exp2f(part - full);
+}
+
+__global__ __launch_bounds__(RECALL_THREADS) void lse_recall_kernel(const float* __restrict__ part, const float* __restrict__ full,
+                                                                    double* __restrict__ out, int Sq, int row0, int rows) {
+  __shared__ double red[RECALL_THREADS / 64];
+  const int64_t base = (int64_t)blockIdx.x * Sq + row0;
+  part += base, full += base;
+  double acc = 0.0;
+  // float4 where the panel's first row is 16-byte aligned in both buffers (workgroup-uniform); scalars otherwise and for the tail
+  const bool vec = (((uintptr_t)part | (uintptr_t)full) & 15) == 0;
+  const int rows4 = vec ? rows & ~3 : 0;
+  for (int i = (int)threadIdx.x * 4; i < rows4; i += RECALL_THREADS * 4) {
+    const float4 a = *(const float4*)(part + i), b = *(const float4*)(full + i);
+    acc += ((double)recall_term(a.x, b.x) + (double)recall_term(a.y, b.y)) +
+           ((double)recall_term(a.z, b.z) + (double)recall_term(a.w, b.w));
+  }
+  for (int i = rows4 + (int)threadIdx.x; i < rows; i += RECALL_THREADS) acc += (double)recall_term(part[i], full[i]);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < RECALL_THREADS / 64; ++w) tot += red[w];
+    out[blockIdx.x] = tot / (double)rows;
+  }
+}
+
+}  // namespace a128q
+}  // namespace alg
+
+extern "C" int alg_attn_lse_recall(const float* lse_part, const float* lse_full, double* out, int panels, int Sq, int row0,
+                                   int rows, void* stream) {
+  if (!lse_part || !lse_full || !out || ((uintptr_t)lse_part & 3) || ((uintptr_t)lse_full & 3) || ((uintptr_t)out & 7)) {
+    set_error("alg_attn_lse_recall: lse_part / lse_full must be 4-byte and out 8-byte aligned device pointers");
+    return ALG_EINVAL;
+  }
+  if (panels <= 0 || Sq <= 0 || row0 < 0 || rows <= 0 || (int64_t)row0 + rows > Sq) {
+    set_error("alg_attn_lse_recall: bad argument (panels=%d Sq=%d row0=%d rows=%d: the rows must lie inside [0, Sq))", panels, Sq,
+              row0, rows);
+    return ALG_EINVAL;
+  }
+  hipLaunchKernelGGL(a128q::lse_recall_kernel, dim3((unsigned)panels), dim3(a128q::RECALL_THREADS), 0, (hipStream_t)stream,
+                     lse_part, lse_full, out, Sq, row0, rows);
+  return check_launch("alg_attn_lse_recall");
 }

@@ -120,13 +120,15 @@ class HunyuanVideoImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, text_encoder_2=None, tokenizer_2=None, image_processor=None,
-                        device="cuda", fp8_attention=False, fp8=False, attn_window=0, **_):
+                        device="cuda", fp8_attention=False, fp8=False, attn_window=0, attn_window_recall=0.0,
+                        **_):
         """Local-disk loader of a diffusers-format HunyuanVideo-I2V directory (`run.py:68-90`): `transformer/`,
         `text_encoder/` (Llava-Llama-3) + `tokenizer/` + `image_processor/`, `text_encoder_2/` (CLIP-L text tower) +
         `tokenizer_2/`, `vae/`, `scheduler/`.  `fp8=True` loads the transformer with e4m3 block linears
         (HunyuanVideoTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.
         `attn_window` > 0 switches the transformer's frame-window joint attention on with that many latent frames on each side
-        (alg_amd/attn_window.py; off by default)."""
+        (alg_amd/attn_window.py; off by default); `attn_window_recall` > 0 keeps that window only on the heads whose measured
+        recall reaches it (attn_window.HeadWindowHost)."""
         import os
 
         from .schedulers import FlowMatchEulerDiscreteScheduler
@@ -140,6 +142,8 @@ class HunyuanVideoImageToVideoPipeline:
                                                                          fp8=fp8)
         if attn_window:
             transformer.attn_window = int(attn_window)
+        if attn_window_recall:
+            transformer.attn_window_recall = float(attn_window_recall)
         if text_encoder is None and has("text_encoder"):
             from .text_encoder_llava import LlavaForConditionalGeneration
             text_encoder = LlavaForConditionalGeneration.from_pretrained(model_path, device=device)
@@ -548,6 +552,10 @@ class HunyuanVideoImageToVideoPipeline:
 
         neg3 = lambda a, b: torch.cat([a, a, b], dim=0)
         neg2 = lambda a, b: torch.cat([a, b], dim=0)
+        # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
+        use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
+        if use_recall:
+            self.transformer.reset_attn_window_heads()
         for i, t in enumerate(timesteps):
             if self._interrupt:
                 continue
@@ -579,7 +587,8 @@ class HunyuanVideoImageToVideoPipeline:
             noise_pred = attn_window.call_transformer(
                 self.transformer, i < attn_window_dense_steps, hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
                 encoder_attention_mask=mask, pooled_projections=pooled, guidance=guidance,
-                attention_kwargs=attention_kwargs, return_dict=False)[0]
+                attention_kwargs=attention_kwargs, return_dict=False,
+                calibrate=use_recall and i == attn_window.calibration_step(attn_window_dense_steps))[0]
             # hy:1254-1261 keys the combine on shape[0] (3 -> three chunks, 2 -> two chunks, anything else: none)
             if noise_pred.shape[0] in (2, 3):
                 noise_pred = _lib.cfg_combine(noise_pred.contiguous(), noise_pred.shape[0], true_cfg_scale)

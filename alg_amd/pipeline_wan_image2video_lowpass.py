@@ -105,12 +105,12 @@ class WanImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, image_encoder=None, image_processor=None, device="cuda",
-                        fp8=False, fp8_attention=False, step_cache=0.0, attn_window=0, **_):
+                        fp8=False, fp8_attention=False, step_cache=0.0, attn_window=0, attn_window_recall=0.0, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
         (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan).
         `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default);
         `attn_window` > 0 its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by
-        default)."""
+        default); `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost)."""
         import os
 
         from .image_encoder_clip import CLIPImageProcessor, CLIPVisionModel
@@ -126,6 +126,8 @@ class WanImageToVideoPipeline:
             transformer.step_cache = float(step_cache)
         if attn_window:
             transformer.attn_window = int(attn_window)
+        if attn_window_recall:
+            transformer.attn_window_recall = float(attn_window_recall)
         if text_encoder is None and has("text_encoder"):
             text_encoder = UMT5EncoderModel.from_pretrained(model_path, device=device)
         if tokenizer is None:
@@ -476,6 +478,13 @@ class WanImageToVideoPipeline:
                 raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
                                        "passes and leave the single-GPU result; run one of the two")
             self.transformer.reset_step_cache()
+        # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
+        use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
+        if use_recall:
+            if cfg_split is not None:
+                raise _lib.AlgHipError("attn_window_recall > 0 with cfg_split: the two ranks of a CFG pair would decide the windowed "
+                                       "heads on different passes; run one of the two")
+            self.transformer.reset_attn_window_heads()
         for i, t in enumerate(timesteps):
             if self._interrupt or i < self._first_step:
                 continue
@@ -514,7 +523,8 @@ class WanImageToVideoPipeline:
                                         "(the Wan ALG loop needs guidance_scale > 1)")
             latent_model_input = assemble_channel_concat(latents, groups, tdtype)
             # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
-            dit = functools.partial(attn_window.call_transformer, self.transformer, i < attn_window_dense_steps)
+            dit = functools.partial(attn_window.call_transformer, self.transformer, i < attn_window_dense_steps,
+                                    calibrate=use_recall and i == attn_window.calibration_step(attn_window_dense_steps))
             n = latent_model_input.shape[0]
             timestep = t.expand(n).to(device)
             ehs = torch.cat(embeds, dim=0)

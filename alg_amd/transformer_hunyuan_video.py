@@ -36,7 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import frame_window_ranges
+from .attn_window import HeadWindowHost, KvRangesHeads, frame_window_ranges
 from .transformer_wan import k_scale_bound
 
 BF = torch.bfloat16
@@ -148,7 +148,7 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
     return sd
 
 
-class HunyuanVideoTransformer3DModel:
+class HunyuanVideoTransformer3DModel(HeadWindowHost):
     dtype = BF
 
     # the block linears that fp8 mode quantises, per output channel (attribute names of a block's weights): dual blocks, latent
@@ -181,6 +181,9 @@ class HunyuanVideoTransformer3DModel:
         self.attn_window = 0
         self.attn_sink_frames = 1
         self._attn_ranges = {}    # (F, hw, valid, J, window, sink) -> KvRanges, or None where the window covers the whole video
+        # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall (over the latent queries,
+        # minimum over the samples) reaches it keep the window (attn_window.HeadWindowHost).  0.0: the shared window, nothing allocated
+        self._head_window_init()
         self.fp8 = bool(fp8)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
@@ -530,6 +533,13 @@ class HunyuanVideoTransformer3DModel:
         H8 = _lib.headnorm_rope_fp8
         kvr = [self._window_ranges(F_, first, valid[b], J) for b in range(N)] if self.attn_window else [None] * N   # None: dense
 
+        # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
+        hwm = None
+        if kvr[0] is not None:
+            hwm = self._head_window_mode((F_, first, int(self.attn_window), int(self.attn_sink_frames)),
+                                         len(self.dual) + len(self.single), N, heads, J, (N, J, D))
+        cal = hwm if hwm not in (None, "dense", "tables") else None
+
         def attention(bi=0):
             """bi: index of the block in dual + single order (its K scales, fp8_attention)."""
             prof = self.profile
@@ -546,9 +556,28 @@ class HunyuanVideoTransformer3DModel:
                                              ks_off=(bi * N + b) * heads, vt_off=b * D * ws.J_pad, vts_off=b * D,
                                              o_off=b * J * (D + M))
                     continue
-                if kvr[b] is not None:
+                kv_b = kvr[b]
+                if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
+                    kv_b = None if hwm == "dense" or cal is not None else self._layer_table(kvr[b], bi)
+                if cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
+                    A = (1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad)
+                    offs = dict(q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad, lse_off=b * heads * J)
+                    _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, ws.am, *A, J * (D + M), D + M, scale,
+                                                      self._head_full(J, S + valid[b]), lse=cal.lse_full, o_off=b * J * (D + M), **offs)
+                    _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, cal.o, *A, J * D, D, scale, kvr[b], lse=cal.lse_part,
+                                                      o_off=b * J * D, **offs)
+                    _lib.attn_lse_recall(cal.lse_part, cal.lse_full, cal.recall, heads, J, row0=0, rows=S,      # latent queries only
+                                         part_off=b * heads * J, full_off=b * heads * J, out_off=(bi * N + b) * heads)
+                    continue
+                if isinstance(kv_b, KvRangesHeads):
+                    _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
+                                                      J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
+                                                      q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
+                                                      o_off=b * J * (D + M))
+                    continue
+                if kv_b is not None:
                     _lib.flash_attn_d128_ranges(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D,
-                                                2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kvr[b],
+                                                2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
                                                 q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
                                                 o_off=b * J * (D + M))
                     continue
@@ -714,6 +743,9 @@ class HunyuanVideoTransformer3DModel:
                 T("gemm_out_mlp", G, ws.am, PK(Lw, Lw.out[0]), ws.x, J, D, AM, AM, AM, D, bias=Lw.out[1], R=ws.x, ldr=D, gate=ws.mod, gate_off=2 * D,
                   strideGate=smod_bs, gate_seg_stride=sseg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D,
                   strideR=J * D)
+
+        if cal is not None:
+            self._head_window_finish(cal, kvr)
 
         # ---- output head: AdaLayerNormContinuous (scale | shift), projection, unpatchify ----
         G(ws.semb1, w.ada_out[0], ws.mod_out, N, 2 * D, D, D, D, 2 * D, bias=w.ada_out[1])

@@ -31,7 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import frame_window_ranges
+from .attn_window import HeadWindowHost, KvRangesHeads, frame_window_ranges
 from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
@@ -153,7 +153,7 @@ def k_scale_bound(norm_weight, norm_dim, heads, rope):
     return (w * (1.02 * math.sqrt(norm_dim * (2.0 if rope else 1.0)) / 448.0)).contiguous()
 
 
-class WanTransformer3DModel(StepCacheHost):
+class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
     dtype = BF
 
     def __init__(self, config: WanTransformerConfig, weights: dict, device="cuda", fp8=False, fp8_attention=False):
@@ -185,6 +185,9 @@ class WanTransformer3DModel(StepCacheHost):
         self.attn_window = 0
         self.attn_sink_frames = 1
         self._attn_ranges = {}    # (F, hw, window, sink) -> KvRanges, or None where the window covers the whole video
+        # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall reaches it keep the window
+        # (attn_window.HeadWindowHost: attn_window_stats, reset_attn_window_heads).  0.0: the shared window, nothing allocated
+        self._head_window_init()
         if config.qk_norm != "rms_norm_across_heads" or config.attention_head_dim != 128:
             raise NotImplementedError("the Wan DiT path is built for rms_norm_across_heads and head_dim 128")
         if tuple(config.patch_size)[0] != 1:
@@ -477,6 +480,14 @@ class WanTransformer3DModel(StepCacheHost):
         packed = None
         sc = self._step_cache_begin(ws.x, cache_keys, cache_force, 0, S)   # None: off, nothing below differs from the plain forward
         kvr = self._window_ranges(F_, S // F_) if self.attn_window else None    # None: the dense launch
+        # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
+        hwm = None
+        if kvr is not None:
+            hwm = self._head_window_mode((F_, S // F_, int(self.attn_window), int(self.attn_sink_frames)), len(self.blocks), N,
+                                         heads, S, (N, S, D))
+        cal = hwm if hwm not in (None, "dense", "tables") else None
+        full = self._head_full(S, S) if cal is not None else None
+        kvr0 = kvr
         for li, L in enumerate(self.blocks):
             if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
                 break                 # hit: x = x1 + the cached tail, straight to the head
@@ -506,7 +517,18 @@ class WanTransformer3DModel(StepCacheHost):
             else:
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
-                if kvr is not None:
+                if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
+                    kvr = None if hwm == "dense" or cal is not None else self._layer_table(kvr0, li)
+                if cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
+                    A = (N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale)
+                    T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, *A, full, lse=cal.lse_full, k_off=D)
+                    T("attn_calib", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, cal.o, *A, kvr0, lse=cal.lse_part, k_off=D)
+                    T("attn_calib", _lib.attn_lse_recall, cal.lse_part, cal.lse_full, cal.recall, N * heads, S,
+                      out_off=li * N * heads)
+                elif isinstance(kvr, KvRangesHeads):
+                    T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
+                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, k_off=D)
+                elif kvr is not None:
                     T("attn_self", _lib.flash_attn_d128_ranges, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
                       S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, k_off=D)
                 else:
@@ -556,6 +578,9 @@ class WanTransformer3DModel(StepCacheHost):
             if len(self.blocks) == 1:  # no tail to skip: the probe and the rule run all the same (x + 0 on a hit)
                 T("step_cache", sc.after_block0, ws.x)
             T("step_cache", sc.end, ws.x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
+
+        if cal is not None:
+            self._head_window_finish(cal, [kvr0])
 
         # ---- output head ----
         _lib.layernorm_mod_f32(ws.x, ws.y, None, None, ws.mod_out, ws.mod_out, 2 * D, N, S, D, cfg.eps, scale_off=D,

@@ -323,6 +323,31 @@ int alg_flash_attn_d128_ranges(const void* q, const void* k, const void* vt, voi
                                int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, const int32_t* kv_ranges,
                                int max_ranges, void* stream);
 
+/* alg_flash_attn_d128_ranges with (a) a table row per head and (b) an optional log-sum-exp output: the primitives under the
+ * per-head frame window chosen by recall (alg_amd/attn_window.py: head_window_ranges, decide_heads).  Same kernel, same operands,
+ * same defensive reading of the table, and with table_heads == 1 and lse == NULL the bits of alg_flash_attn_d128_ranges.
+ *   kv_ranges   : DEVICE table int32 [table_heads][q_blocks][max_ranges][2].  table_heads is 1 (one table for every head, the
+ *                 layout above) or `heads` (the workgroup of (b, h, q block) reads row h * q_blocks + q block; one table serves
+ *                 every batch item).  Any other value is ALG_EINVAL.  Each head's slice obeys the rules above.
+ *   lse         : NULL, or DEVICE fp32 [batch][heads][Sq], contiguous, 4-byte aligned (else ALG_EINVAL).  When given, the kernel
+ *                 also writes once per query  lse[b][h][q] = log2( sum over the VISITED keys j of 2^(c * q.k_j) ),
+ *                 c = scale * log2(e): the log2-domain log-sum-exp of the scaled scores, from the kernel's own running max and
+ *                 fp32 row sum (m * c + log2(l); docs/numerics.md).  o is bit for bit what it is without lse.
+ * A block the table leaves without a key writes zeros to o and -inf to lse. */
+int alg_flash_attn_d128_ranges_heads(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                                     int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
+                                     int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale,
+                                     const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, void* stream);
+
+/* Recall of a key subset from two lse outputs of alg_flash_attn_d128_ranges_heads over the same queries (lse_part: the subset,
+ * lse_full: all keys), both fp32 [panels][Sq] with panels = batch * heads:
+ *   out[p] = mean over q in [row0, row0 + rows) of exp2f(lse_part[p][q] - lse_full[p][q]),  a term being 0 where lse_part is -inf
+ * i.e. the fraction of the softmax mass of panel p's queries that lies on the subset.  out is DEVICE double [panels], 8-byte
+ * aligned.  One launch for all panels; fp32 exp2, double accumulation in a fixed two-level order (per lane, then across the lanes
+ * of the panel's workgroup): run-to-run bit-identical.  0 <= row0, rows >= 1, row0 + rows <= Sq, else ALG_EINVAL. */
+int alg_attn_lse_recall(const float* lse_part, const float* lse_full, double* out, int panels, int Sq, int row0, int rows,
+                        void* stream);
+
 /* Opt-in e4m3 form of alg_flash_attn_d128 on v_mfma_scale_f32_32x32x64_f8f6f4 (attention128_fp8.hip): non-causal, ungrouped
  * (kv_group != 1 or causal != 0 is ALG_EINVAL), separate Sq / Skv, ragged last tile, bf16 output; strides in elements = bytes.
  *   q  : OCP e4m3, element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d;  q_scale: float32 [batch][Sq][heads]

@@ -20,6 +20,13 @@ d = 64) -- alg_flash_attn_d64_ex in its default form (pre-scaled Q, split-KV tai
 no tail) with the full-range table and the windows 1 / 2 / 4 --, the C2 steps with attn_window = 2 between two dense runs, and the
 accuracy arms on the trained-like CogVideoX model at the medium grid (8 heads x 64, 4 blocks, 9 latent frames of 384 tokens).
 
+--family heads is the per-head window chosen by recall (profiles/attn_window_heads_ab.json), head_dim 128 only: at the same three
+launch shapes alg_flash_attn_d128_ranges_heads with the full-range table and with the half-coverage window, each without and with
+the lse output, and a per-head table in which every second head is dense -- set against 0.5 * (all dense + all windowed) of the same
+job; the first two arms are repeated last (their distance is the job's spread).  Its steps arms time iterations 0-1 of the C3 / C5 /
+C4 workloads with attn_window_recall = 0.9 on the half-coverage window (iteration 0 is the calibration forward; on these Gaussian
+weights no head reaches 0.9, so iteration 1 is dense) between two runs with attn_window = 0.  No bound is set for any of them.
+
 Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
 import argparse
 import gc
@@ -36,7 +43,7 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from alg_amd import _lib  # noqa: E402
-from alg_amd.attn_window import frame_window_ranges, full_ranges  # noqa: E402
+from alg_amd.attn_window import frame_window_ranges, full_ranges, head_window_ranges  # noqa: E402
 
 BF = torch.bfloat16
 DEV = torch.device("cuda:0")
@@ -112,6 +119,89 @@ def kernel_arms(name, iters):
     out["full_range_minus_dense_ms"] = out["arms"]["full_range"]["median_ms"] - d
     out["full_range_within_dense_spread"] = out["full_range_minus_dense_ms"] <= out["dense_spread_ms"]
     del qk, vt, o
+    torch.cuda.empty_cache()
+    return out
+
+
+def kernel_arms_heads(name, iters):
+    F, hw, valid, rows, heads = SHAPES[name]
+    S, D = F * hw, heads * 128
+    Sq, Skv = S + rows, S + valid
+    pad = (Sq + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(Sq, 2 * D, generator=g, device=DEV, dtype=BF)
+    vt = torch.randn(D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(Sq, D, dtype=BF, device=DEV)
+    lse = torch.empty(heads, Sq, dtype=torch.float32, device=DEV)
+    args = (qk, qk, vt, o, 1, heads, Sq, Skv, Sq * 2 * D, 2 * D, Sq * 2 * D, 2 * D, D * pad, pad, Sq * D, D, 1.0 / 128 ** 0.5)
+    w, half = window_for(F, hw, valid, rows, 0.5)
+    full = full_ranges(Sq, Skv)
+    mixed = head_window_ranges(half, [h % 2 == 0 for h in range(heads)])
+    for t in (half, full, mixed):
+        t.device_table
+    run = lambda t, l: (lambda: _lib.flash_attn_d128_ranges_heads(*args, t, lse=l, k_off=D))
+    arms = [("full_range_first", run(full, None), 1.0), ("window_first", run(half, None), half.coverage),
+            ("full_range_lse", run(full, lse), 1.0), ("window_lse", run(half, lse), half.coverage),
+            ("half_heads_dense", run(mixed, None), mixed.coverage),
+            ("shared_entry_window", lambda: _lib.flash_attn_d128_ranges(*args, half, k_off=D), half.coverage),
+            ("full_range_last", run(full, None), 1.0), ("window_last", run(half, None), half.coverage)]
+    out = {"queries": Sq, "keys": Skv, "heads": heads, "frames": F, "tokens_per_frame": hw, "attn_window": w, "arms": {}}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        arms[0][1]()
+        torch.cuda.synchronize()
+    for label, fn, cov in arms:
+        r = timed(fn, iters)
+        r["coverage"] = cov
+        out["arms"][label] = r
+    ms = lambda k: out["arms"][k]["median_ms"]
+    d = out["full_range_ms_mean"] = (ms("full_range_first") + ms("full_range_last")) / 2
+    h = out["window_ms_mean"] = (ms("window_first") + ms("window_last")) / 2
+    out["full_range_spread_ms"], out["window_spread_ms"] = abs(ms("full_range_first") - ms("full_range_last")), abs(ms("window_first") - ms("window_last"))
+    out["lse_cost_full_range_ms"], out["lse_cost_window_ms"] = ms("full_range_lse") - d, ms("window_lse") - h
+    out["half_heads_dense_over_mean_of_both"] = ms("half_heads_dense") / (0.5 * (d + h))
+    out["shared_entry_minus_new_entry_window_ms"] = ms("shared_entry_window") - h
+    del qk, vt, o, lse
+    torch.cuda.empty_cache()
+    return out
+
+
+def step_arms_heads(workload, recall=0.9):
+    F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
+    w_half = window_for(F, hw, valid, rows, 0.5)[0]
+    args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
+    wl.build()
+    torch.cuda.synchronize()
+    out = {"attn_window": w_half, "attn_window_recall": recall, "arms": {}}
+    for label, w, r in (("off_first", 0, 0.0), ("calibration_then_decided", w_half, recall), ("off_last", 0, 0.0)):
+        wl.model.attn_window, wl.model.attn_window_recall = w, r
+        bench.run_steps(wl, 1)
+        torch.cuda.synchronize()
+        with bench.SmiSampler(0) as smi:
+            t0 = time.perf_counter()
+            bench.run_steps(wl, 2)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+        sm = smi.summary() or {}
+        out["arms"][label] = {"attn_window": w, "attn_window_recall": r, "seconds_two_steps": s,
+                              "finite": bool(torch.isfinite(wl.last_out.float()).all().item()),
+                              "power_w": (sm.get("power_w") or {}).get("mean"), "sclk_mhz": (sm.get("sclk_mhz") or {}).get("mean")}
+        if r:
+            st = wl.model.attn_window_stats
+            flat = [x for rec in st for row in rec["recall"] for x in row]
+            out["layers_calibrated"] = len(st)
+            out["heads_windowed"] = sum(sum(rec["windowed"]) for rec in st)
+            out["recall_min_mean_max"] = [min(flat), sum(flat) / len(flat), max(flat)] if flat else None
+    a, b = out["arms"]["off_first"]["seconds_two_steps"], out["arms"]["off_last"]["seconds_two_steps"]
+    out["off_seconds_mean"], out["off_spread_seconds"] = (a + b) / 2, abs(a - b)
+    out["calibration_step_cost_seconds"] = out["arms"]["calibration_then_decided"]["seconds_two_steps"] - out["off_seconds_mean"]
+    out["calibration_step_cost_over_dense_step"] = out["calibration_step_cost_seconds"] / (out["off_seconds_mean"] / 2)
+    kvr = [t for t in wl.model._attn_ranges.values() if t is not None]
+    out["coverage"] = kvr[0].coverage if kvr else None
+    wl.model.attn_window, wl.model.attn_window_recall = 0, 0.0
+    del wl
+    gc.collect()
     torch.cuda.empty_cache()
     return out
 
@@ -340,7 +430,9 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--family", choices=["d128", "d64"], default="d128", help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2)")
+    ap.add_argument("--family", choices=["d128", "d64", "heads"], default="d128",
+                    help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2); heads: the per-head window chosen by recall (d = 128)")
+    ap.add_argument("--workloads", default="c3,c5,c4", help="--family heads: the workloads of the steps arms")
     a = ap.parse_args()
     parts = a.only or ["kernel", "accuracy", "steps"]
     res = {}
@@ -354,6 +446,21 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
 
+    if a.family == "heads":
+        res["weights"] = ("synthetic Gaussian: recall is about the coverage, so no head reaches a threshold above it; hit rates and "
+                          "quality on a trained checkpoint are unmeasured")
+        if "kernel" in parts:
+            res.setdefault("kernel", {})
+            for name in SHAPES:
+                res["kernel"][name] = kernel_arms_heads(name, a.iters)
+                save()
+        if "steps" in parts:
+            res.setdefault("steps", {})
+            for wlname in a.workloads.split(","):
+                res["steps"][wlname] = step_arms_heads(wlname)
+                save()
+        print(json.dumps(res))
+        return
     if a.family == "d64":
         if "kernel" in parts:
             res["kernel"] = {"c2_2x48x17776": kernel_arms_d64(a.iters)}
