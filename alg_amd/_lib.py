@@ -34,7 +34,7 @@ EXPORTS = (
     "alg_flash_attn_d64_workspace_bytes", "alg_calib_mfma_bf16", "alg_wall_clock_khz", "alg_attn_clock_tap", "alg_attn_path_tap",
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
-    "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall",
+    "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall", "alg_flash_attn_d64_ranges_heads",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -190,6 +190,8 @@ def load_library():
     lib.alg_flash_attn_d64_ex.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int64,
                                           c_int64, c_int64, c_int64, c_int64, c_float, c_int, c_void_p, c_int64, c_void_p]
     lib.alg_flash_attn_d64_ranges.argtypes = [c_void_p] * 4 + [c_int] * 3 + [c_int64] * 6 + [c_void_p, c_int, c_void_p]
+    lib.alg_flash_attn_d64_ranges_heads.argtypes = ([c_void_p] * 4 + [c_int] * 3 + [c_int64] * 6 +
+                                                    [c_void_p, c_int, c_int, c_void_p, c_void_p])
     lib.alg_patchify.argtypes = [c_void_p, c_int64, POINTER(c_void_p), c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_void_p]
     lib.alg_unpatchify.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
@@ -1056,6 +1058,39 @@ def flash_attn_d64_ranges(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt
     _check(lib.alg_flash_attn_d64_ranges(c_void_p(q.data_ptr() + 2 * q_off), c_void_p(k.data_ptr() + 2 * k_off), _ptr(vt), _ptr(o),
                                          batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride,
                                          _ptr(table), kv_ranges.max_ranges, _stream()), "alg_flash_attn_d64_ranges")
+    return o
+
+
+def flash_attn_d64_ranges_heads(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride,
+                                kv_ranges, lse=None, q_off=0, k_off=0, lse_off=0):
+    """flash_attn_d64_ranges with a table per head (kv_ranges: an attn_window.KvRangesHeads built for these heads and Sq == Skv == S)
+    or one for all (a KvRanges), and, when `lse` is given (fp32, contiguous, batch * heads * S elements from lse_off), the
+    log2-domain log-sum-exp of the pre-scaled scores over the keys each query visited (include/alg_hip.h:
+    alg_flash_attn_d64_ranges_heads).  One launch: no split-KV tail, no workspace."""
+    from .attn_window import KvRanges, KvRangesHeads
+    if not isinstance(kv_ranges, (KvRanges, KvRangesHeads)):
+        raise AlgHipError("flash_attn_d64_ranges_heads takes an attn_window.KvRanges or KvRangesHeads, got %s"
+                          % type(kv_ranges).__name__)
+    if kv_ranges.Sq != S or kv_ranges.Skv != S:
+        raise AlgHipError("flash_attn_d64_ranges_heads: the table was built for Sq=%d Skv=%d, the call has Sq=Skv=%d"
+                          % (kv_ranges.Sq, kv_ranges.Skv, S))
+    table_heads = kv_ranges.heads if isinstance(kv_ranges, KvRangesHeads) else 1
+    if table_heads not in (1, heads):
+        raise AlgHipError("flash_attn_d64_ranges_heads: the table was built for %d heads, the call has %d" % (table_heads, heads))
+    lib = load_library()
+    for t in (q, k, vt, o):
+        _dev(t, "attention operand")
+    lse_p = c_void_p(0)
+    if lse is not None:
+        _dev(lse, "lse")
+        if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < lse_off + batch * heads * S:
+            raise AlgHipError("flash_attn_d64_ranges_heads: lse must be contiguous fp32 with room for [batch][heads][S]")
+        lse_p = c_void_p(lse.data_ptr() + 4 * lse_off)
+    table = kv_ranges.on(q.device)
+    _check(lib.alg_flash_attn_d64_ranges_heads(c_void_p(q.data_ptr() + 2 * q_off), c_void_p(k.data_ptr() + 2 * k_off), _ptr(vt),
+                                               _ptr(o), batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride,
+                                               o_rstride, _ptr(table), kv_ranges.max_ranges, table_heads, lse_p, _stream()),
+           "alg_flash_attn_d64_ranges_heads")
     return o
 
 

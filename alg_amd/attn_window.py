@@ -10,7 +10,8 @@ f + W" is ONE contiguous run of keys, and the frame window is a host-side policy
     frame_window_ranges  the policy: conditioning frames (sink) + the frames within `window` of the block's own + the prompt
     ranges_to_mask       the table as a boolean [Sq, Skv] mask (tests, records)
 
-Per-head windows chosen by recall (head_dim 128: alg_flash_attn_d128_ranges_heads, alg_attn_lse_recall).  A frame window is nearly
+Per-head windows chosen by recall (head_dim 128: alg_flash_attn_d128_ranges_heads; head_dim 64: alg_flash_attn_d64_ranges_heads;
+both reduced by alg_attn_lse_recall).  A frame window is nearly
 exact for a head whose softmax mass lies in neighbouring frames and wrong for one that spreads it over the video, so with
 `attn_window_recall` > 0 the models measure, on one forward of each video, the RECALL of every (layer, head) -- the fraction of
 softmax mass its latent queries keep inside the window -- and only the heads that reach the threshold keep the window:
@@ -103,7 +104,7 @@ class KvRanges:
 class KvRangesHeads:
     """A table int32 [heads][q_blocks][max_ranges][2]: head h's slice is a KvRanges table for (Sq, Skv) and is validated as one
     (ValueError names the head in front of KvRanges' message).  What _lib.flash_attn_d128_ranges_heads takes for table_heads =
-    heads."""
+    heads, and _lib.flash_attn_d64_ranges_heads for Sq == Skv."""
 
     def __init__(self, table, Skv, Sq):
         t = torch.as_tensor(table)
@@ -265,8 +266,8 @@ def _prefixed_ranges(F, hw, W, sink, prefix, rows):
 
 
 class HeadWindowHost:
-    """What a DiT with `attn_window` needs for per-head windows chosen by recall (mixed into WanTransformer3DModel and
-    HunyuanVideoTransformer3DModel).
+    """What a DiT with `attn_window` needs for per-head windows chosen by recall (mixed into WanTransformer3DModel,
+    HunyuanVideoTransformer3DModel and CogVideoXTransformer3DModel).
 
         attn_window_recall   0.0: off -- the forward is the shared-window one, launch for launch.  > 0 (with attn_window > 0): a head
                              keeps the window only where its measured recall reaches this value
@@ -280,8 +281,13 @@ class HeadWindowHost:
     alg_attn_lse_recall reduces the two over the latent-query rows into row `layer` of a device buffer [layers][samples][heads].
     One copy to pinned host memory and one stream synchronisation end the forward; decide_heads then runs per layer on the host.
     Later forwards launch, per layer, the dense entry (no head windowed), today's shared-table entry (every head) or
-    alg_flash_attn_d128_ranges_heads with the layer's device-resident table: nothing on the host depends on the GPU any more, so
-    they can be captured."""
+    alg_flash_attn_d128_ranges_heads (CogVideoX, head_dim 64: alg_flash_attn_d64_ranges_heads) with the layer's device-resident
+    table: nothing on the host depends on the GPU any more, so they can be captured.
+
+    CogVideoX: the recall is taken over the latent-query rows [T, S) of the joint sequence (T prompt tokens first), and its dense
+    entry may plan a split-KV tail, which the ranged entry never does: the calibration forward's attention output is the dense
+    entry's SINGLE-LAUNCH form bit for bit (what ALG_ATTN_SPLIT_TAIL=0 gives) and differs from a planned tail by that option's
+    documented <= 1 bf16 step, in that one forward of the video."""
 
     def _head_window_init(self):
         self.attn_window_recall = 0.0

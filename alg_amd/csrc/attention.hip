@@ -32,6 +32,8 @@
 //                                           for any offset.  (ALG_ATTN_PP=7 is attention64_m16.hip.)
 //   flash_attn_d64_pipe_kernel<OFF, true>   the same two frames over the key ranges of a table, one range after the other
 //                                           (alg_flash_attn_d64_ranges: the opt-in frame window, off by default)
+//   flash_attn_d64_pipe_kernel<OFF, true, true>  ... that also write the log-sum-exp of the visited keys from an exact row sum
+//                                           (alg_flash_attn_d64_ranges_heads with an lse pointer: the calibration forward)
 //
 // Measured and removed (the sources are in the history, the records in profiles/r1_*, profiles/r3_attention_d64_pingpong.txt,
 // profiles/r3_attention_pipe_bench_ab.txt and docs/lab_notebook_r*.md).  MI355X, C2 shape (2 x 48 heads x 17,776 tokens),
@@ -81,10 +83,13 @@ struct AttnP {
   uint64_t* clk;   // clock tap (calibrate.hip: alg_attn_clock_tap) or NULL: {cycles, wall} at start / end of every 64th workgroup
   int clk_slots;
   uint64_t* path;  // path counters (calibrate.hip: alg_attn_path_tap) or NULL: {statement entries, tiles inside, tiles straight}
-  // flash_attn_d64_pipe_kernel<OFF, RANGES = true> only (alg_flash_attn_d64_ranges); the dense instantiations read none of them
-  const int32_t* ranges;   // device table [q_blocks][max_ranges][2] of (begin, end) key indices
+  // flash_attn_d64_pipe_kernel<OFF, RANGES = true> only (alg_flash_attn_d64_ranges, alg_flash_attn_d64_ranges_heads); the dense
+  // instantiations read none of them
+  const int32_t* ranges;   // device table [q_blocks][max_ranges][2] of (begin, end) key indices, or [heads][q_blocks][max_ranges][2]
   int max_ranges;
   int use_statement;       // 0: every tile through the C++ tile body (ALG_ATTN_PP=0: the frame on its own)
+  int head_rows;           // q_blocks when the table has a leading head dimension ([heads][q_blocks][max_ranges][2]), else 0
+  float* lse;              // fp32 [batch][heads][S]: log2-domain log-sum-exp of the (pre-scaled) scores over the visited keys, or NULL
 };
 
 struct Frag {
@@ -211,9 +216,15 @@ __device__ __forceinline__ void softmax_tile_lazy(const f32x16 (&s)[2], float c,
 // (-64, 64) (probabilities then span 2^-64 .. 2^64 at most before the lazy rescale threshold trips: harmless for fp32 /
 // bf16), and p = exp2(s) needs no subtraction at all.  Rows whose scores are further out keep a non-zero offset and take
 // the subtracting path; the exact max / rescale path is the lazy one of softmax_tile_lazy.
+//
+// EXACT (flash_attn_d64_pipe_kernel<OFF, true, LSE = true> only): *dl also accumulates (fp32 sum of the UNROUNDED probabilities) -
+// (the dot2 sum of the bf16-rounded ones), rescaled with l_run: l_run + *dl is the row sum a log-sum-exp wants, while l_run, the
+// probabilities and O -- everything the output is made of -- are computed exactly as without it.
+template <bool EXACT = false>
 __device__ __forceinline__ void softmax_tile_zero(const f32x16 (&s)[2], float& m_run, float& l_run, f32x16 (&o_acc)[2],
-                                                  bf16x8 (&pf)[4]) {
+                                                  bf16x8 (&pf)[4], float* dl = nullptr) {
   typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
+  float esum = 0.0f;   // EXACT: the unrounded sum of the last probs() pass
   auto probs = [&](auto sub_c, float m) -> float {
     constexpr bool SUB = decltype(sub_c)::value;
     float psum = 0.0f;
@@ -230,6 +241,7 @@ __device__ __forceinline__ void softmax_tile_zero(const f32x16 (&s)[2], float& m
           pk.u[j] = pack_bf2(p0, p1);
           psum = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf2v, pk.u[j]), __builtin_bit_cast(bf2v, 0x3f803f80u),
                                                  psum, false);
+          if constexpr (EXACT) esum += p0, esum += p1;
         }
         pf[sub * 2 + g] = pk.v;
       }
@@ -254,9 +266,11 @@ __device__ __forceinline__ void softmax_tile_zero(const f32x16 (&s)[2], float& m
     for (int dt = 0; dt < 2; ++dt)
 #pragma unroll
       for (int e = 0; e < 16; ++e) o_acc[dt][e] *= alpha;
+    if constexpr (EXACT) *dl *= alpha, esum = 0.0f;   // (the first pass's sum may be inf / NaN: it is dropped like psum)
     psum = probs(BoolC<true>{}, m_run);
   }
   l_run += psum;
+  if constexpr (EXACT) *dl += esum - psum;
 }
 
 // O^T += V^T P^T for one 64-row tile
@@ -493,8 +507,16 @@ __global__ __launch_bounds__(256) void flash_attn_d64_merge_kernel(const AttnP p
 // handed over by s_waitcnt vmcnt(0) + one workgroup barrier; inside a segment the DMA count per iteration stays constant (the
 // counted vmcnt(2) wait relies on it).  Everything a segment adds is wave-uniform and lives in SGPRs: nothing new is live across
 // the statement in vector registers (LaneCtx below).
-template <bool OFF, bool RANGES>
+//
+// LSE (RANGES only; alg_flash_attn_d64_ranges_heads with an lse pointer -- the host picks the instantiation): the epilogue also
+// writes the log2-domain log-sum-exp of the visited keys, m_run + log2(row sum).  The frame's own row sum l_run is a sum of
+// bf16-ROUNDED probabilities wherever the C++ tile body ran (each off by up to 2^-8), so these instantiations carry one more
+// per-lane value, dl = (exact fp32 sum) - (rounded sum) over those tiles (softmax_tile_zero<EXACT>; the statements add unrounded
+// probabilities themselves and never rescale, so dl passes them unchanged), and take log2(l + dl).  O is bit for bit what the
+// LSE = false instantiation writes; the four LSE = false instantiations have no trace of any of this.
+template <bool OFF, bool RANGES, bool LSE = false>
 __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const AttnP p) {
+  static_assert(RANGES || !LSE, "the LSE output exists on the ranged instantiations only");
   __shared__ __attribute__((aligned(16))) char smem[8 * ATT_TILE];
   char* const k_ring = smem;
   char* const v_ring = smem + 4 * ATT_TILE;
@@ -531,6 +553,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
 #pragma unroll
   for (int i = 0; i < 32; ++i) oa[i >> 4][i & 15] = 0.0f;
   float m_run = -INFINITY, l_run = 0.0f;
+  float dl = 0.0f;   // LSE only
 
   // Everything lane-derived is rebuilt from a lane id (LaneCtx): the C++ loops in front of and behind the statement each build
   // their own from a freshly laundered id, so that none of it is live across the statement (values that are compete with its
@@ -585,7 +608,8 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
       qk_tile(k_ring + (t & 3) * ATT_TILE, qf, c.f, s);
       if (ragged && t == T - 1) mask_tail(s, t * KVB, S, c.h2);
       bf16x8 pf[4];
-      softmax_tile_zero(s, m_run, l_run, oa, pf);
+      if constexpr (LSE) softmax_tile_zero<true>(s, m_run, l_run, oa, pf, &dl);
+      else softmax_tile_zero(s, m_run, l_run, oa, pf);
       pv_tile(v_ring + (t & 3) * ATT_TILE, pf, c.f, oa);
     }
   };
@@ -600,7 +624,7 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
   if constexpr (RANGES) {
     // defensive read: whatever the table holds, the segment lies inside the panel and starts on the dense kernel's tile grid
     // (the bit-2/3 column permutation and the 16-byte alignment of the V^T DMA hold for begin % 64 == 0 only)
-    const int32_t* r = p.ranges + ((int64_t)qb * p.max_ranges + seg) * 2;
+    const int32_t* r = p.ranges + ((int64_t)(h * p.head_rows + qb) * p.max_ranges + seg) * 2;   // (h, head_rows: wave-uniform)
     const int begin = __builtin_amdgcn_readfirstlane(min(max(r[0], 0), Sq)) & ~(KVB - 1);
     const int end = __builtin_amdgcn_readfirstlane(min(max(r[1], 0), Sq));
     if (end <= begin) continue;
@@ -735,6 +759,16 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
         *(uint2*)(op + d) = v;
       }
   }
+  if constexpr (LSE) {
+    // sum over the visited keys of 2^s = 2^m_run (l_tot + dl_tot) (Q is pre-scaled: the scores are in log2 units): once per query
+    // -- both h2 lanes hold the sums, and the same m_run (softmax_tile_zero folds the tile max across the halves before it moves
+    // the offset)
+    const float dl_tot = dl + __shfl_xor(dl, 32, 64);
+    if (p.lse != nullptr) {   // uniform
+      if (c.q_row < Sq && c.h2 == 0)
+        p.lse[(int64_t)bh * Sq + c.q_row] = visited ? m_run + __builtin_amdgcn_logf(l_tot + dl_tot) : -INFINITY;
+    }
+  }
   if (tap && c.lane == 0) {
     uint64_t* cp = p.clk + (size_t)(blockIdx.x >> 6) * 4;   // one workgroup owns a slot (block / 64 < slots)
     cp[0] = tap_c0, cp[1] = tap_r0, cp[2] = __builtin_readcyclecounter(), cp[3] = wall_clock64();
@@ -866,8 +900,13 @@ static void attn64_launch_ranges(unsigned blocks, AttnP& p, hipStream_t s) {
   int pp = opt(OPT_ATTN_PP);
   if (pp >= 3 && ((int64_t)(p.S + 4 * KVB) * p.q_rs * 2 >= (1ll << 31) || (int64_t)65 * p.vt_rs * 2 >= (1ll << 31))) pp = 0;
   p.use_statement = pp >= 3;
-  if (pp == 8) hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<true, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
-  else hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<false, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
+  if (p.lse == nullptr) {
+    if (pp == 8) hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<true, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
+    else hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<false, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
+  } else {   // the LSE output: the instantiations that also carry the exact row sum (named last: the others keep their order)
+    if (pp == 8) hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<true, true, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
+    else hipLaunchKernelGGL((flash_attn_d64_pipe_kernel<false, true, true>), dim3(blocks), dim3(ATT_THREADS), 0, s, p);
+  }
 }
 
 }  // namespace alg
@@ -907,7 +946,7 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
   p.path = path_tap_for(s);
   p.unit0 = p.tail_units = p.tail_split = p.tail_tiles = 0;
   p.ws_o = p.ws_ml = nullptr;
-  p.ranges = nullptr, p.max_ranges = 0, p.use_statement = 1;
+  p.ranges = nullptr, p.max_ranges = 0, p.use_statement = 1, p.head_rows = 0, p.lse = nullptr;
   const int nbh = batch * heads;
   // the split-KV tail runs only in a caller-provided workspace (alg_flash_attn_d64_workspace_bytes); without one the whole
   // problem is a single launch (same rows up to fp32 summation order in the tail units)
@@ -928,21 +967,29 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
 }
 
 // Each block of 256 queries attends to its row of a table of key ranges (include/alg_hip.h): pre-scaled Q only (the
-// ALG_ATTN_Q_PRESCALED form of alg_flash_attn_d64_ex), ONE launch -- no split-KV tail, no workspace.
-extern "C" int alg_flash_attn_d64_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
-                                         int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
-                                         int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
-                                         void* stream) {
+// ALG_ATTN_Q_PRESCALED form of alg_flash_attn_d64_ex), ONE launch -- no split-KV tail, no workspace.  Both entries run this:
+// `what` names the caller in the error text.
+static int ranges64_entry(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                          int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
+                          int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, void* stream) {
   const int rc = attn64_check(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride);
   if (rc != ALG_OK) {
-    set_error("alg_flash_attn_d64_ranges: the operands fail the checks of alg_flash_attn_d64 (batch=%d heads=%d S=%d; q/k/vt "
+    set_error("%s: the operands fail the checks of alg_flash_attn_d64 (batch=%d heads=%d S=%d; q/k/vt "
               "16-byte aligned rows, o 8-byte aligned, vt row stride %lld covering S rounded up to %d)",
-              batch, heads, S, (long long)vt_rstride, KVB);
+              what, batch, heads, S, (long long)vt_rstride, KVB);
     return rc;
   }
   if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > 4) {
-    set_error("alg_flash_attn_d64_ranges: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)",
+    set_error("%s: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)", what,
               (const void*)kv_ranges, max_ranges);
+    return ALG_EINVAL;
+  }
+  if (table_heads != 1 && table_heads != heads) {
+    set_error("%s: table_heads must be 1 (one table for every head) or heads = %d, got %d", what, heads, table_heads);
+    return ALG_EINVAL;
+  }
+  if ((uintptr_t)lse & 3) {
+    set_error("%s: lse must be 4-byte aligned (got %p)", what, (const void*)lse);
     return ALG_EINVAL;
   }
   hipStream_t s = (hipStream_t)stream;
@@ -958,11 +1005,30 @@ extern "C" int alg_flash_attn_d64_ranges(const void* q, const void* k, const voi
   p.unit0 = p.tail_units = p.tail_split = p.tail_tiles = 0;
   p.ws_o = p.ws_ml = nullptr;
   p.ranges = kv_ranges, p.max_ranges = max_ranges;
+  p.head_rows = table_heads == 1 ? 0 : p.q_blocks;
+  p.lse = lse;
   const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
   if (grid > 0x7fffffff) {
-    set_error("alg_flash_attn_d64_ranges: grid too large (batch=%d heads=%d S=%d)", batch, heads, S);
+    set_error("%s: grid too large (batch=%d heads=%d S=%d)", what, batch, heads, S);
     return ALG_EINVAL;
   }
   attn64_launch_ranges((unsigned)grid, p, s);
-  return check_launch("alg_flash_attn_d64_ranges");
+  return check_launch(what);
+}
+
+extern "C" int alg_flash_attn_d64_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                                         int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                                         int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
+                                         void* stream) {
+  return ranges64_entry("alg_flash_attn_d64_ranges", q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride,
+                        o_bstride, o_rstride, kv_ranges, max_ranges, 1, nullptr, stream);
+}
+
+// The same launch with a table row per (head, q block) when table_heads == heads, and the log-sum-exp output (include/alg_hip.h).
+extern "C" int alg_flash_attn_d64_ranges_heads(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                                               int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                                               int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
+                                               int table_heads, float* lse, void* stream) {
+  return ranges64_entry("alg_flash_attn_d64_ranges_heads", q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride,
+                        vt_rstride, o_bstride, o_rstride, kv_ranges, max_ranges, table_heads, lse, stream);
 }

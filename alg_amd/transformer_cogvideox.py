@@ -36,7 +36,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .attn_window import frame_window_ranges
+from .attn_window import HeadWindowHost, KvRangesHeads, frame_window_ranges
 from .step_cache import StepCacheHost
 
 
@@ -81,7 +81,7 @@ def _bf(t, device):
     return t.to(device=device, dtype=torch.bfloat16).contiguous()
 
 
-class CogVideoXTransformer3DModel(StepCacheHost):
+class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
     dtype = torch.bfloat16
 
     # the block linears that fp8 mode quantises, per output channel: Q|K, V, attention out, feed-forward in / out
@@ -140,6 +140,9 @@ class CogVideoXTransformer3DModel(StepCacheHost):
         self.attn_window = 0
         self.attn_sink_frames = 1
         self._attn_ranges = {}    # (frames, hw, T, window, sink) -> KvRanges, or None where the window covers the whole video
+        # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall reaches it keep the window
+        # (attn_window.HeadWindowHost: attn_window_stats, reset_attn_window_heads).  0.0: the shared window, nothing allocated
+        self._head_window_init()
         self._sincos = {}
         dev = self.device
         w = weights
@@ -353,7 +356,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
                 self._quantize_layer(L, drop_bf16=False)
         return ws["q8"], ws["q8s"]
 
-    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr=None):
+    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr=None, cal=None):
         """One transformer block with e4m3 operands on its five linears: the launch order of the bf16 block, each GEMM input
         quantised per token into q8 / q8s first (by the LayerNorm itself where a norm produces it)."""
         cfg, G, TM = self.config, _lib.gemm, self._timed
@@ -393,7 +396,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
            bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
         TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
            cfg.qk_norm_eps, q_scale=q_scale)
-        self._attention(ws, kvr, N, S, scale, prescale)
+        self._attention(ws, kvr, N, S, scale, prescale, cal)
         quant(att, D)
         lin("gemm_out", L["wo8"], x, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
@@ -420,12 +423,27 @@ class CogVideoXTransformer3DModel(StepCacheHost):
             self._attn_ranges[key] = r
         return self._attn_ranges[key]
 
-    def _attention(self, ws, kvr, N, S, scale, prescale):
-        """softmax(q k^T * scale) v of the joint sequence from qk / vt into att: the dense launch, or (kvr: the frame-window table)
-        the ranged one."""
+    def _attention(self, ws, kvr, N, S, scale, prescale, cal=None):
+        """softmax(q k^T * scale) v of the joint sequence from qk / vt into att: the dense launch, (kvr: the frame-window table) the
+        ranged one, or (kvr: a per-head table, attn_window_recall > 0) alg_flash_attn_d64_ranges_heads.
+
+        cal = (buffers, layer, window table, prompt tokens): the calibration forward of HeadWindowHost.  att is written by the
+        per-head entry with the one full range -- the dense entry's single-launch form, bit for bit -- which also writes lse_full; a
+        second launch with the window table writes lse_part (its output goes to a scratch buffer), and alg_attn_lse_recall reduces
+        the two over the latent-query rows [T, S) into row `layer` of the recall buffer."""
         cfg = self.config
         D, Hn = cfg.inner_dim, cfg.num_attention_heads
         qk, vt, att, S_pad = ws["qk"], ws["vt"], ws["att"], ws["S_pad"]
+        if cal is not None:
+            c, layer, base, T = cal
+            A = (N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D)
+            self._timed("attn", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, att, *A, self._head_full(S, S), lse=c.lse_full, k_off=D)
+            self._timed("attn_calib", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, c.o, *A, base, lse=c.lse_part, k_off=D)
+            return self._timed("attn_calib", _lib.attn_lse_recall, c.lse_part, c.lse_full, c.recall, N * Hn, S, row0=T, rows=S - T,
+                               out_off=layer * N * Hn)
+        if isinstance(kvr, KvRangesHeads):
+            return self._timed("attn", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad,
+                               S_pad, S * D, D, kvr, k_off=D)
         if kvr is not None:
             return self._timed("attn", _lib.flash_attn_d64_ranges, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad,
                                S * D, D, kvr, k_off=D)
@@ -538,13 +556,23 @@ class CogVideoXTransformer3DModel(StepCacheHost):
         wo_k, wf1_k, wf2_k = ("pwo", "pwf1", "pwf2") if packed else ("wo", "wf1", "wf2")
         kvr = self._window_ranges(Fr // p_t, (Hh // p) * (Ww // p), T) if self.attn_window else None   # None: the dense launch
         sc = self._step_cache_begin(x, cache_keys, cache_force, T, P)   # None: off, nothing below differs from the plain forward
+        # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
+        hwm = None
+        if kvr is not None:
+            hwm = self._head_window_mode((Fr // p_t, (Hh // p) * (Ww // p), T, int(self.attn_window), int(self.attn_sink_frames)),
+                                         len(self.layers), N, Hn, S, (N, S, D))
+        calib = hwm if hwm not in (None, "dense", "tables") else None
+        kvr0, cal = kvr, None
         for li, L in enumerate(self.layers):
             if li == 1 and sc is not None and TM("step_cache", sc.after_block0, x):
                 break                 # hit: x = x1 + the cached tail, straight to the head
             m1 = li * 12 * D          # norm1: shift @+0, scale @+2D, gate @+4D (each [2][D])
             m2 = m1 + 6 * D           # norm2
+            if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
+                kvr = None if hwm == "dense" or calib is not None else self._layer_table(kvr0, li)
+                cal = (calib, li, kvr0, T) if calib is not None else None
             if fp8:
-                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr)
+                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr, cal)
                 continue
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
                T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
@@ -563,7 +591,7 @@ class CogVideoXTransformer3DModel(StepCacheHost):
                     TM("gemm_vt", G, *vt_call[0], **vt_call[1])
                 TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
                                    cfg.qk_norm_eps, q_scale=q_scale)
-            self._attention(ws, kvr, N, S, scale, prescale)
+            self._attention(ws, kvr, N, S, scale, prescale, cal)
             TM("gemm_out", G, att, L[wo_k], x, S, D, D, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
               strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * D, strideC=S * D, strideR=S * D)
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm2_w"], L["norm2_b"], mod, mod, self.mod_cols, N, S, D,
@@ -577,6 +605,9 @@ class CogVideoXTransformer3DModel(StepCacheHost):
             if len(self.layers) == 1:  # no tail to skip: the probe and the rule run all the same (x + 0 on a hit)
                 TM("step_cache", sc.after_block0, x)
             TM("step_cache", sc.end, x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
+
+        if calib is not None:
+            self._head_window_finish(calib, [kvr0])
 
         # 4. norm_final over the joint sequence, AdaLayerNorm on the video tokens, proj_out, unpatchify
         _lib.layernorm_modulate(x, y, self.norm_final_w, self.norm_final_b, None, None, 0, N, S, D, T, cfg.norm_eps)

@@ -283,6 +283,31 @@ int alg_flash_attn_d64_ranges(const void* q, const void* k, const void* vt, void
                               int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
                               int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, void* stream);
 
+/* alg_flash_attn_d64_ranges with (a) a table row per head and (b) an optional log-sum-exp output: the d = 64 twin of
+ * alg_flash_attn_d128_ranges_heads below, the primitive under CogVideoX's per-head frame window chosen by recall
+ * (alg_amd/attn_window.py: head_window_ranges, decide_heads).  Same kernel, same operands and checks, same defensive reading of the
+ * table, the same choice by ALG_ATTN_PP, one launch; alg_flash_attn_d64_ranges IS this entry with table_heads == 1 and lse == NULL.
+ *   kv_ranges   : DEVICE table int32 [table_heads][q_blocks][max_ranges][2].  table_heads is 1 (one table for every head, the
+ *                 layout above) or `heads` (the workgroup of (b, h, q block) reads row h * q_blocks + q block; one table serves
+ *                 every batch item).  Any other value is ALG_EINVAL.  Each head's slice obeys the rules above.
+ *   lse         : NULL, or DEVICE fp32 [batch][heads][S], contiguous, 4-byte aligned (else ALG_EINVAL).  When given, the kernel
+ *                 also writes once per query  lse[b][h][q] = log2( sum over the VISITED keys j of 2^(q.k_j) )  -- q is pre-scaled,
+ *                 so the scores are in log2 units and no factor is applied -- as m + log2(l) from the kernel's own running offset
+ *                 and row sum.  o is bit for bit what it is without lse.
+ *                 Numerics: the d = 64 frames sum the bf16-ROUNDED probabilities in their C++ tile body (fdot2 over the packed P,
+ *                 round to nearest), where the d = 128 kernel keeps an fp32 sum of the unrounded ones; that sum alone would put up
+ *                 to one bf16 rounding, 2^-8 relative, into l (5.6e-3 into lse).  A launch with lse therefore runs instantiations
+ *                 of the kernel that also carry, per query, the difference between the fp32 sum of the unrounded probabilities
+ *                 and the rounded sum over those tiles, and lse is taken from their total: it has fp32 accuracy, like the d = 128
+ *                 entry's (docs/numerics.md), at the price of two more additions per score pair in the C++ tile body of that
+ *                 launch only.  A launch without lse runs the kernels of alg_flash_attn_d64_ranges.  alg_attn_lse_recall takes the
+ *                 lse of either entry.
+ * A block the table leaves without a key writes zeros to o and -inf to lse. */
+int alg_flash_attn_d64_ranges_heads(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                                    int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                                    int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, int table_heads,
+                                    float* lse, void* stream);
+
 /* wan:910-917 (WanTransformer3DModel self- and cross-attention, head_dim 128; diffusers WanAttnProcessor SDPA)
  * Same contract as alg_flash_attn_d64 with head_dim 128 and separate query / key lengths:
  *   q : element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d,  s < Sq
@@ -339,8 +364,9 @@ int alg_flash_attn_d128_ranges_heads(const void* q, const void* k, const void* v
                                      int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale,
                                      const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, void* stream);
 
-/* Recall of a key subset from two lse outputs of alg_flash_attn_d128_ranges_heads over the same queries (lse_part: the subset,
- * lse_full: all keys), both fp32 [panels][Sq] with panels = batch * heads:
+/* Recall of a key subset from two lse outputs of alg_flash_attn_d128_ranges_heads or of alg_flash_attn_d64_ranges_heads (it knows
+ * nothing of the head dimension) over the same queries (lse_part: the subset, lse_full: all keys), both fp32 [panels][Sq] with
+ * panels = batch * heads:
  *   out[p] = mean over q in [row0, row0 + rows) of exp2f(lse_part[p][q] - lse_full[p][q]),  a term being 0 where lse_part is -inf
  * i.e. the fraction of the softmax mass of panel p's queries that lies on the subset.  out is DEVICE double [panels], 8-byte
  * aligned.  One launch for all panels; fp32 exp2, double accumulation in a fixed two-level order (per lane, then across the lanes

@@ -3,6 +3,7 @@ run of this).  One job, arms alternated, package power and shader clock sampled 
 
     python scripts/attn_window_ab.py --out profiles/attn_window_ab.json [--only kernel|steps|accuracy]
     python scripts/attn_window_ab.py --family d64 --out profiles/attn_window_d64_ab.json [--only kernel|steps|accuracy]
+    python scripts/attn_window_ab.py --family heads64 --out profiles/attn_window_heads_d64_ab.json [--only kernel|steps]
 
   kernel    alg_flash_attn_d128 against alg_flash_attn_d128_ranges at the three launch shapes (C3 32,760 x 40 heads, C5 75,600 x 40,
             C4 119,056 queries x 118,848 keys x 24 heads): the dense entry (first and last arm: their distance is the job's spread),
@@ -26,6 +27,13 @@ the lse output, and a per-head table in which every second head is dense -- set 
 job; the first two arms are repeated last (their distance is the job's spread).  Its steps arms time iterations 0-1 of the C3 / C5 /
 C4 workloads with attn_window_recall = 0.9 on the half-coverage window (iteration 0 is the calibration forward; on these Gaussian
 weights no head reaches 0.9, so iteration 1 is dense) between two runs with attn_window = 0.  No bound is set for any of them.
+
+--family heads64 is the same for head_dim 64 (CogVideoX, profiles/attn_window_heads_d64_ab.json): at the C2 launch shape
+alg_flash_attn_d64_ranges_heads with the full-range table and with the window-2 table, each without and with the lse output, a per-head
+table in which every second head is dense against 0.5 * (all dense + all windowed) of the same job, and for orientation the shared-table
+entry on the window and the dense entry in its default form (split-KV tail on); the steps arms time iterations 0-1 of the C2 workload with
+attn_window = 2, attn_window_recall = 0.9 between two runs with the window off (iteration 0 is the calibration forward), and record the
+recall minimum, mean and maximum next to the coverage.  No bound is set for any of them.
 
 Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
 import argparse
@@ -166,9 +174,12 @@ def kernel_arms_heads(name, iters):
     return out
 
 
-def step_arms_heads(workload, recall=0.9):
-    F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
-    w_half = window_for(F, hw, valid, rows, 0.5)[0]
+def step_arms_heads(workload, recall=0.9, window=None):
+    if window is not None:
+        w_half = window        # (CogVideoX: the window is given; 2 has a coverage of 0.44 at C2)
+    else:
+        F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
+        w_half = window_for(F, hw, valid, rows, 0.5)[0]
     args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
     wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
     wl.build()
@@ -248,6 +259,51 @@ def kernel_arms_d64(iters):
     out["full_range_over_dense"] = out["arms"]["full_range"]["median_ms"] / d    # (no split-KV tail: 1.5-5 % expected, attention.hip)
     out["full_range_within_dense_spread"] = out["full_range_minus_dense_ms"] <= out["dense_spread_ms"]
     del qk, vt, o
+    torch.cuda.empty_cache()
+    return out
+
+
+def kernel_arms_heads_d64(iters, window=2):
+    S, D, N, heads = C2_T + C2_F * C2_HW, C2_HEADS * 64, C2_N, C2_HEADS
+    pad = (S + 127) // 128 * 128
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(N, S, 2 * D, generator=g, device=DEV, dtype=BF)          # the model's layout: Q | K rows, V^T apart
+    qk[:, :, :D] *= 0.125 * 1.4426950408889634                                # Q pre-scaled: the scores are in log2 units
+    vt = torch.randn(N, D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(N, S, D, dtype=BF, device=DEV)
+    lse = torch.empty(N, heads, S, dtype=torch.float32, device=DEV)
+    args = (qk, qk, vt, o, N, heads, S, S * 2 * D, 2 * D, D * pad, pad, S * D, D)
+    win = frame_window_ranges(C2_F, C2_HW, window, prefix=C2_T)
+    full = full_ranges(S, S)
+    mixed = head_window_ranges(win, [h % 2 == 0 for h in range(heads)])
+    for t in (win, full, mixed):
+        t.device_table
+    run = lambda t, l: (lambda: _lib.flash_attn_d64_ranges_heads(*args, t, lse=l, k_off=D))
+    arms = [("full_range_first", run(full, None), 1.0), ("window_first", run(win, None), win.coverage),
+            ("full_range_lse", run(full, lse), 1.0), ("window_lse", run(win, lse), win.coverage),
+            ("half_heads_dense", run(mixed, None), mixed.coverage),
+            ("shared_entry_window", lambda: _lib.flash_attn_d64_ranges(*args, win, k_off=D), win.coverage),
+            ("dense_entry_split_tail", lambda: _lib.flash_attn_d64(*args, 0.125, k_off=D, q_prescaled=True), 1.0),
+            ("full_range_last", run(full, None), 1.0), ("window_last", run(win, None), win.coverage)]
+    out = {"samples": N, "tokens": S, "heads": heads, "frames": C2_F, "tokens_per_frame": C2_HW, "prompt_tokens": C2_T,
+           "attn_window": window, "arms": {}}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        arms[0][1]()
+        torch.cuda.synchronize()
+    for label, fn, cov in arms:
+        r = timed(fn, iters)
+        r["coverage"] = cov
+        out["arms"][label] = r
+    ms = lambda k: out["arms"][k]["median_ms"]
+    d = out["full_range_ms_mean"] = (ms("full_range_first") + ms("full_range_last")) / 2
+    h = out["window_ms_mean"] = (ms("window_first") + ms("window_last")) / 2
+    out["full_range_spread_ms"], out["window_spread_ms"] = abs(ms("full_range_first") - ms("full_range_last")), abs(ms("window_first") - ms("window_last"))
+    out["lse_cost_full_range_ms"], out["lse_cost_window_ms"] = ms("full_range_lse") - d, ms("window_lse") - h
+    out["half_heads_dense_over_mean_of_both"] = ms("half_heads_dense") / (0.5 * (d + h))
+    out["shared_entry_minus_new_entry_window_ms"] = ms("shared_entry_window") - h
+    out["full_range_over_dense_entry"] = d / ms("dense_entry_split_tail")
+    del qk, vt, o, lse
     torch.cuda.empty_cache()
     return out
 
@@ -430,8 +486,9 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--family", choices=["d128", "d64", "heads"], default="d128",
-                    help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2); heads: the per-head window chosen by recall (d = 128)")
+    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64"], default="d128",
+                    help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2); heads: the per-head window chosen by recall (d = 128); "
+                         "heads64: the same for d = 64 (CogVideoX, C2)")
     ap.add_argument("--workloads", default="c3,c5,c4", help="--family heads: the workloads of the steps arms")
     a = ap.parse_args()
     parts = a.only or ["kernel", "accuracy", "steps"]
@@ -446,6 +503,17 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
 
+    if a.family == "heads64":
+        res["weights"] = ("synthetic Gaussian: recall is about the coverage, so no head reaches a threshold above it; hit rates and "
+                          "quality on a trained checkpoint are unmeasured")
+        if "kernel" in parts:
+            res["kernel"] = {"c2_2x48x17776": kernel_arms_heads_d64(a.iters)}
+            save()
+        if "steps" in parts:
+            res["steps"] = {"c2": step_arms_heads("c2", window=2)}
+            save()
+        print(json.dumps(res))
+        return
     if a.family == "heads":
         res["weights"] = ("synthetic Gaussian: recall is about the coverage, so no head reaches a threshold above it; hit rates and "
                           "quality on a trained checkpoint are unmeasured")
