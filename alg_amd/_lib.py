@@ -35,6 +35,7 @@ EXPORTS = (
     "alg_flash_attn_d128_fp8", "alg_quantize_fp8_khead", "alg_quantize_fp8_vt", "alg_rmsnorm_rope_fp8", "alg_headnorm_rope_fp8",
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
     "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall", "alg_flash_attn_d64_ranges_heads",
+    "alg_flash_attn_d128_ranges_order", "alg_flash_attn_d64_ranges_order",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -126,6 +127,8 @@ def load_library():
     lib.alg_flash_attn_d128_ranges.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d128_ranges_heads.argtypes = ([c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 +
                                                      [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p])
+    lib.alg_flash_attn_d128_ranges_order.argtypes = ([c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 +
+                                                     [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p])
     lib.alg_attn_lse_recall.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p]
     lib.alg_flash_attn_d128_ex.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
     lib.alg_flash_attn_d128_dual.argtypes = ([c_void_p] * 3 + [c_int] + [c_int64] * 4 + [c_void_p] * 2 + [c_int] + [c_int64] * 4 +
@@ -192,6 +195,8 @@ def load_library():
     lib.alg_flash_attn_d64_ranges.argtypes = [c_void_p] * 4 + [c_int] * 3 + [c_int64] * 6 + [c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d64_ranges_heads.argtypes = ([c_void_p] * 4 + [c_int] * 3 + [c_int64] * 6 +
                                                     [c_void_p, c_int, c_int, c_void_p, c_void_p])
+    lib.alg_flash_attn_d64_ranges_order.argtypes = ([c_void_p] * 4 + [c_int] * 3 + [c_int64] * 6 +
+                                                    [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p])
     lib.alg_patchify.argtypes = [c_void_p, c_int64, POINTER(c_void_p), c_void_p, c_int, c_int, c_int, c_int, c_int,
                                  c_int, c_void_p]
     lib.alg_unpatchify.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
@@ -577,16 +582,43 @@ def flash_attn_d128_ranges_heads(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs,
     """flash_attn_d128_ranges with a table per head (kv_ranges: an attn_window.KvRangesHeads built for these heads) or one for all
     (a KvRanges), and, when `lse` is given (fp32, contiguous, batch * heads * Sq elements from lse_off), the log2-domain
     log-sum-exp of the scaled scores over the keys each query visited (include/alg_hip.h: alg_flash_attn_d128_ranges_heads)."""
+    return _ranges_heads_d128("flash_attn_d128_ranges_heads", None, q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs,
+                              vt_rs, o_bs, o_rs, scale, kv_ranges, lse, q_off, k_off, vt_off, o_off, lse_off)
+
+
+def flash_attn_d128_ranges_order(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, scale, kv_ranges,
+                                 order, lse=None, q_off=0, k_off=0, vt_off=0, o_off=0, lse_off=0):
+    """flash_attn_d128_ranges_heads with its workgroups in the order `order` gives, an attn_window.LaunchOrder built for this
+    (batch, heads, ceil(Sq / 256)): only that type is taken, so every order that reaches the kernel from Python holds every unit
+    exactly once.  The result is flash_attn_d128_ranges_heads' bit for bit (include/alg_hip.h: alg_flash_attn_d128_ranges_order)."""
+    _order_check("flash_attn_d128_ranges_order", order, batch, heads, Sq)
+    return _ranges_heads_d128("flash_attn_d128_ranges_order", order, q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs,
+                              vt_rs, o_bs, o_rs, scale, kv_ranges, lse, q_off, k_off, vt_off, o_off, lse_off)
+
+
+def _order_check(what, order, batch, heads, Sq):
+    from .attn_window import Q_BLOCK, LaunchOrder
+    if not isinstance(order, LaunchOrder):
+        raise AlgHipError("%s takes an attn_window.LaunchOrder, got %s" % (what, type(order).__name__))
+    q_blocks = (Sq + Q_BLOCK - 1) // Q_BLOCK
+    # (a unit's index is (b * heads + h) * q_blocks + qb: batch and heads enter it through their product only)
+    if (order.batch * order.heads, order.q_blocks) != (batch * heads, q_blocks):
+        raise AlgHipError("%s: the order was built for (batch, heads, q_blocks) = (%d, %d, %d), the call has (%d, %d, %d)"
+                          % (what, order.batch, order.heads, order.q_blocks, batch, heads, q_blocks))
+
+
+def _ranges_heads_d128(what, order, q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, scale,
+                       kv_ranges, lse, q_off, k_off, vt_off, o_off, lse_off):
     from .attn_window import KvRanges, KvRangesHeads
     if not isinstance(kv_ranges, (KvRanges, KvRangesHeads)):
-        raise AlgHipError("flash_attn_d128_ranges_heads takes an attn_window.KvRanges or KvRangesHeads, got %s"
-                          % type(kv_ranges).__name__)
+        raise AlgHipError("%s takes an attn_window.KvRanges or KvRangesHeads, got %s"
+                          % (what, type(kv_ranges).__name__))
     if kv_ranges.Sq != Sq or kv_ranges.Skv != Skv:
-        raise AlgHipError("flash_attn_d128_ranges_heads: the table was built for Sq=%d Skv=%d, the call has Sq=%d Skv=%d"
-                          % (kv_ranges.Sq, kv_ranges.Skv, Sq, Skv))
+        raise AlgHipError("%s: the table was built for Sq=%d Skv=%d, the call has Sq=%d Skv=%d"
+                          % (what, kv_ranges.Sq, kv_ranges.Skv, Sq, Skv))
     table_heads = kv_ranges.heads if isinstance(kv_ranges, KvRangesHeads) else 1
     if table_heads not in (1, heads):
-        raise AlgHipError("flash_attn_d128_ranges_heads: the table was built for %d heads, the call has %d" % (table_heads, heads))
+        raise AlgHipError("%s: the table was built for %d heads, the call has %d" % (what, table_heads, heads))
     lib = load_library()
     for t in (q, k, vt, o):
         _dev(t, "attention operand")
@@ -594,10 +626,17 @@ def flash_attn_d128_ranges_heads(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs,
     if lse is not None:
         _dev(lse, "lse")
         if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < lse_off + batch * heads * Sq:
-            raise AlgHipError("flash_attn_d128_ranges_heads: lse must be contiguous fp32 with room for [batch][heads][Sq]")
+            raise AlgHipError("%s: lse must be contiguous fp32 with room for [batch][heads][Sq]" % what)
         lse_p = c_void_p(lse.data_ptr() + 4 * lse_off)
     table = kv_ranges.on(q.device)
     at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
+    if order is not None:
+        ot = order.on(q.device)
+        _check(lib.alg_flash_attn_d128_ranges_order(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv,
+                                                    q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale), _ptr(table),
+                                                    kv_ranges.max_ranges, table_heads, lse_p, _ptr(ot), int(ot.numel()), _stream()),
+               "alg_flash_attn_d128_ranges_order")
+        return o
     _check(lib.alg_flash_attn_d128_ranges_heads(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv,
                                                 q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale), _ptr(table),
                                                 kv_ranges.max_ranges, table_heads, lse_p, _stream()),
@@ -1067,16 +1106,32 @@ def flash_attn_d64_ranges_heads(q, k, vt, o, batch, heads, S, q_bstride, q_rstri
     or one for all (a KvRanges), and, when `lse` is given (fp32, contiguous, batch * heads * S elements from lse_off), the
     log2-domain log-sum-exp of the pre-scaled scores over the keys each query visited (include/alg_hip.h:
     alg_flash_attn_d64_ranges_heads).  One launch: no split-KV tail, no workspace."""
+    return _ranges_heads_d64("flash_attn_d64_ranges_heads", None, q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride,
+                             vt_rstride, o_bstride, o_rstride, kv_ranges, lse, q_off, k_off, lse_off)
+
+
+def flash_attn_d64_ranges_order(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride,
+                                kv_ranges, order, lse=None, q_off=0, k_off=0, lse_off=0):
+    """flash_attn_d64_ranges_heads with its workgroups in the order `order` gives, an attn_window.LaunchOrder built for this
+    (batch, heads, ceil(S / 256)): only that type is taken.  The result is flash_attn_d64_ranges_heads' bit for bit
+    (include/alg_hip.h: alg_flash_attn_d64_ranges_order)."""
+    _order_check("flash_attn_d64_ranges_order", order, batch, heads, S)
+    return _ranges_heads_d64("flash_attn_d64_ranges_order", order, q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride,
+                             vt_rstride, o_bstride, o_rstride, kv_ranges, lse, q_off, k_off, lse_off)
+
+
+def _ranges_heads_d64(what, order, q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride,
+                      kv_ranges, lse, q_off, k_off, lse_off):
     from .attn_window import KvRanges, KvRangesHeads
     if not isinstance(kv_ranges, (KvRanges, KvRangesHeads)):
-        raise AlgHipError("flash_attn_d64_ranges_heads takes an attn_window.KvRanges or KvRangesHeads, got %s"
-                          % type(kv_ranges).__name__)
+        raise AlgHipError("%s takes an attn_window.KvRanges or KvRangesHeads, got %s"
+                          % (what, type(kv_ranges).__name__))
     if kv_ranges.Sq != S or kv_ranges.Skv != S:
-        raise AlgHipError("flash_attn_d64_ranges_heads: the table was built for Sq=%d Skv=%d, the call has Sq=Skv=%d"
-                          % (kv_ranges.Sq, kv_ranges.Skv, S))
+        raise AlgHipError("%s: the table was built for Sq=%d Skv=%d, the call has Sq=Skv=%d"
+                          % (what, kv_ranges.Sq, kv_ranges.Skv, S))
     table_heads = kv_ranges.heads if isinstance(kv_ranges, KvRangesHeads) else 1
     if table_heads not in (1, heads):
-        raise AlgHipError("flash_attn_d64_ranges_heads: the table was built for %d heads, the call has %d" % (table_heads, heads))
+        raise AlgHipError("%s: the table was built for %d heads, the call has %d" % (what, table_heads, heads))
     lib = load_library()
     for t in (q, k, vt, o):
         _dev(t, "attention operand")
@@ -1084,9 +1139,17 @@ def flash_attn_d64_ranges_heads(q, k, vt, o, batch, heads, S, q_bstride, q_rstri
     if lse is not None:
         _dev(lse, "lse")
         if lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() < lse_off + batch * heads * S:
-            raise AlgHipError("flash_attn_d64_ranges_heads: lse must be contiguous fp32 with room for [batch][heads][S]")
+            raise AlgHipError("%s: lse must be contiguous fp32 with room for [batch][heads][S]" % what)
         lse_p = c_void_p(lse.data_ptr() + 4 * lse_off)
     table = kv_ranges.on(q.device)
+    if order is not None:
+        ot = order.on(q.device)
+        _check(lib.alg_flash_attn_d64_ranges_order(c_void_p(q.data_ptr() + 2 * q_off), c_void_p(k.data_ptr() + 2 * k_off), _ptr(vt),
+                                                   _ptr(o), batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride,
+                                                   o_rstride, _ptr(table), kv_ranges.max_ranges, table_heads, lse_p, _ptr(ot),
+                                                   int(ot.numel()), _stream()),
+               "alg_flash_attn_d64_ranges_order")
+        return o
     _check(lib.alg_flash_attn_d64_ranges_heads(c_void_p(q.data_ptr() + 2 * q_off), c_void_p(k.data_ptr() + 2 * k_off), _ptr(vt),
                                                _ptr(o), batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride,
                                                o_rstride, _ptr(table), kv_ranges.max_ranges, table_heads, lse_p, _stream()),

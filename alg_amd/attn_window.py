@@ -20,9 +20,20 @@ softmax mass its latent queries keep inside the window -- and only the heads tha
     head_window_ranges   the window's rows for the windowed heads, the one full range for the others
     decide_heads         recall [samples][heads] -> windowed [heads]: the minimum over the samples reaches the threshold
 
+A launch order balanced by coverage (alg_flash_attn_d128_ranges_order, alg_flash_attn_d64_ranges_order; `attn_window_balance`).  A
+layer with dense and windowed heads holds units (head, query block) of very different cost, and the kernels' own order deals heads
+to the eight dispatch lanes by bh % 8, head-major.  The launch can take a static order instead, computed here once per table:
+
+    LaunchOrder          a validated order, uploaded once; the only thing the _order wrappers of _lib take
+    unit_costs           key tiles (+ SEGMENT_COST per range) of every unit of a table
+    balanced_order       "lanes" (heads whole to the least loaded lane, long units first), "units", "natural"
+
+Every workgroup computes what it computed before, so the output is bit-identical for every order.
+
 Only the policy is an approximation; its visual quality on a trained checkpoint is unmeasured (README), so it is off by default.
 """
 import math
+import time
 from types import SimpleNamespace
 
 import numpy as np
@@ -31,6 +42,9 @@ import torch
 Q_BLOCK = 256      # queries per workgroup of attention128_q64.hip and of attention.hip
 KV_ALIGN = 64      # their key tile: a range begins on the dense kernel's tile grid
 MAX_RANGES = 4
+LANES = 8          # workgroups b with the same b % 8 share a dispatch lane (an XCD, as observed: the kernels' bh % 8 rule)
+SEGMENT_COST = 2   # cost of a key range beyond its tiles, in key tiles: see unit_costs
+ORDER_POLICIES = ("lanes", "units", "natural")
 
 
 class KvRanges:
@@ -127,6 +141,142 @@ class KvRangesHeads:
 
     on = KvRanges.on
     device_table = KvRanges.device_table
+
+
+class LaunchOrder:
+    """A launch order for the ranged attention entries: a CPU int32 vector whose entry b is the unit bh * q_blocks + qb that
+    workgroup b runs, or -1 for a workgroup that exits.  Validated on the CPU: the length is a multiple of 8, every unit in
+    [0, batch * heads * q_blocks) occurs exactly once, every other entry is -1.  ValueError names the rule and the first
+    offending entry."""
+
+    def __init__(self, order, batch, heads, q_blocks):
+        t = torch.as_tensor(order)
+        if t.dtype != torch.int32 or t.dim() != 1 or t.device.type != "cpu":
+            raise ValueError("LaunchOrder takes a CPU int32 vector, got %s %s" % (t.dtype, tuple(t.shape)))
+        batch, heads, q_blocks = int(batch), int(heads), int(q_blocks)
+        if batch < 1 or heads < 1 or q_blocks < 1:
+            raise ValueError("LaunchOrder needs batch, heads, q_blocks >= 1 (got %d, %d, %d)" % (batch, heads, q_blocks))
+        n, units = int(t.numel()), batch * heads * q_blocks
+        if n == 0 or n % LANES:
+            raise ValueError("the order's length %d is not a multiple of %d" % (n, LANES))
+        a = t.numpy().astype(np.int64)
+        bad = np.nonzero((a < -1) | (a >= units))[0]
+        if bad.size:
+            raise ValueError("entry %d is %d: out of range (a unit in [0, %d) or -1)" % (bad[0], a[bad[0]], units))
+        at = np.nonzero(a >= 0)[0]                       # the entries that hold a unit, in entry order
+        count = np.bincount(a[at], minlength=units)
+        if (count > 1).any():
+            _, first = np.unique(a[at], return_index=True)            # the first entry of every unit
+            again = np.setdiff1d(np.arange(at.size), first)
+            i = at[again[0]]
+            raise ValueError("entry %d: duplicate unit %d (first at entry %d; every unit occurs exactly once)"
+                             % (i, a[i], at[np.nonzero(a[at] == a[i])[0][0]]))
+        missing = np.nonzero(count == 0)[0]
+        if missing.size:
+            raise ValueError("missing unit %d (bh %d, q block %d): every unit in [0, %d) occurs exactly once"
+                             % (missing[0], missing[0] // q_blocks, missing[0] % q_blocks, units))
+        self.order = t.clone().contiguous()
+        self.batch, self.heads, self.q_blocks = batch, heads, q_blocks
+        self._device = {}
+
+    def on(self, device):
+        """The order on `device`, uploaded once per device (outside any stream capture, like KvRanges.on)."""
+        device = torch.device(device)
+        dev = torch.cuda.current_device() if device.index is None else device.index
+        t = self._device.get(dev)
+        if t is None:
+            t = self._device[dev] = self.order.to(torch.device("cuda", dev))
+        return t
+
+    @property
+    def device_table(self):
+        """The order on the current device."""
+        return self.on("cuda")
+
+    def __len__(self):
+        return int(self.order.numel())
+
+
+def unit_costs(kv_ranges, batch, heads):
+    """The cost [batch * heads][q_blocks] (a list of lists of ints) of every unit of a launch with the table `kv_ranges`, a
+    KvRanges (one table for every head) or a KvRangesHeads built for `heads`: for the unit's table row the sum over its used
+    ranges of ceil((end - begin) / 64) key tiles, plus SEGMENT_COST per used range.
+
+    SEGMENT_COST (2 tiles) stands for what a range costs beyond its steady-state tiles -- priming the ring and the C++ tile 0.
+    Nobody has measured it.  Only the ORDER that results from the costs matters (balanced_order sorts and sums them), not their
+    scale, and a range is a small part of a unit wherever the window is worth having."""
+    if isinstance(kv_ranges, KvRangesHeads):
+        if kv_ranges.heads != int(heads):
+            raise ValueError("unit_costs: the table was built for %d heads, the launch has %d" % (kv_ranges.heads, heads))
+    elif not isinstance(kv_ranges, KvRanges):
+        raise ValueError("unit_costs takes a KvRanges or a KvRangesHeads, got %s" % type(kv_ranges).__name__)
+    if int(batch) < 1 or int(heads) < 1:
+        raise ValueError("unit_costs needs batch >= 1 and heads >= 1 (got %d, %d)" % (batch, heads))
+    a = kv_ranges.table.numpy().astype(np.int64)          # [q_blocks][max_ranges][2], or with a leading head dimension
+    used = a[..., 1] > a[..., 0]
+    tiles = (a[..., 1] - a[..., 0] + KV_ALIGN - 1) // KV_ALIGN
+    per_head = ((tiles + SEGMENT_COST) * used).sum(axis=-1)          # [q_blocks] or [heads][q_blocks]
+    if per_head.ndim == 1:
+        per_head = np.broadcast_to(per_head, (int(heads), per_head.shape[0]))
+    return np.tile(per_head, (int(batch), 1)).tolist()               # row bh = b * heads + h
+
+
+def balanced_order(costs, policy="lanes", heads=None):
+    """A LaunchOrder for units of cost costs[bh][qb] (unit_costs), laid out so that entry b belongs to lane b & 7.  `heads` (default:
+    all of costs' rows, batch 1) only labels the LaunchOrder: a unit's index depends on batch * heads alone.
+
+        "lanes"    heads bh are assigned whole to the lane with the least load so far, in descending order of head cost (ties:
+                   the lower bh, the lower lane); each lane's units are then sorted by descending cost (ties: (bh, qb) ascending)
+                   and the lanes padded with -1 at the end to the longest.  A head stays on one lane, as in the kernels' own
+                   order (the K / V^T locality that bh % 8 gives).
+        "units"    all units sorted by descending cost (ties: (bh, qb)) and dealt round-robin over the lanes: the better
+                   schedule in a list-scheduling model, at the price of the head-to-lane affinity.
+        "natural"  the kernels' own mapping as a table (bh = (b >> 3) // q_blocks * 8 + (b & 7), qb = (b >> 3) % q_blocks): for
+                   tests and for pricing the indirection."""
+    costs = [list(row) for row in costs]
+    if not costs or not costs[0] or any(len(r) != len(costs[0]) for r in costs):
+        raise ValueError("balanced_order takes costs[batch * heads][q_blocks] with at least one unit")
+    if policy not in ORDER_POLICIES:
+        raise ValueError("balanced_order: policy must be one of %s, got %r" % (", ".join(ORDER_POLICIES), policy))
+    nbh, qn = len(costs), len(costs[0])
+    C = np.asarray(costs, dtype=np.int64)
+    by_cost = lambda units: units[np.lexsort((units, -C.reshape(-1)[units]))]      # descending cost, ties by (bh, qb) ascending
+    if policy == "natural":
+        b = np.arange((nbh + LANES - 1) // LANES * LANES * qn)
+        bh, qb = (b >> 3) // qn * LANES + (b & 7), (b >> 3) % qn
+        order = np.where(bh < nbh, bh * qn + qb, -1)
+    elif policy == "lanes":
+        head_cost = C.sum(axis=1)
+        load, heads_of = [0] * LANES, [[] for _ in range(LANES)]
+        for bh in np.lexsort((np.arange(nbh), -head_cost)).tolist():
+            x = min(range(LANES), key=lambda i: (load[i], i))
+            load[x] += int(head_cost[bh])
+            heads_of[x].append(bh)
+        order = np.full((max(len(h) for h in heads_of) * qn, LANES), -1, dtype=np.int64)
+        for x, hs in enumerate(heads_of):
+            if hs:
+                order[:len(hs) * qn, x] = by_cost((np.asarray(sorted(hs))[:, None] * qn + np.arange(qn)[None, :]).reshape(-1))
+        order = order.reshape(-1)
+    else:      # dealt round-robin over the lanes: entry i of the sorted list is on lane i % 8
+        order = np.full((nbh * qn + LANES - 1) // LANES * LANES, -1, dtype=np.int64)
+        order[:nbh * qn] = by_cost(np.arange(nbh * qn))
+    order = torch.from_numpy(order.astype(np.int32))
+    heads = nbh if heads is None else int(heads)
+    if heads < 1 or nbh % heads:
+        raise ValueError("balanced_order: %d rows of costs are no multiple of heads = %d" % (nbh, heads))
+    return LaunchOrder(order, nbh // heads, heads, qn)
+
+
+def _balance_policy(value):
+    """attn_window_balance -> None (off), "lanes" or "units".  True is "units": the policy that won at most launch shapes when the
+    two were measured (profiles/attn_window_order_ab.json; README)."""
+    if value is False or value is None or value == 0:
+        return None
+    if value is True or value == 1:
+        return "units"
+    if value in ("lanes", "units"):
+        return value
+    raise ValueError("attn_window_balance must be False, True (= \"units\"), \"lanes\" or \"units\", got %r" % (value,))
 
 
 def head_window_ranges(base, windowed):
@@ -273,7 +423,13 @@ class HeadWindowHost:
                              keeps the window only where its measured recall reaches this value
         attn_window_stats    after a calibration forward one record per layer:
                              {"layer", "recall": [[per head] per sample], "windowed": [bool per head]}
-        reset_attn_window_heads()   forgets the decisions (the samplers call it at the start of a video)
+        attn_window_balance  False: off -- every launch is exactly what it is without the flag.  True (= "units"), "lanes" or "units":
+                             a calibrated layer whose table is per-head (dense AND windowed heads) launches the _order entry with a
+                             balanced_order of that policy; the output keeps its bits.  Needs attn_window_recall > 0
+                             Set it BEFORE the calibration forward where later forwards are captured: that forward builds the
+                             orders of its own batch size; any other (another batch size, a flag or policy changed later) is
+                             built on the first eager forward that needs it, and a capture that would have to build one raises
+        reset_attn_window_heads()   forgets the decisions and the launch orders (the samplers call it at the start of a video)
 
     With attn_window > 0 and attn_window_recall > 0 a forward is dense until the model is calibrated; the calibration forward is the
     one call_transformer(..., calibrate=True) marks.  Its self-attention output is the dense one (the ranged entry with the one
@@ -297,6 +453,9 @@ class HeadWindowHost:
         self._attn_head_tables = {}      # (base table id, windowed) -> KvRanges | KvRangesHeads | None
         self._attn_cal = None            # the calibration buffers, allocated on the first calibration forward only
         self._attn_full = {}             # (Sq, Skv) -> the one-full-range table of the calibration forward's dense launch
+        self.attn_window_balance = False
+        self.attn_window_order_build_seconds = 0.0     # host time spent building and uploading launch orders, since construction
+        self._attn_orders = {}           # (per-head table id, batch, policy) -> (table, LaunchOrder), next to _attn_head_tables
 
     @property
     def attn_window_calibrated(self):
@@ -305,6 +464,7 @@ class HeadWindowHost:
     def reset_attn_window_heads(self):
         self._attn_decided = None
         self._attn_head_tables = {}
+        self._attn_orders = {}
         self.attn_window_stats = []
 
     def _head_window_mode(self, key, layers, samples, heads, rows, o_shape):
@@ -312,7 +472,11 @@ class HeadWindowHost:
         "dense" (not calibrated, not asked to), "tables" (calibrated for `key`), or the calibration buffers (this IS the
         calibration forward).  `key`: what the decisions depend on (video shape, window, sink)."""
         thr = float(self.attn_window_recall)
+        policy = _balance_policy(self.attn_window_balance)
         if not thr > 0.0:
+            if policy is not None:
+                raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense "
+                                 "and windowed heads, which only the recall policy produces" % (self.attn_window_balance,))
             return None
         key = (key, thr)
         if self._attn_decided is not None and self._attn_decided[0] != key:
@@ -334,9 +498,11 @@ class HeadWindowHost:
         c.key = key
         return c
 
-    def _head_window_finish(self, c, bases):
+    def _head_window_finish(self, c, bases, batch=None):
         """End of the calibration forward: the recalls to the host (one copy, one synchronisation), decide_heads per layer, and
-        the per-head tables of `bases` (the window tables this forward used) built and uploaded."""
+        the per-head tables of `bases` (the window tables this forward used) built and uploaded -- with attn_window_balance, also
+        the launch order of every per-head table for launches of `batch` items (default: the forward's samples).  An order for
+        another batch size is built by _layer_order on the first eager forward that needs it."""
         c.host.copy_(c.recall, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         decided, stats = [], []
@@ -349,9 +515,12 @@ class HeadWindowHost:
             stats.append({"layer": li, "recall": rec, "windowed": windowed})
         self._attn_decided = (c.key, decided)
         self.attn_window_stats = stats
+        batch = c.shape[1] if batch is None else int(batch)
         for base in bases:
             for windowed in set(decided):
-                self._head_table(base, windowed)
+                t = self._head_table(base, windowed)
+                if isinstance(t, KvRangesHeads):
+                    self._layer_order(t, batch)
 
     def _head_full(self, Sq, Skv):
         if (Sq, Skv) not in self._attn_full:
@@ -371,6 +540,31 @@ class HeadWindowHost:
     def _layer_table(self, base, layer):
         """The table layer `layer` launches with once calibrated."""
         return self._head_table(base, self._attn_decided[1][layer])
+
+    def _layer_order(self, table, batch):
+        """The LaunchOrder a launch of `batch` items with the per-head table `table` takes under attn_window_balance, or None when
+        the flag is off: built and uploaded once per (table, batch, policy).  _head_window_finish builds the orders of the
+        calibration forward's batch size, so the forwards of that size behind it find theirs here and can be captured.  Any other
+        order -- another batch size (a sampler step with fewer passes than the calibration step), or a flag switched on or a
+        policy changed after the calibration -- is built on the first EAGER forward that asks for it; inside a stream capture a
+        missing order is an error, not an upload.  attn_window_order_build_seconds adds up the host time spent here."""
+        policy = _balance_policy(self.attn_window_balance)
+        if policy is None:
+            return None
+        k = (id(table), int(batch), policy)
+        if k not in self._attn_orders:
+            from . import _lib
+            if _lib._capturing():   # refused before anything is uploaded
+                raise _lib.AlgHipError("attn_window_balance: no launch order for batch %d and policy %r has been built yet, and "
+                                       "building one uploads a table, which cannot be captured into a graph -- set the flag "
+                                       "before the calibration forward and run one eager forward of this batch size first"
+                                       % (batch, policy))
+            t0 = time.perf_counter()
+            order = balanced_order(unit_costs(table, batch, table.heads), policy, heads=table.heads)
+            order.on(self.device)
+            self._attn_orders[k] = (table, order)     # (the table is held: its id stays its own)
+            self.attn_window_order_build_seconds += time.perf_counter() - t0
+        return self._attn_orders[k][1]
 
 
 def call_transformer(transformer, dense, *args, forward=None, calibrate=False, **kw):

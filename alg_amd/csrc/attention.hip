@@ -34,6 +34,8 @@
 //                                           (alg_flash_attn_d64_ranges: the opt-in frame window, off by default)
 //   flash_attn_d64_pipe_kernel<OFF, true, true>  ... that also write the log-sum-exp of the visited keys from an exact row sum
 //                                           (alg_flash_attn_d64_ranges_heads with an lse pointer: the calibration forward)
+//                                           Every RANGES = true instantiation also takes an optional launch-order table
+//                                           (alg_flash_attn_d64_ranges_order): workgroup b runs the unit order[b]
 //
 // Measured and removed (the sources are in the history, the records in profiles/r1_*, profiles/r3_attention_d64_pingpong.txt,
 // profiles/r3_attention_pipe_bench_ab.txt and docs/lab_notebook_r*.md).  MI355X, C2 shape (2 x 48 heads x 17,776 tokens),
@@ -90,6 +92,9 @@ struct AttnP {
   int use_statement;       // 0: every tile through the C++ tile body (ALG_ATTN_PP=0: the frame on its own)
   int head_rows;           // q_blocks when the table has a leading head dimension ([heads][q_blocks][max_ranges][2]), else 0
   float* lse;              // fp32 [batch][heads][S]: log2-domain log-sum-exp of the (pre-scaled) scores over the visited keys, or NULL
+  // alg_flash_attn_d64_ranges_order only (NULL and 0 from every other entry)
+  const int32_t* order;    // device int32 [order_len]: the unit bh * q_blocks + qb workgroup b runs (negative: it exits), or NULL
+  int order_len;           // = the grid
 };
 
 struct Frag {
@@ -523,7 +528,18 @@ __global__ __launch_bounds__(ATT_THREADS) void flash_attn_d64_pipe_kernel(const 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int nbh = p.batch * p.heads;
   int bh, qb;
-  {
+  bool ordered = false;
+  if constexpr (RANGES) ordered = p.order != nullptr;
+  if (ordered) {
+    // the launch order is data the host computed (attn_window.balanced_order): one wave-uniform load.  Defensive read: whatever
+    // the table holds, the workgroup runs a unit of this launch or none
+    const int bid = blockIdx.x;
+    if (bid >= p.order_len) return;
+    const int u = __builtin_amdgcn_readfirstlane(p.order[bid]);
+    if (u < 0 || u >= nbh * p.q_blocks) return;
+    bh = u / p.q_blocks;
+    qb = u - bh * p.q_blocks;
+  } else {
     const int bid = blockIdx.x;
     const int xcd = bid & 7;
     const int idx = bid >> 3;
@@ -947,6 +963,7 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
   p.unit0 = p.tail_units = p.tail_split = p.tail_tiles = 0;
   p.ws_o = p.ws_ml = nullptr;
   p.ranges = nullptr, p.max_ranges = 0, p.use_statement = 1, p.head_rows = 0, p.lse = nullptr;
+  p.order = nullptr, p.order_len = 0;
   const int nbh = batch * heads;
   // the split-KV tail runs only in a caller-provided workspace (alg_flash_attn_d64_workspace_bytes); without one the whole
   // problem is a single launch (same rows up to fp32 summation order in the tail units)
@@ -971,7 +988,8 @@ extern "C" int alg_flash_attn_d64_ex(const void* q, const void* k, const void* v
 // `what` names the caller in the error text.
 static int ranges64_entry(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
                           int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
-                          int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, void* stream) {
+                          int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse,
+                          const int32_t* order, int order_len, bool ordered, void* stream) {
   const int rc = attn64_check(q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride);
   if (rc != ALG_OK) {
     set_error("%s: the operands fail the checks of alg_flash_attn_d64 (batch=%d heads=%d S=%d; q/k/vt "
@@ -1007,10 +1025,21 @@ static int ranges64_entry(const char* what, const void* q, const void* k, const 
   p.ranges = kv_ranges, p.max_ranges = max_ranges;
   p.head_rows = table_heads == 1 ? 0 : p.q_blocks;
   p.lse = lse;
-  const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
+  p.order = nullptr, p.order_len = 0;
+  int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
   if (grid > 0x7fffffff) {
     set_error("%s: grid too large (batch=%d heads=%d S=%d)", what, batch, heads, S);
     return ALG_EINVAL;
+  }
+  if (ordered) {   // alg_flash_attn_d64_ranges_order: the order table is the grid (the other entries pass NULL)
+    const int64_t units = (int64_t)batch * heads * p.q_blocks;
+    if (!order || ((uintptr_t)order & 3) || order_len <= 0 || order_len % 8 || (int64_t)order_len < units) {
+      set_error("%s: order must be a 4-byte aligned device int32[order_len] with order_len a multiple of 8 and at least "
+                "batch * heads * q_blocks = %lld (got %p, %d)", what, (long long)units, (const void*)order, order_len);
+      return ALG_EINVAL;
+    }
+    p.order = order, p.order_len = order_len;
+    grid = order_len;
   }
   attn64_launch_ranges((unsigned)grid, p, s);
   return check_launch(what);
@@ -1021,7 +1050,7 @@ extern "C" int alg_flash_attn_d64_ranges(const void* q, const void* k, const voi
                                          int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
                                          void* stream) {
   return ranges64_entry("alg_flash_attn_d64_ranges", q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride, vt_rstride,
-                        o_bstride, o_rstride, kv_ranges, max_ranges, 1, nullptr, stream);
+                        o_bstride, o_rstride, kv_ranges, max_ranges, 1, nullptr, nullptr, 0, false, stream);
 }
 
 // The same launch with a table row per (head, q block) when table_heads == heads, and the log-sum-exp output (include/alg_hip.h).
@@ -1030,5 +1059,15 @@ extern "C" int alg_flash_attn_d64_ranges_heads(const void* q, const void* k, con
                                                int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
                                                int table_heads, float* lse, void* stream) {
   return ranges64_entry("alg_flash_attn_d64_ranges_heads", q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride,
-                        vt_rstride, o_bstride, o_rstride, kv_ranges, max_ranges, table_heads, lse, stream);
+                        vt_rstride, o_bstride, o_rstride, kv_ranges, max_ranges, table_heads, lse, nullptr, 0, false, stream);
+}
+
+// The same launch in the order a device table gives: workgroup b runs the unit order[b] (include/alg_hip.h).  Every workgroup
+// computes what it computes in alg_flash_attn_d64_ranges_heads, so O and lse are that entry's bit for bit, for every order.
+extern "C" int alg_flash_attn_d64_ranges_order(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                                               int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                                               int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges,
+                                               int table_heads, float* lse, const int32_t* order, int order_len, void* stream) {
+  return ranges64_entry("alg_flash_attn_d64_ranges_order", q, k, vt, o, batch, heads, S, q_bstride, q_rstride, vt_bstride,
+                        vt_rstride, o_bstride, o_rstride, kv_ranges, max_ranges, table_heads, lse, order, order_len, true, stream);
 }

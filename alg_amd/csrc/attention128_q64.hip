@@ -25,6 +25,8 @@
 // the key ranges of its row of a device table one after the other, each as a panel of its own, with one drain of the ring between
 // two of them.  alg_flash_attn_d128_ranges_heads is the same instantiation with a table row per (head, q
 // block) and an optional output of the log2-domain log-sum-exp of the visited keys (the recall policy of attn_window.py).
+// alg_flash_attn_d128_ranges_order is that launch with its workgroups in an order the host computed (attn_window.balanced_order):
+// workgroup b runs the unit order[b] and computes what it computes in the other entries.
 //
 // DEFAULT for non-causal, ungrouped attention over at least POLICY_TILES KV tiles; ALG_ATTN128_Q64=0 switches it off (the
 // 32-query pipelined kernel takes over), =2 takes every call of at least MIN_TILES tiles (tests).
@@ -63,6 +65,9 @@ struct P {
   // RANGES, alg_flash_attn_d128_ranges_heads only (0 and NULL from the other entries; the dense instantiation reads neither)
   int head_rows;           // q_blocks when the table has a leading head dimension ([heads][q_blocks][max_ranges][2]), else 0
   float* lse;              // fp32 [batch][heads][Sq]: log2-domain log-sum-exp of the scaled scores over the visited keys, or NULL
+  // RANGES, alg_flash_attn_d128_ranges_order only (NULL and 0 from every other entry; the dense instantiation reads neither)
+  const int32_t* order;    // device int32 [order_len]: the unit bh * q_blocks + qb workgroup b runs (negative: it exits), or NULL
+  int order_len;           // = the grid
 };
 
 // RANGES = false: every key of the panel, ONE segment [0, Skv) -- the dense kernel.  RANGES = true: the workgroup's 256 queries
@@ -77,7 +82,18 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int nbh = p.batch * p.heads;
   int bh, qb;
-  {
+  bool ordered = false;
+  if constexpr (RANGES) ordered = p.order != nullptr;
+  if (ordered) {
+    // the launch order is data the host computed (attn_window.balanced_order): one wave-uniform load.  Defensive read: whatever
+    // the table holds, the workgroup runs a unit of this launch or none
+    const int bid = blockIdx.x;
+    if (bid >= p.order_len) return;
+    const int u = __builtin_amdgcn_readfirstlane(p.order[bid]);
+    if (u < 0 || u >= nbh * p.q_blocks) return;
+    bh = u / p.q_blocks;
+    qb = u - bh * p.q_blocks;
+  } else {
     const int bid = blockIdx.x;
     const int xcd = bid & 7, idx = bid >> 3;
     const int slot = idx / p.q_blocks;
@@ -367,7 +383,7 @@ template <bool RANGES>
 static int launch_q64(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
                       int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs, int64_t o_rs,
                       float scale, const int32_t* ranges, int max_ranges, int use_statement, hipStream_t stream,
-                      int table_heads = 1, float* lse = nullptr) {
+                      int table_heads = 1, float* lse = nullptr, const int32_t* order = nullptr, int order_len = 0) {
   using namespace a128q;
   // 31-bit BYTE offsets inside one (batch, head) for the DMA's lane offsets; V^T rows cover whole 64-key tiles
   if ((int64_t)(Skv + 64) * k_rs * 2 >= (1ll << 31) || (int64_t)129 * vt_rs * 2 >= (1ll << 31) ||
@@ -394,7 +410,10 @@ static int launch_q64(const char* what, const void* q, const void* k, const void
   p.max_ranges = max_ranges;
   p.head_rows = table_heads == 1 ? 0 : p.q_blocks;
   p.lse = lse;
-  const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
+  p.order = order;
+  p.order_len = order ? order_len : 0;
+  // an order table IS the grid: one workgroup per entry (ranges_entry has checked that it holds every unit's place)
+  const int64_t grid = order ? (int64_t)order_len : (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
   if (grid > 0x7fffffff) return 1;
   hipLaunchKernelGGL(flash_attn_d128_q64_kernel<RANGES>, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
   return check_launch(what);
@@ -423,7 +442,8 @@ using namespace alg;
 static int ranges_entry(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
                         int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride, int64_t vt_bstride,
                         int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, const int32_t* kv_ranges,
-                        int max_ranges, int table_heads, float* lse, void* stream) {
+                        int max_ranges, int table_heads, float* lse, const int32_t* order, int order_len, bool ordered,
+                        void* stream) {
   if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
     set_error("%s: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", what, batch, heads, Sq, Skv);
     return ALG_EINVAL;
@@ -451,9 +471,19 @@ static int ranges_entry(const char* what, const void* q, const void* k, const vo
     set_error("%s: vt row stride %lld must cover Skv rounded up to %d", what, (long long)vt_rstride, a128q::KVB);
     return ALG_EINVAL;
   }
+  if (ordered) {   // alg_flash_attn_d128_ranges_order: the order table is the grid (the other entries pass NULL)
+    const int64_t units = (int64_t)batch * heads * ((Sq + a128q::NW * a128q::QW - 1) / (a128q::NW * a128q::QW));
+    if (!order || ((uintptr_t)order & 3) || order_len <= 0 || order_len % 8 || (int64_t)order_len < units) {
+      set_error("%s: order must be a 4-byte aligned device int32[order_len] with order_len a multiple of 8 and at least "
+                "batch * heads * q_blocks = %lld (got %p, %d)", what, (long long)units, (const void*)order, order_len);
+      return ALG_EINVAL;
+    }
+  } else {
+    order = nullptr, order_len = 0;
+  }
   const int rc = launch_q64<true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
                                   vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
-                                  (hipStream_t)stream, table_heads, lse);
+                                  (hipStream_t)stream, table_heads, lse, order, order_len);
   if (rc == 1) {
     set_error("%s: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large", what);
     return ALG_ELIMIT;
@@ -466,7 +496,7 @@ extern "C" int alg_flash_attn_d128_ranges(const void* q, const void* k, const vo
                                           int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
                                           float scale, const int32_t* kv_ranges, int max_ranges, void* stream) {
   return ranges_entry("alg_flash_attn_d128_ranges", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride,
-                      vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, 1, nullptr, stream);
+                      vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, 1, nullptr, nullptr, 0, false, stream);
 }
 
 // The same launch with a table row per (head, q block) when table_heads == heads, and the log-sum-exp output (include/alg_hip.h).
@@ -476,7 +506,20 @@ extern "C" int alg_flash_attn_d128_ranges_heads(const void* q, const void* k, co
                                                 int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_ranges,
                                                 int table_heads, float* lse, void* stream) {
   return ranges_entry("alg_flash_attn_d128_ranges_heads", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
-                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, stream);
+                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, nullptr, 0,
+                      false, stream);
+}
+
+// The same launch in the order a device table gives: workgroup b runs the unit order[b] (include/alg_hip.h).  Every workgroup
+// computes what it computes in alg_flash_attn_d128_ranges_heads, so O and lse are that entry's bit for bit, for every order.
+extern "C" int alg_flash_attn_d128_ranges_order(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
+                                                int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride,
+                                                int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
+                                                int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_ranges,
+                                                int table_heads, float* lse, const int32_t* order, int order_len, void* stream) {
+  return ranges_entry("alg_flash_attn_d128_ranges_order", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
+                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, order,
+                      order_len, true, stream);
 }
 
 namespace alg {

@@ -131,7 +131,7 @@ class CogVideoXImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
                         scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False,
-                        step_cache=0.0, attn_window=0, attn_window_recall=0.0, **_):
+                        step_cache=0.0, attn_window=0, attn_window_recall=0.0, attn_window_balance=False, **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
@@ -140,11 +140,19 @@ class CogVideoXImageToVideoPipeline:
         switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default), `attn_window` > 0
         its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by default);
         `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost) and needs
-        `attn_window` > 0 (ValueError otherwise)."""
+        `attn_window` > 0 (ValueError otherwise); `attn_window_balance` (True = "units", "lanes", "units"; needs
+        attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
+        order (attn_window.balanced_order), bit-identical output."""
         import os
+
+        from .attn_window import _balance_policy
 
         if attn_window_recall and not int(attn_window) > 0:
             raise ValueError("attn_window_recall=%r needs attn_window > 0: the recall is that of a frame window" % (attn_window_recall,))
+        _balance_policy(attn_window_balance)
+        if attn_window_balance and not attn_window_recall:
+            raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
+                             "windowed heads" % (attn_window_balance,))
 
         from .autoencoder_kl_cogvideox import AutoencoderKLCogVideoX
         from .text_encoder_t5 import T5EncoderModel
@@ -160,6 +168,8 @@ class CogVideoXImageToVideoPipeline:
             transformer.attn_window = int(attn_window)
         if attn_window_recall:
             transformer.attn_window_recall = float(attn_window_recall)
+        if attn_window_balance:
+            transformer.attn_window_balance = attn_window_balance
         if vae is None and has("vae"):
             vae = AutoencoderKLCogVideoX.from_pretrained(model_path, device=device)
         if text_encoder is None and has("text_encoder"):

@@ -121,15 +121,23 @@ class HunyuanVideoImageToVideoPipeline:
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, text_encoder_2=None, tokenizer_2=None, image_processor=None,
                         device="cuda", fp8_attention=False, fp8=False, attn_window=0, attn_window_recall=0.0,
-                        **_):
+                        attn_window_balance=False, **_):
         """Local-disk loader of a diffusers-format HunyuanVideo-I2V directory (`run.py:68-90`): `transformer/`,
         `text_encoder/` (Llava-Llama-3) + `tokenizer/` + `image_processor/`, `text_encoder_2/` (CLIP-L text tower) +
         `tokenizer_2/`, `vae/`, `scheduler/`.  `fp8=True` loads the transformer with e4m3 block linears
         (HunyuanVideoTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.
         `attn_window` > 0 switches the transformer's frame-window joint attention on with that many latent frames on each side
         (alg_amd/attn_window.py; off by default); `attn_window_recall` > 0 keeps that window only on the heads whose measured
-        recall reaches it (attn_window.HeadWindowHost)."""
+        recall reaches it (attn_window.HeadWindowHost); `attn_window_balance` (True = "units", "lanes", "units"; needs
+        attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
+        order (attn_window.balanced_order), bit-identical output."""
         import os
+
+        from .attn_window import _balance_policy
+        _balance_policy(attn_window_balance)
+        if attn_window_balance and not attn_window_recall:
+            raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
+                             "windowed heads" % (attn_window_balance,))
 
         from .schedulers import FlowMatchEulerDiscreteScheduler
         from .text_encoder_clip import CLIPTextModel
@@ -144,6 +152,8 @@ class HunyuanVideoImageToVideoPipeline:
             transformer.attn_window = int(attn_window)
         if attn_window_recall:
             transformer.attn_window_recall = float(attn_window_recall)
+        if attn_window_balance:
+            transformer.attn_window_balance = attn_window_balance
         if text_encoder is None and has("text_encoder"):
             from .text_encoder_llava import LlavaForConditionalGeneration
             text_encoder = LlavaForConditionalGeneration.from_pretrained(model_path, device=device)

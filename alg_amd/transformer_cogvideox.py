@@ -441,6 +441,10 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             self._timed("attn_calib", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, c.o, *A, base, lse=c.lse_part, k_off=D)
             return self._timed("attn_calib", _lib.attn_lse_recall, c.lse_part, c.lse_full, c.recall, N * Hn, S, row0=T, rows=S - T,
                                out_off=layer * N * Hn)
+        order = self._layer_order(kvr, N) if isinstance(kvr, KvRangesHeads) else None      # attn_window_balance
+        if order is not None:
+            return self._timed("attn", _lib.flash_attn_d64_ranges_order, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad,
+                               S_pad, S * D, D, kvr, order, k_off=D)
         if isinstance(kvr, KvRangesHeads):
             return self._timed("attn", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad,
                                S_pad, S * D, D, kvr, k_off=D)

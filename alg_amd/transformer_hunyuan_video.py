@@ -569,6 +569,13 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                     _lib.attn_lse_recall(cal.lse_part, cal.lse_full, cal.recall, heads, J, row0=0, rows=S,      # latent queries only
                                          part_off=b * heads * J, full_off=b * heads * J, out_off=(bi * N + b) * heads)
                     continue
+                order = self._layer_order(kv_b, 1) if isinstance(kv_b, KvRangesHeads) else None      # attn_window_balance
+                if order is not None:
+                    _lib.flash_attn_d128_ranges_order(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
+                                                      J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
+                                                      order, q_off=b * J * 2 * D, k_off=b * J * 2 * D + D,
+                                                      vt_off=b * D * ws.J_pad, o_off=b * J * (D + M))
+                    continue
                 if isinstance(kv_b, KvRangesHeads):
                     _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
                                                       J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
@@ -745,7 +752,7 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                   strideR=J * D)
 
         if cal is not None:
-            self._head_window_finish(cal, kvr)
+            self._head_window_finish(cal, kvr, batch=1)   # (one launch per sample)
 
         # ---- output head: AdaLayerNormContinuous (scale | shift), projection, unpatchify ----
         G(ws.semb1, w.ada_out[0], ws.mod_out, N, 2 * D, D, D, D, 2 * D, bias=w.ada_out[1])

@@ -519,12 +519,16 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
                 if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
                     kvr = None if hwm == "dense" or cal is not None else self._layer_table(kvr0, li)
+                order = self._layer_order(kvr, N) if isinstance(kvr, KvRangesHeads) else None      # attn_window_balance
                 if cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
                     A = (N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale)
                     T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, *A, full, lse=cal.lse_full, k_off=D)
                     T("attn_calib", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, cal.o, *A, kvr0, lse=cal.lse_part, k_off=D)
                     T("attn_calib", _lib.attn_lse_recall, cal.lse_part, cal.lse_full, cal.recall, N * heads, S,
                       out_off=li * N * heads)
+                elif order is not None:
+                    T("attn_self", _lib.flash_attn_d128_ranges_order, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
+                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, order, k_off=D)
                 elif isinstance(kvr, KvRangesHeads):
                     T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
                       S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, k_off=D)

@@ -308,6 +308,25 @@ int alg_flash_attn_d64_ranges_heads(const void* q, const void* k, const void* vt
                                     int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, int table_heads,
                                     float* lse, void* stream);
 
+/* alg_flash_attn_d64_ranges_heads in a launch order the host computed: the d = 64 twin of alg_flash_attn_d128_ranges_order below
+ * (alg_amd/attn_window.py: LaunchOrder, balanced_order).  Same kernel, operands, checks and defensive reading of the table, one
+ * launch of order_len workgroups.
+ *   order     : DEVICE int32 [order_len], 4-byte aligned.  Entry b is the unit workgroup b runs, bh * q_blocks + qb with
+ *               bh = b_item * heads + h and q_blocks = ceil(S / 256), or a negative value for a workgroup that exits at once.
+ *   order_len : a multiple of 8, at least batch * heads * q_blocks (entries 8 i + x share dispatch lane x, as blocks 8 i + x of the
+ *               other entries do).
+ * A null or misaligned order, an order_len that is no multiple of 8 or smaller than batch * heads * q_blocks are ALG_EINVAL before
+ * any launch.  The kernel reads the entry defensively: a value outside [0, batch * heads * q_blocks) makes the workgroup exit, so no
+ * content of `order` makes it read or write outside the operands.  The order has to hold every unit exactly once for o (and lse) to
+ * be complete -- a unit that is missing leaves its rows unwritten, one that occurs twice is computed twice with the same bits;
+ * attn_window.LaunchOrder validates that on the host.  Every workgroup computes exactly what the workgroup of that unit computes in
+ * alg_flash_attn_d64_ranges_heads: o and lse are that entry's BIT FOR BIT for every valid order; only the time differs.
+ * Enqueue-only and allocation-free. */
+int alg_flash_attn_d64_ranges_order(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int S,
+                                    int64_t q_bstride, int64_t q_rstride, int64_t vt_bstride, int64_t vt_rstride,
+                                    int64_t o_bstride, int64_t o_rstride, const int32_t* kv_ranges, int max_ranges, int table_heads,
+                                    float* lse, const int32_t* order, int order_len, void* stream);
+
 /* wan:910-917 (WanTransformer3DModel self- and cross-attention, head_dim 128; diffusers WanAttnProcessor SDPA)
  * Same contract as alg_flash_attn_d64 with head_dim 128 and separate query / key lengths:
  *   q : element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d,  s < Sq
@@ -363,6 +382,28 @@ int alg_flash_attn_d128_ranges_heads(const void* q, const void* k, const void* v
                                      int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
                                      int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale,
                                      const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, void* stream);
+
+/* alg_flash_attn_d128_ranges_heads in a launch order the host computed (alg_amd/attn_window.py: LaunchOrder, balanced_order).  The
+ * other ranged entries map workgroup b to the unit (bh = (b >> 3) / q_blocks * 8 + (b & 7), qb = (b >> 3) % q_blocks): heads dealt
+ * to the eight dispatch lanes by bh % 8, units head-major.  With a per-head table a dense head's units cost several times a
+ * windowed head's, and that order neither starts the long units first nor evens out the lanes.  Here workgroup b runs unit
+ * order[b].  Same kernel, operands, checks and defensive reading of the table; one launch of order_len workgroups.
+ *   order     : DEVICE int32 [order_len], 4-byte aligned.  Entry b is bh * q_blocks + qb with bh = b_item * heads + h and
+ *               q_blocks = ceil(Sq / 256), or a negative value for a workgroup that exits at once.
+ *   order_len : a multiple of 8, at least batch * heads * q_blocks (entries 8 i + x share dispatch lane x).
+ * A null or misaligned order, an order_len that is no multiple of 8 or smaller than batch * heads * q_blocks are ALG_EINVAL before
+ * any launch; an order_len beyond the 31-bit grid is ALG_ELIMIT.  The kernel reads the entry defensively: a value outside
+ * [0, batch * heads * q_blocks) makes the workgroup exit, so no content of `order` makes it read or write outside the operands.
+ * The order has to hold every unit exactly once for o (and lse) to be complete -- a missing unit leaves its rows unwritten, one
+ * that occurs twice is computed twice with the same bits; attn_window.LaunchOrder validates that on the host.  Every workgroup
+ * computes exactly what the workgroup of that unit computes in alg_flash_attn_d128_ranges_heads: o and lse are that entry's BIT FOR
+ * BIT for every valid order; only the time differs.  No workgroup talks to another: the order is data.  Enqueue-only and
+ * allocation-free. */
+int alg_flash_attn_d128_ranges_order(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                                     int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
+                                     int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale,
+                                     const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, const int32_t* order,
+                                     int order_len, void* stream);
 
 /* Recall of a key subset from two lse outputs of alg_flash_attn_d128_ranges_heads or of alg_flash_attn_d64_ranges_heads (it knows
  * nothing of the head dimension) over the same queries (lse_part: the subset, lse_full: all keys), both fp32 [panels][Sq] with

@@ -4,6 +4,7 @@ run of this).  One job, arms alternated, package power and shader clock sampled 
     python scripts/attn_window_ab.py --out profiles/attn_window_ab.json [--only kernel|steps|accuracy]
     python scripts/attn_window_ab.py --family d64 --out profiles/attn_window_d64_ab.json [--only kernel|steps|accuracy]
     python scripts/attn_window_ab.py --family heads64 --out profiles/attn_window_heads_d64_ab.json [--only kernel|steps]
+    python scripts/attn_window_ab.py --family order --out profiles/attn_window_order_ab.json [--only kernel|steps]
 
   kernel    alg_flash_attn_d128 against alg_flash_attn_d128_ranges at the three launch shapes (C3 32,760 x 40 heads, C5 75,600 x 40,
             C4 119,056 queries x 118,848 keys x 24 heads): the dense entry (first and last arm: their distance is the job's spread),
@@ -35,6 +36,15 @@ entry on the window and the dense entry in its default form (split-KV tail on); 
 attn_window = 2, attn_window_recall = 0.9 between two runs with the window off (iteration 0 is the calibration forward), and record the
 recall minimum, mean and maximum next to the coverage.  No bound is set for any of them.
 
+--family order is the coverage-balanced launch order (profiles/attn_window_order_ab.json; alg_flash_attn_d128_ranges_order at the C3 /
+C5 / C4 launch shapes, alg_flash_attn_d64_ranges_order at C2, the half-coverage windows of the records above): all heads dense (first
+and last: the job's spread), all heads windowed, every second head dense through the existing entry (twice: their distance is what a
+gain has to exceed), through the new entry with the "natural" table (the price of the indirection) and with "lanes" and "units", three
+of four heads windowed with natural / "lanes" / "units", and the shared all-windowed table with "lanes" (reported only: the model
+predicts no gain).  Each mixed arm is set against 0.5 * (all dense + all windowed) of the same job, and as the fraction of the
+available saving it realises.  Its steps arms time iterations 0-1 of the bench workloads with attn_window_balance off / on / "lanes" /
+off in one process, attn_window_recall at the workload's recorded mean recall so that about half the heads window.  No bound is set.
+
 Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
 import argparse
 import gc
@@ -51,7 +61,8 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from alg_amd import _lib  # noqa: E402
-from alg_amd.attn_window import frame_window_ranges, full_ranges, head_window_ranges  # noqa: E402
+from alg_amd.attn_window import (balanced_order, frame_window_ranges, full_ranges, head_window_ranges,  # noqa: E402
+                                 unit_costs)
 
 BF = torch.bfloat16
 DEV = torch.device("cuda:0")
@@ -308,6 +319,162 @@ def kernel_arms_heads_d64(iters, window=2):
     return out
 
 
+def _order_arms(run_heads, run_order, win, full, batch, heads, iters):
+    """The arms of --family order for one launch shape.  run_heads(table) / run_order(table, order) -> a launch closure."""
+    half = head_window_ranges(win, [h % 2 == 0 for h in range(heads)])          # every second head dense
+    quarter = head_window_ranges(win, [h % 4 != 0 for h in range(heads)])       # three of four heads windowed
+    order = lambda t, policy: balanced_order(unit_costs(t, batch, heads), policy, heads=heads)
+    arms = [("all_dense_first", run_heads(full)), ("all_windowed", run_heads(win)),
+            ("half_dense_heads_entry_a", run_heads(half)),
+            ("half_dense_natural", run_order(half, order(half, "natural"))),
+            ("half_dense_lanes", run_order(half, order(half, "lanes"))),
+            ("half_dense_units", run_order(half, order(half, "units"))),
+            ("half_dense_heads_entry_b", run_heads(half)),
+            ("quarter_dense_natural", run_order(quarter, order(quarter, "natural"))),
+            ("quarter_dense_lanes", run_order(quarter, order(quarter, "lanes"))),
+            ("quarter_dense_units", run_order(quarter, order(quarter, "units"))),
+            ("all_windowed_lanes", run_order(win, order(win, "lanes"))),
+            ("all_dense_last", run_heads(full))]
+    out = {"coverage_window": win.coverage, "arms": {}}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        arms[0][1]()
+        torch.cuda.synchronize()
+    for label, fn in arms:
+        out["arms"][label] = timed(fn, iters)
+    ms = lambda k: out["arms"][k]["median_ms"]
+    d = out["all_dense_ms_mean"] = (ms("all_dense_first") + ms("all_dense_last")) / 2
+    w = ms("all_windowed")
+    out["all_dense_spread_ms"] = abs(ms("all_dense_first") - ms("all_dense_last"))
+    out["half_dense_natural_spread_ms"] = abs(ms("half_dense_heads_entry_a") - ms("half_dense_heads_entry_b"))
+    nat = out["half_dense_heads_entry_ms_mean"] = (ms("half_dense_heads_entry_a") + ms("half_dense_heads_entry_b")) / 2
+    out["indirection_cost_ms"] = ms("half_dense_natural") - nat
+    for label, dense_frac in [(k, 0.5) for k in out["arms"] if k.startswith("half_dense")] + \
+                             [(k, 0.25) for k in out["arms"] if k.startswith("quarter_dense")]:
+        ideal = dense_frac * d + (1.0 - dense_frac) * w        # what the mix costs when every head costs what it costs alone
+        r = out["arms"][label]
+        r["over_mean_of_both"] = r["median_ms"] / ideal
+        r["fraction_of_saving"] = (d - r["median_ms"]) / (d - ideal)
+    for k in ("lanes", "units"):
+        out["half_dense_%s_gain_ms" % k] = nat - ms("half_dense_" + k)
+        out["half_dense_%s_is_a_gain" % k] = out["half_dense_%s_gain_ms" % k] > out["half_dense_natural_spread_ms"]
+        out["quarter_dense_%s_gain_ms" % k] = ms("quarter_dense_natural") - ms("quarter_dense_" + k)
+    out["all_windowed_lanes_minus_heads_entry_ms"] = ms("all_windowed_lanes") - w
+    return out
+
+
+def kernel_arms_order(name, iters):
+    F, hw, valid, rows, heads = SHAPES[name]
+    S, D = F * hw, heads * 128
+    Sq, Skv = S + rows, S + valid
+    pad = (Sq + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(Sq, 2 * D, generator=g, device=DEV, dtype=BF)
+    vt = torch.randn(D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(Sq, D, dtype=BF, device=DEV)
+    args = (qk, qk, vt, o, 1, heads, Sq, Skv, Sq * 2 * D, 2 * D, Sq * 2 * D, 2 * D, D * pad, pad, Sq * D, D, 1.0 / 128 ** 0.5)
+    w, win = window_for(F, hw, valid, rows, 0.5)
+
+    def run_heads(t):
+        t.device_table
+        return lambda: _lib.flash_attn_d128_ranges_heads(*args, t, k_off=D)
+
+    def run_order(t, order):
+        t.device_table, order.device_table
+        return lambda: _lib.flash_attn_d128_ranges_order(*args, t, order, k_off=D)
+
+    out = {"queries": Sq, "keys": Skv, "heads": heads, "frames": F, "tokens_per_frame": hw, "attn_window": w}
+    out.update(_order_arms(run_heads, run_order, win, full_ranges(Sq, Skv), 1, heads, iters))
+    del qk, vt, o
+    torch.cuda.empty_cache()
+    return out
+
+
+def kernel_arms_order_d64(iters, window=2):
+    S, D, N, heads = C2_T + C2_F * C2_HW, C2_HEADS * 64, C2_N, C2_HEADS
+    pad = (S + 127) // 128 * 128
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(N, S, 2 * D, generator=g, device=DEV, dtype=BF)
+    qk[:, :, :D] *= 0.125 * 1.4426950408889634                                # Q pre-scaled: the scores are in log2 units
+    vt = torch.randn(N, D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(N, S, D, dtype=BF, device=DEV)
+    args = (qk, qk, vt, o, N, heads, S, S * 2 * D, 2 * D, D * pad, pad, S * D, D)
+    win = frame_window_ranges(C2_F, C2_HW, window, prefix=C2_T)
+
+    def run_heads(t):
+        t.device_table
+        return lambda: _lib.flash_attn_d64_ranges_heads(*args, t, k_off=D)
+
+    def run_order(t, order):
+        t.device_table, order.device_table
+        return lambda: _lib.flash_attn_d64_ranges_order(*args, t, order, k_off=D)
+
+    out = {"samples": N, "tokens": S, "heads": heads, "frames": C2_F, "tokens_per_frame": C2_HW, "prompt_tokens": C2_T,
+           "attn_window": window}
+    out.update(_order_arms(run_heads, run_order, win, full_ranges(S, S), N, heads, iters))
+    del qk, vt, o
+    torch.cuda.empty_cache()
+    return out
+
+
+# the workloads' recorded mean recalls (profiles/attn_window_heads_ab.json, attn_window_heads_d64_ab.json): about half the heads window
+ORDER_RECALL = {"c3": 0.49, "c5": 0.49, "c4": 0.52, "c2": 0.43}
+
+
+def step_arms_order(workload, window=None):
+    if window is not None:
+        w_half = window
+    else:
+        F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
+        w_half = window_for(F, hw, valid, rows, 0.5)[0]
+    recall = ORDER_RECALL[workload]
+    args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
+    wl.build()
+    torch.cuda.synchronize()
+    wl.model.attn_window, wl.model.attn_window_recall = w_half, recall
+    out = {"attn_window": w_half, "attn_window_recall": recall, "arms": {}}
+    outs = {}
+    # (True is "units"; the "lanes" arm rides along so that the two policies are compared at step level too)
+    for label, flag in (("balance_off_first", False), ("balance_on", True), ("balance_lanes", "lanes"), ("balance_off_last", False)):
+        wl.model.attn_window_balance = flag
+        host0 = wl.model.attn_window_order_build_seconds
+        bench.run_steps(wl, 1)
+        torch.cuda.synchronize()
+        with bench.SmiSampler(0) as smi:
+            t0 = time.perf_counter()
+            bench.run_steps(wl, 2)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+        sm = smi.summary() or {}
+        outs[label] = wl.last_out.float().cpu()
+        st = wl.model.attn_window_stats
+        mixed = [rec for rec in st if 0 < sum(rec["windowed"]) < len(rec["windowed"])]
+        out["arms"][label] = {"attn_window_balance": flag, "seconds_two_steps": s,
+                              "finite": bool(torch.isfinite(wl.last_out.float()).all().item()),
+                              "layers_calibrated": len(st), "layers_mixed": len(mixed),
+                              "fraction_of_heads_windowed": (sum(sum(rec["windowed"]) for rec in st) /
+                                                             max(1, sum(len(rec["windowed"]) for rec in st))),
+                              "orders_cached": len(wl.model._attn_orders),
+                              # host time spent building and uploading launch orders in this arm, its warm-up iteration included;
+                              # what of it fell inside the two timed iterations is the calibration forward's share
+                              "policy": {False: None, True: "units"}.get(flag, flag),
+                              "order_build_host_seconds": wl.model.attn_window_order_build_seconds - host0,
+                              "power_w": (sm.get("power_w") or {}).get("mean"), "sclk_mhz": (sm.get("sclk_mhz") or {}).get("mean")}
+    a, b = out["arms"]["balance_off_first"]["seconds_two_steps"], out["arms"]["balance_off_last"]["seconds_two_steps"]
+    out["off_seconds_mean"], out["off_spread_seconds"] = (a + b) / 2, abs(a - b)
+    out["on_minus_off_seconds"] = out["arms"]["balance_on"]["seconds_two_steps"] - out["off_seconds_mean"]
+    out["lanes_minus_off_seconds"] = out["arms"]["balance_lanes"]["seconds_two_steps"] - out["off_seconds_mean"]
+    # (C4 draws fresh latents from its generator on every call: its runs are different videos)
+    fixed = "latents" in wl.kwargs
+    out["outputs_bit_identical"] = (bool(all(torch.equal(outs["balance_off_first"], o) for o in outs.values())) if fixed else None)
+    wl.model.attn_window, wl.model.attn_window_recall, wl.model.attn_window_balance = 0, 0.0, False
+    del wl, outs
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
 def accuracy_cog(frames=9, steps=4, layers=4):
     """A 4-step ALG sampler on the trained-like CogVideoX model at the medium grid (tests/helpers/trained_like_cases.py: 8 heads x
     64) with `layers` blocks, `frames` latent frames of 384 tokens behind 10 prompt tokens."""
@@ -486,10 +653,11 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64"], default="d128",
+    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64", "order"], default="d128",
                     help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2); heads: the per-head window chosen by recall (d = 128); "
-                         "heads64: the same for d = 64 (CogVideoX, C2)")
-    ap.add_argument("--workloads", default="c3,c5,c4", help="--family heads: the workloads of the steps arms")
+                         "heads64: the same for d = 64 (CogVideoX, C2); order: the coverage-balanced launch order (both head dims)")
+    ap.add_argument("--workloads", default="c3,c5,c4", help="--family heads / order: the workloads of the steps arms")
+    ap.add_argument("--shapes", default=",".join(list(SHAPES) + ["c2_2x48x17776"]), help="--family order: the kernel arms' launch shapes")
     a = ap.parse_args()
     parts = a.only or ["kernel", "accuracy", "steps"]
     res = {}
@@ -503,6 +671,21 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
 
+    if a.family == "order":
+        res["weights"] = ("synthetic Gaussian: which heads window on a trained checkpoint, and so the mix a layer has, is unmeasured; the "
+                          "kernel arms fix the mix (every second head dense, three of four windowed)")
+        if "kernel" in parts:
+            res.setdefault("kernel", {})
+            for name in a.shapes.split(","):
+                res["kernel"][name] = kernel_arms_order_d64(a.iters) if name.startswith("c2") else kernel_arms_order(name, a.iters)
+                save()
+        if "steps" in parts:
+            res.setdefault("steps", {})
+            for wlname in a.workloads.split(","):
+                res["steps"][wlname] = step_arms_order(wlname, window=2 if wlname == "c2" else None)
+                save()
+        print(json.dumps(res))
+        return
     if a.family == "heads64":
         res["weights"] = ("synthetic Gaussian: recall is about the coverage, so no head reaches a threshold above it; hit rates and "
                           "quality on a trained checkpoint are unmeasured")
