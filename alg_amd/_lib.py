@@ -36,6 +36,7 @@ EXPORTS = (
     "alg_layernorm_modulate_seg_fp8", "alg_quantize_fp8_rows_batched", "alg_step_cache_probe", "alg_step_cache_workspace_bytes",
     "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall", "alg_flash_attn_d64_ranges_heads",
     "alg_flash_attn_d128_ranges_order", "alg_flash_attn_d64_ranges_order",
+    "alg_flash_attn_d128_ranges_prefix", "alg_attn_prefix_mass",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -130,6 +131,9 @@ def load_library():
     lib.alg_flash_attn_d128_ranges_order.argtypes = ([c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 +
                                                      [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p])
     lib.alg_attn_lse_recall.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p]
+    lib.alg_flash_attn_d128_ranges_prefix.argtypes = ([c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 +
+                                                      [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p])
+    lib.alg_attn_prefix_mass.argtypes = [c_void_p] * 2 + [c_int] * 5 + [c_void_p]
     lib.alg_flash_attn_d128_ex.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
     lib.alg_flash_attn_d128_dual.argtypes = ([c_void_p] * 3 + [c_int] + [c_int64] * 4 + [c_void_p] * 2 + [c_int] + [c_int64] * 4 +
                                              [c_void_p] + [c_int] * 3 + [c_int64] * 4 + [c_float, c_void_p])
@@ -657,6 +661,56 @@ def attn_lse_recall(lse_part, lse_full, out, panels, Sq, row0=0, rows=None, part
     _check(load_library().alg_attn_lse_recall(c_void_p(lse_part.data_ptr() + 4 * part_off), c_void_p(lse_full.data_ptr() + 4 * full_off),
                                               c_void_p(out.data_ptr() + 8 * out_off), panels, Sq, row0, rows, _stream()),
            "alg_attn_lse_recall")
+    return out
+
+
+def flash_attn_d128_ranges_prefix(q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, scale, kv_segments,
+                                  lse_prefix, q_off=0, k_off=0, vt_off=0, o_off=0, prefix_off=0):
+    """flash_attn_d128_ranges_heads over kv_segments -- an attn_window.KvSegments (a partition of [0, Skv) into up to 12 segments
+    per block: the launch is the dense attention), or a KvRanges / KvRangesHeads -- which writes into `lse_prefix` (fp32,
+    contiguous, batch * heads * segments * Sq elements from prefix_off) the log2-domain log-sum-exp of the keys visited so far
+    behind every segment (include/alg_hip.h: alg_flash_attn_d128_ranges_prefix)."""
+    from .attn_window import KvRanges, KvRangesHeads, KvSegments
+    what = "flash_attn_d128_ranges_prefix"
+    if not isinstance(kv_segments, (KvSegments, KvRanges, KvRangesHeads)):
+        raise AlgHipError("%s takes an attn_window.KvSegments, KvRanges or KvRangesHeads, got %s" % (what, type(kv_segments).__name__))
+    if kv_segments.Sq != Sq or kv_segments.Skv != Skv:
+        raise AlgHipError("%s: the table was built for Sq=%d Skv=%d, the call has Sq=%d Skv=%d"
+                          % (what, kv_segments.Sq, kv_segments.Skv, Sq, Skv))
+    table_heads = kv_segments.heads if isinstance(kv_segments, KvRangesHeads) else 1
+    if table_heads not in (1, heads):
+        raise AlgHipError("%s: the table was built for %d heads, the call has %d" % (what, table_heads, heads))
+    segments = kv_segments.segments if isinstance(kv_segments, KvSegments) else kv_segments.max_ranges
+    lib = load_library()
+    for t in (q, k, vt, o):
+        _dev(t, "attention operand")
+    if lse_prefix is None:
+        raise AlgHipError("%s: lse_prefix is not optional" % what)
+    _dev(lse_prefix, "lse_prefix")
+    if (lse_prefix.dtype != torch.float32 or not lse_prefix.is_contiguous() or prefix_off < 0
+            or lse_prefix.numel() < prefix_off + batch * heads * segments * Sq):
+        raise AlgHipError("%s: lse_prefix must be contiguous fp32 with room for [batch][heads][%d][Sq]" % (what, segments))
+    table = kv_segments.on(q.device)
+    at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
+    _check(lib.alg_flash_attn_d128_ranges_prefix(at(q, q_off), at(k, k_off), at(vt, vt_off), at(o, o_off), batch, heads, Sq, Skv,
+                                                 q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs, o_rs, float(scale), _ptr(table),
+                                                 segments, table_heads, c_void_p(lse_prefix.data_ptr() + 4 * prefix_off), _stream()),
+           "alg_flash_attn_d128_ranges_prefix")
+    return o
+
+
+def attn_prefix_mass(lse_prefix, out, panels, segments, Sq, row0=0, rows=None, prefix_off=0, out_off=0):
+    """out[p][i] (float64, device) = mean over the rows [row0, row0 + rows) of exp2(P_i - P_last) - exp2(P_(i-1) - P_last) for the
+    `panels` panels of `segments` prefixes of Sq rows each: the softmax mass the queries have on the keys of segment i
+    (include/alg_hip.h: alg_attn_prefix_mass).  Offsets in elements."""
+    rows = Sq - row0 if rows is None else rows
+    for t, dt, n, off, name in ((lse_prefix, torch.float32, panels * segments * Sq, prefix_off, "lse_prefix"),
+                                (out, torch.float64, panels * segments, out_off, "out")):
+        _dev(t, name)
+        if t.dtype != dt or not t.is_contiguous() or off < 0 or t.numel() < off + n:
+            raise AlgHipError("attn_prefix_mass: %s must be contiguous %s with at least %d elements behind offset %d" % (name, dt, n, off))
+    _check(load_library().alg_attn_prefix_mass(c_void_p(lse_prefix.data_ptr() + 4 * prefix_off), c_void_p(out.data_ptr() + 8 * out_off),
+                                               panels, segments, Sq, row0, rows, _stream()), "alg_attn_prefix_mass")
     return out
 
 

@@ -30,6 +30,17 @@ to the eight dispatch lanes by bh % 8, head-major.  The launch can take a static
 
 Every workgroup computes what it computed before, so the output is bit-identical for every order.
 
+The window WIDTH per head from one calibration pass (head_dim 128: alg_flash_attn_d128_ranges_prefix, reduced by
+alg_attn_prefix_mass; `attn_window_widths`).  The ranged kernel runs a block's key ranges one after the other, so a launch over ALL
+keys, cut into nested rings around the block's own frames, yields the forward's attention output AND the softmax mass inside every
+candidate width; a head then takes the narrowest width that reaches the recall, else it stays dense:
+
+    KvSegments              a validated partition of [0, Skv) into up to 12 segments per block (the launch is the dense attention)
+    frame_profile_segments  the rings: sink | far left | left rings | core | right rings | far right | tail
+    width_segments          which segments count for which width
+    decide_widths           recall [samples][heads][widths] -> the width per head (0: dense)
+    head_width_ranges       the window's rows at each head's own width
+
 Only the policy is an approximation; its visual quality on a trained checkpoint is unmeasured (README), so it is off by default.
 """
 import math
@@ -39,6 +50,7 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+MAX_SEGMENTS = 12  # alg_flash_attn_d128_ranges_prefix: segments per block of a KvSegments
 Q_BLOCK = 256      # queries per workgroup of attention128_q64.hip and of attention.hip
 KV_ALIGN = 64      # their key tile: a range begins on the dense kernel's tile grid
 MAX_RANGES = 4
@@ -137,6 +149,58 @@ class KvRangesHeads:
         self.Skv, self.Sq = per_head[0].Skv, per_head[0].Sq
         self.q_blocks, self.max_ranges = per_head[0].q_blocks, per_head[0].max_ranges
         self.coverage = sum(r.coverage for r in per_head) / self.heads
+        self._device = {}
+
+    on = KvRanges.on
+    device_table = KvRanges.device_table
+
+
+class KvSegments:
+    """A table int32 [q_blocks][segments][2] of (begin, end) key indices whose non-empty entries PARTITION [0, Skv) in every
+    block, validated on the CPU: 1 <= segments <= 12; an entry with end <= begin is empty and may stand anywhere; the non-empty
+    entries of a block are ascending and disjoint, begin % 64 == 0, begin < end <= Skv, and together they cover [0, Skv) exactly
+    once -- so a launch over the table IS the dense attention, and the segment index means what the builder says in every block.
+    ValueError names the block and the rule.  The only table _lib.flash_attn_d128_ranges_prefix takes besides KvRanges(Heads)."""
+
+    def __init__(self, table, Skv, Sq):
+        t = torch.as_tensor(table)
+        if t.dtype != torch.int32 or t.dim() != 3 or t.shape[2] != 2 or t.device.type != "cpu":
+            raise ValueError("KvSegments takes a CPU int32 table [q_blocks][segments][2], got %s %s" % (t.dtype, tuple(t.shape)))
+        Skv, Sq = int(Skv), int(Sq)
+        if Sq < 1 or Skv < 1:
+            raise ValueError("KvSegments needs Sq >= 1 and Skv >= 1 (got %d, %d)" % (Sq, Skv))
+        q_blocks = (Sq + Q_BLOCK - 1) // Q_BLOCK
+        if t.shape[0] != q_blocks:
+            raise ValueError("the table has %d blocks, Sq=%d needs ceil(Sq / %d) = %d" % (t.shape[0], Sq, Q_BLOCK, q_blocks))
+        if not 1 <= t.shape[1] <= MAX_SEGMENTS:
+            raise ValueError("segments must be 1..%d, got %d" % (MAX_SEGMENTS, t.shape[1]))
+        a = t.numpy().astype(np.int64)
+        for j in range(q_blocks):
+            covered = 0        # the non-empty entries so far cover [0, covered)
+            for i in range(a.shape[1]):
+                b, e = int(a[j, i, 0]), int(a[j, i, 1])
+                if e <= b:
+                    continue
+                if b % KV_ALIGN:
+                    raise ValueError("block %d: begin %d of entry %d is not a multiple of %d" % (j, b, i, KV_ALIGN))
+                if b < 0:
+                    raise ValueError("block %d: entry %d (%d, %d) needs 0 <= begin < end" % (j, i, b, e))
+                if e > Skv:
+                    raise ValueError("block %d: end %d of entry %d is beyond Skv = %d" % (j, e, i, Skv))
+                if b < covered:
+                    raise ValueError("block %d: entry %d (%d, %d) is not sorted behind / overlaps the entry ending at %d"
+                                     % (j, i, b, e, covered))
+                if b > covered:
+                    raise ValueError("block %d: the keys [%d, %d) in front of entry %d are in no segment (the entries partition "
+                                     "[0, Skv))" % (j, covered, b, i))
+                covered = e
+            if covered != Skv:
+                raise ValueError("block %d: the keys [%d, %d) are in no segment (the entries partition [0, Skv))" % (j, covered, Skv))
+        self.table = t.clone().contiguous()
+        self.Skv, self.Sq = Skv, Sq
+        self.q_blocks, self.segments = q_blocks, int(t.shape[1])
+        self.max_ranges = self.segments
+        self.coverage = 1.0
         self._device = {}
 
     on = KvRanges.on
@@ -312,6 +376,162 @@ def decide_heads(recall, threshold):
     return out
 
 
+def _widths_tuple(widths, what):
+    """`widths` (a sequence of ints, or the string "1,2,4") as a strictly ascending tuple of positive ints; ValueError otherwise."""
+    if isinstance(widths, str):
+        try:
+            widths = tuple(int(x) for x in widths.split(","))
+        except ValueError:
+            raise ValueError("%s: %r is no comma-separated list of ints" % (what, widths)) from None
+    try:
+        ws = tuple(widths)
+    except TypeError:
+        raise ValueError("%s must be a sequence of ints, got %r" % (what, widths)) from None
+    if (not ws or any(isinstance(w, bool) or not isinstance(w, (int, np.integer)) for w in ws) or ws[0] < 1
+            or any(b <= a for a, b in zip(ws, ws[1:]))):
+        raise ValueError("%s must be a strictly ascending tuple of positive ints, got %r" % (what, widths))
+    if 2 * len(ws) + 3 > MAX_SEGMENTS:
+        raise ValueError("%s: %d widths need %d segments, the kernel takes %d (at most %d widths)"
+                         % (what, len(ws), 2 * len(ws) + 3, MAX_SEGMENTS, (MAX_SEGMENTS - 3) // 2))
+    return tuple(int(w) for w in ws)
+
+
+def _ascending(values):
+    """values with every entry raised to its predecessor's (a running maximum; NaN entries stay and are skipped over)."""
+    out = []
+    for v in values:
+        out.append(max(v, out[-1]) if out and not math.isnan(v) and not math.isnan(out[-1]) else v)
+    return out
+
+
+def width_segments(k):
+    """For a frame_profile_segments table of k widths: per width index j the segment indices whose mass counts for width j --
+    sink (0), tail (2k + 2), core (k + 1) and the rings 2 .. j + 1 on both sides (left ring r at k - r + 2, right ring r at k + r)."""
+    k = int(k)
+    out = []
+    for j in range(1, k + 1):
+        idx = [0, k + 1, 2 * k + 2]
+        for r in range(2, j + 1):
+            idx += [k - r + 2, k + r]
+        out.append(sorted(idx))
+    return out
+
+
+def frame_profile_segments(frames, tokens_per_frame, widths, sink_frames=1, tail=None, rows=None):
+    """The keys of frame_window_ranges' layout (no prefix) cut into 2k + 3 segments per block of 256 queries, k = len(widths), as a
+    KvSegments: a partition of [0, Skv), so the launch is the dense attention, and the segment index means the same in every block.
+    With f64(x) = x - x % 64, F = frames, hw = tokens_per_frame and a block covering the latent frames fa .. fb the cuts are
+
+        E_s = f64(min(sink, F) hw)
+        L_j = max(E_s, f64(max(fa - w_j, 0) hw))
+        R_j = T0 if min(fb + w_j + 1, F) == F else max(L_1, f64(min(fb + w_j + 1, F) hw))
+        T0  = f64(F hw) with a tail, else Skv
+
+    and the segments, in table order,
+
+        [0, E_s) sink | [E_s, L_k) far left | [L_k, L_(k-1)) .. [L_2, L_1) left rings | [L_1, R_1) core |
+        [R_1, R_2) .. [R_(k-1), R_k) right rings | [R_k, T0) far right | [T0, Skv) tail
+
+    (empty ones are stored as (0, 0)).  A block that holds any row >= F hw puts [0, Skv) into the core segment.  The mass counted
+    for width w_j is sink + tail + core + the rings 2 .. j on both sides (width_segments).
+
+    CONSERVATIVE ROUNDING.  Every cut lies on the 64-key grid, and the cuts are rounded so that for every block and every width
+    the counted key set is a SUBSET of what frame_window_ranges(..., window=w_j) visits (which rounds its begins DOWN and keeps its
+    ends), short by at most 126 keys; the two are equal where hw % 64 == 0 and there is no tail.  A recall measured on this table
+    is therefore a LOWER BOUND for the recall of the table that will be launched."""
+    F, hw, sink = int(frames), int(tokens_per_frame), int(sink_frames)
+    ws = _widths_tuple(widths, "frame_profile_segments: widths")
+    if F < 1 or hw < 1 or sink < 0:
+        raise ValueError("frame_profile_segments: frames=%d tokens_per_frame=%d sink_frames=%d" % (F, hw, sink))
+    k = len(ws)
+    S = F * hw
+    Sq = S if rows is None else int(rows)
+    f64 = lambda x: x - x % KV_ALIGN
+    if tail is not None:
+        tb, te = int(tail[0]), int(tail[1])
+        if not S <= tb < te:
+            raise ValueError("frame_profile_segments: tail (%d, %d) must lie behind the %d video keys and hold a key" % (tb, te, S))
+        Skv, T0 = te, f64(S)
+    else:
+        Skv = T0 = S
+    q_blocks = (Sq + Q_BLOCK - 1) // Q_BLOCK
+    t = torch.zeros(q_blocks, 2 * k + 3, 2, dtype=torch.int32)
+    for j in range(q_blocks):
+        r0, r1 = j * Q_BLOCK, min((j + 1) * Q_BLOCK, Sq) - 1
+        if r1 >= S:
+            t[j, k + 1, 0], t[j, k + 1, 1] = 0, Skv
+            continue
+        fa, fb = r0 // hw, r1 // hw
+        Es = f64(min(sink, F) * hw)
+        L = [max(Es, f64(max(fa - w, 0) * hw)) for w in ws]                              # L[0] = L_1 >= L_2 >= ... >= L_k >= E_s
+        R = [T0 if min(fb + w + 1, F) == F else max(L[0], f64(min(fb + w + 1, F) * hw)) for w in ws]      # R_1 <= ... <= R_k <= T0
+        cuts = [0, Es] + L[::-1] + R + [T0, Skv]                                         # 2k + 4 cuts, ascending
+        for i in range(2 * k + 3):
+            if cuts[i + 1] > cuts[i]:
+                t[j, i, 0], t[j, i, 1] = cuts[i], cuts[i + 1]
+    return KvSegments(t, Skv, Sq)
+
+
+def decide_widths(recall, widths, threshold):
+    """recall[sample][head][width index] (Python floats: the softmax mass head h's queries keep inside width w_j, per sample) ->
+    [int per head]: the smallest w_j whose recall reaches `threshold` on EVERY sample, else 0 (dense).  A head with a NaN gets 0."""
+    ws = _widths_tuple(widths, "decide_widths: widths")
+    rows = [[list(h) for h in r] for r in recall]
+    if (not rows or not rows[0] or any(len(r) != len(rows[0]) for r in rows)
+            or any(len(h) != len(ws) for r in rows for h in r)):
+        raise ValueError("decide_widths takes recall[samples][heads][%d widths] with at least one sample and one head" % len(ws))
+    thr = float(threshold)
+    out = []
+    for h in range(len(rows[0])):
+        vals = [[float(x) for x in r[h]] for r in rows]
+        chosen = 0
+        if not any(math.isnan(x) for v in vals for x in v):
+            for j, w in enumerate(ws):
+                if min(v[j] for v in vals) >= thr:
+                    chosen = w
+                    break
+        out.append(chosen)
+    return out
+
+
+def head_width_ranges(base_by_width, chosen):
+    """The per-head table of a layer whose heads chose their own width: head h gets the rows of base_by_width[chosen[h]] (the
+    frame_window_ranges table of that width; None where that window is the dense attention), or the one full range [(0, Skv)] for
+    chosen[h] == 0, zero-padded to the largest max_ranges among the tables in use.  The shared KvRanges when every head chose the
+    same width, None when every head is dense, a KvRangesHeads otherwise."""
+    chosen = [int(w) for w in chosen]
+    if not chosen:
+        raise ValueError("head_width_ranges: no head")
+    tables = {}
+    for w in set(chosen):
+        if w == 0:
+            tables[w] = None
+            continue
+        if w not in base_by_width:
+            raise ValueError("head_width_ranges: no table for the chosen width %d (have %s)" % (w, sorted(base_by_width)))
+        tables[w] = base_by_width[w]
+        if tables[w] is not None and not isinstance(tables[w], KvRanges):
+            raise ValueError("head_width_ranges takes KvRanges tables, got %s for width %d" % (type(tables[w]).__name__, w))
+    used = [t for t in tables.values() if t is not None]
+    if not used:
+        return None
+    if len(tables) == 1:
+        return used[0]
+    if any((t.Sq, t.Skv) != (used[0].Sq, used[0].Skv) for t in used):
+        raise ValueError("head_width_ranges: the tables were built for different (Sq, Skv)")
+    n = max(t.max_ranges for t in used)
+    full = torch.zeros(used[0].q_blocks, n, 2, dtype=torch.int32)
+    full[:, 0, 1] = used[0].Skv
+    padded = {}
+    for w, t in tables.items():
+        if t is None:
+            padded[w] = full
+        else:
+            padded[w] = torch.zeros_like(full)
+            padded[w][:, :t.max_ranges] = t.table
+    return KvRangesHeads(torch.stack([padded[w] for w in chosen]), used[0].Skv, used[0].Sq)
+
+
 def full_ranges(Sq, Skv):
     """The one-range table [0, Skv) for every block: the dense attention through the ranged entry."""
     q_blocks = (Sq + Q_BLOCK - 1) // Q_BLOCK
@@ -429,6 +649,12 @@ class HeadWindowHost:
                              Set it BEFORE the calibration forward where later forwards are captured: that forward builds the
                              orders of its own batch size; any other (another batch size, a flag or policy changed later) is
                              built on the first eager forward that needs it, and a capture that would have to build one raises
+        attn_window_widths   None: off -- calibration, tables and stats are exactly what they are without it.  A strictly ascending
+                             tuple of positive ints whose last element equals attn_window (or the string "1,2,4"; needs
+                             attn_window_recall > 0; head_dim 128 only): every head takes the NARROWEST of these widths that
+                             reaches the recall, else it stays dense, and the calibration is ONE launch per layer (below).  The
+                             stats records gain "recall_by_width": [[[per width] per head] per sample] and "width": [int per head]
+                             (0: dense); "recall" is the recall at the largest width, "windowed" is width > 0
         reset_attn_window_heads()   forgets the decisions and the launch orders (the samplers call it at the start of a video)
 
     With attn_window > 0 and attn_window_recall > 0 a forward is dense until the model is calibrated; the calibration forward is the
@@ -439,6 +665,15 @@ class HeadWindowHost:
     Later forwards launch, per layer, the dense entry (no head windowed), today's shared-table entry (every head) or
     alg_flash_attn_d128_ranges_heads (CogVideoX, head_dim 64: alg_flash_attn_d64_ranges_heads) with the layer's device-resident
     table: nothing on the host depends on the GPU any more, so they can be captured.
+
+    With attn_window_widths the calibration forward of a layer is one alg_flash_attn_d128_ranges_prefix launch over the
+    frame_profile_segments table (per sample in HunyuanVideo) into the REAL attention output -- the exact softmax over all keys,
+    in another fp32 summation grouping than the dense entry's, so that one forward is not bit-identical to the dense one
+    (docs/numerics.md) -- followed by one alg_attn_prefix_mass over the latent-query rows.  Neither a scratch output nor lse_part
+    is allocated.  The masses of the segments that count for a width (width_segments) are summed on the host into
+    recall[sample][head][width], decide_widths picks the width, head_width_ranges builds the layer's table.  The measured recall
+    is a lower bound of the launched table's (frame_profile_segments: conservative rounding).  Later forwards are launch for
+    launch what they are without the widths, with these tables.
 
     CogVideoX: the recall is taken over the latent-query rows [T, S) of the joint sequence (T prompt tokens first), and its dense
     entry may plan a split-KV tail, which the ranged entry never does: the calibration forward's attention output is the dense
@@ -456,10 +691,34 @@ class HeadWindowHost:
         self.attn_window_balance = False
         self.attn_window_order_build_seconds = 0.0     # host time spent building and uploading launch orders, since construction
         self._attn_orders = {}           # (per-head table id, batch, policy) -> (table, LaunchOrder), next to _attn_head_tables
+        self.attn_window_widths = None   # None: off; else the candidate widths (see the class docstring)
+        self._attn_width_bases = {}      # (table ids per width) -> {width: KvRanges | None}: what _head_table takes with widths
 
     @property
     def attn_window_calibrated(self):
         return self._attn_decided is not None
+
+    def _head_window_widths(self):
+        """attn_window_widths validated: None (off) or the tuple of candidate widths."""
+        if self.attn_window_widths is None:
+            return None
+        ws = _widths_tuple(self.attn_window_widths, "attn_window_widths")
+        if ws[-1] != int(self.attn_window):
+            raise ValueError("attn_window_widths %r: the last (largest) width must equal attn_window = %d"
+                             % (self.attn_window_widths, int(self.attn_window)))
+        if not float(self.attn_window_recall) > 0.0:
+            raise ValueError("attn_window_widths=%r needs attn_window_recall > 0: the width of a head is the narrowest that "
+                             "reaches the recall" % (self.attn_window_widths,))
+        return ws
+
+    def _head_width_bases(self, widths, make):
+        """{width: make(width)} (make: the model's cached frame_window_ranges table of that width, or None), the SAME dict for the
+        same tables: _head_table keys its cache by the dict's identity."""
+        tables = [make(w) for w in widths]
+        k = tuple(id(t) for t in tables)
+        if k not in self._attn_width_bases:
+            self._attn_width_bases[k] = dict(zip(widths, tables))     # (the tables are held: their ids stay their own)
+        return self._attn_width_bases[k]
 
     def reset_attn_window_heads(self):
         self._attn_decided = None
@@ -473,22 +732,32 @@ class HeadWindowHost:
         calibration forward).  `key`: what the decisions depend on (video shape, window, sink)."""
         thr = float(self.attn_window_recall)
         policy = _balance_policy(self.attn_window_balance)
+        widths = self._head_window_widths()
         if not thr > 0.0:
             if policy is not None:
                 raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense "
                                  "and windowed heads, which only the recall policy produces" % (self.attn_window_balance,))
             return None
-        key = (key, thr)
+        key = (key, thr) if widths is None else (key, thr, widths)
         if self._attn_decided is not None and self._attn_decided[0] != key:
-            self.reset_attn_window_heads()       # another video shape, window, sink or threshold: the decisions do not carry over
+            self.reset_attn_window_heads()       # another video shape, window, sink, threshold or widths: the decisions do not carry over
         if self._attn_decided is not None:
             return "tables"
         if not self._attn_calibrate:
             return "dense"
         c = self._attn_cal
-        shape = (layers, samples, heads, rows, tuple(o_shape))
+        shape = (layers, samples, heads, rows, tuple(o_shape), widths)
+        if widths is not None:     # one pass: the prefixes of one layer and the masses of all; no scratch output, no lse_part
+            if c is None or c.shape != shape:
+                c = self._attn_cal = SimpleNamespace(shape=shape, widths=widths, segments=2 * len(widths) + 3)
+                dev = self.device
+                c.prefix = torch.empty(samples, heads, c.segments, rows, dtype=torch.float32, device=dev)
+                c.mass = torch.zeros(layers, samples, heads, c.segments, dtype=torch.float64, device=dev)
+                c.host = torch.zeros(layers, samples, heads, c.segments, dtype=torch.float64).pin_memory()
+            c.key = key
+            return c
         if c is None or c.shape != shape:
-            c = self._attn_cal = SimpleNamespace(shape=shape)
+            c = self._attn_cal = SimpleNamespace(shape=shape, widths=None)
             dev = self.device
             c.lse_full = torch.empty(samples, heads, rows, dtype=torch.float32, device=dev)
             c.lse_part = torch.empty(samples, heads, rows, dtype=torch.float32, device=dev)
@@ -502,11 +771,24 @@ class HeadWindowHost:
         """End of the calibration forward: the recalls to the host (one copy, one synchronisation), decide_heads per layer, and
         the per-head tables of `bases` (the window tables this forward used) built and uploaded -- with attn_window_balance, also
         the launch order of every per-head table for launches of `batch` items (default: the forward's samples).  An order for
-        another batch size is built by _layer_order on the first eager forward that needs it."""
-        c.host.copy_(c.recall, non_blocking=True)
+        another batch size is built by _layer_order on the first eager forward that needs it.
+
+        With attn_window_widths: `bases` are the {width: table} dicts of _head_width_bases, the copy brings the segment masses,
+        which are summed per width (width_segments; clipped to 1 like the recall), and decide_widths picks every head's width."""
+        c.host.copy_(c.mass if c.widths is not None else c.recall, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         decided, stats = [], []
-        for li, rec in enumerate(c.host.tolist()):
+        if c.widths is not None:
+            counted = width_segments(len(c.widths))
+            for li, layer in enumerate(c.host.tolist()):
+                # (clipped to 1 like the recall; a ring's mass is the difference of two roundings and may come out below 0 by an
+                # ulp of its prefix, so a width never reports less than the narrower one; NaN stays NaN)
+                by_width = [[_ascending([min(sum(m[i] for i in idx), 1.0) for idx in counted]) for m in sample] for sample in layer]
+                chosen = decide_widths(by_width, c.widths, self.attn_window_recall)
+                decided.append(tuple(chosen))
+                stats.append({"layer": li, "recall": [[h[-1] for h in sample] for sample in by_width],
+                              "windowed": [w > 0 for w in chosen], "recall_by_width": by_width, "width": chosen})
+        for li, rec in enumerate([] if c.widths is not None else c.host.tolist()):
             # a recall is a fraction of softmax mass: where the window holds all of it, the two fp32 LSEs may differ by an ulp
             # the wrong way round (1 + 2e-7 seen), which is clipped here; NaN stays NaN
             rec = [[min(x, 1.0) for x in row] for row in rec]
@@ -528,10 +810,11 @@ class HeadWindowHost:
         return self._attn_full[(Sq, Skv)]
 
     def _head_table(self, base, windowed):
-        """head_window_ranges(base, windowed), built and uploaded once."""
+        """head_window_ranges(base, windowed), built and uploaded once -- or, with attn_window_widths, head_width_ranges(base,
+        widths chosen) for the {width: table} dict `base` of _head_width_bases."""
         k = (id(base), windowed)
         if k not in self._attn_head_tables:
-            t = head_window_ranges(base, windowed)
+            t = head_width_ranges(base, windowed) if isinstance(base, dict) else head_window_ranges(base, windowed)
             if t is not None:
                 t.on(self.device)
             self._attn_head_tables[k] = (base, t)     # (base is held: its id stays its own)

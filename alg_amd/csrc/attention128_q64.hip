@@ -27,6 +27,8 @@
 // block) and an optional output of the log2-domain log-sum-exp of the visited keys (the recall policy of attn_window.py).
 // alg_flash_attn_d128_ranges_order is that launch with its workgroups in an order the host computed (attn_window.balanced_order):
 // workgroup b runs the unit order[b] and computes what it computes in the other entries.
+// alg_flash_attn_d128_ranges_prefix is an instantiation of its own (PREFIX): the same frame over a table of up to 12 segments,
+// which writes the log-sum-exp of the keys visited SO FAR behind every segment (the one-pass calibration of attn_window.py).
 //
 // DEFAULT for non-causal, ungrouped attention over at least POLICY_TILES KV tiles; ALG_ATTN128_Q64=0 switches it off (the
 // 32-query pipelined kernel takes over), =2 takes every call of at least MIN_TILES tiles (tests).
@@ -68,13 +70,17 @@ struct P {
   // RANGES, alg_flash_attn_d128_ranges_order only (NULL and 0 from every other entry; the dense instantiation reads neither)
   const int32_t* order;    // device int32 [order_len]: the unit bh * q_blocks + qb workgroup b runs (negative: it exits), or NULL
   int order_len;           // = the grid
+  // PREFIX, alg_flash_attn_d128_ranges_prefix only (NULL from every other entry; no other instantiation reads it)
+  float* lse_prefix;       // fp32 [batch][heads][max_ranges][Sq]: entry i = the log-sum-exp over the keys of the segments 0 .. i
 };
 
 // RANGES = false: every key of the panel, ONE segment [0, Skv) -- the dense kernel.  RANGES = true: the workgroup's 256 queries
 // visit the key ranges of their row of p.ranges one after the other; each range is a SEGMENT the frame runs exactly as the dense
 // kernel runs a panel of that length whose K / V^T start at `begin` (prime the ring, tile 0 in C++, the statement from t = 1, the
-// tail in C++), with O, the running max and the row sum carried from segment to segment.
-template <bool RANGES>
+// tail in C++), with O, the running max and the row sum carried from segment to segment.  PREFIX (with RANGES): behind every
+// segment of the row, visited or skipped, the log-sum-exp of the keys visited so far goes to p.lse_prefix -- the epilogue's value,
+// taken from the running state, which it leaves as it is.  An instantiation of its own: <true, false> keeps its code.
+template <bool RANGES, bool PREFIX = false>
 __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* const k_ring = smem;
@@ -248,7 +254,23 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
   };
 
   bool visited = !RANGES;   // a segment has run: the ring holds its tiles and its clamped prefetches may still be in flight
+  // PREFIX: what the epilogue writes as lse, from the state behind segment `seg` (once per query: both h2 lanes hold l_tot and
+  // the same m_run); -inf while no key has been visited.  Called at the top of the NEXT segment's iteration
+  auto snapshot = [&](int seg) {
+    const LaneCtx x = make_ctx(fresh_lane());
+#pragma unroll
+    for (int qh = 0; qh < 2; ++qh) {
+      const float l_tot = l_run[qh] + __shfl_xor(l_run[qh], 32, 64);
+      const int q_row = x.q_row + 32 * qh;
+      if (q_row < Sq && x.h2 == 0)
+        p.lse_prefix[((int64_t)bh * p.max_ranges + seg) * Sq + q_row] =
+            visited ? m_run[qh] * c + __builtin_amdgcn_logf(l_tot) : -INFINITY;
+    }
+  };
   for (int seg = 0; seg < (RANGES ? p.max_ranges : 1); ++seg) {
+  if constexpr (PREFIX) {
+    if (seg > 0) snapshot(seg - 1);   // ONE site: a skipped segment comes by here as well; the last one is the epilogue's
+  }
   if constexpr (RANGES) {
     // defensive read: whatever the table holds, the segment lies inside the panel and starts on the dense kernel's tile grid
     // (the bit-2/3 column permutation and the 16-byte alignment of the V^T DMA hold for begin % 64 == 0 only)
@@ -369,6 +391,11 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
       if (p.lse != nullptr && q_row < Sq && x.h2 == 0)
         p.lse[(int64_t)bh * Sq + q_row] = visited ? m_run[qh] * c + __builtin_amdgcn_logf(l_tot) : -INFINITY;
     }
+    if constexpr (PREFIX) {   // the prefix behind the last segment: the lse above, to its place
+      if (q_row < Sq && x.h2 == 0)
+        p.lse_prefix[((int64_t)bh * p.max_ranges + p.max_ranges - 1) * Sq + q_row] =
+            visited ? m_run[qh] * c + __builtin_amdgcn_logf(l_tot) : -INFINITY;
+    }
   }
   if (tap && x.l31 == 0 && x.h2 == 0) {
     uint64_t* cp = p.clk + (size_t)(blockIdx.x >> 6) * 4;   // one workgroup owns a slot (block / 64 < slots)
@@ -379,11 +406,12 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
 }  // namespace a128q
 
 // Fills P and launches; 1 when the operands are beyond what the kernel addresses (31-bit byte offsets inside one (batch, head)).
-template <bool RANGES>
+template <bool RANGES, bool PREFIX = false>
 static int launch_q64(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
                       int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs, int64_t o_rs,
                       float scale, const int32_t* ranges, int max_ranges, int use_statement, hipStream_t stream,
-                      int table_heads = 1, float* lse = nullptr, const int32_t* order = nullptr, int order_len = 0) {
+                      int table_heads = 1, float* lse = nullptr, const int32_t* order = nullptr, int order_len = 0,
+                      float* lse_prefix = nullptr) {
   using namespace a128q;
   // 31-bit BYTE offsets inside one (batch, head) for the DMA's lane offsets; V^T rows cover whole 64-key tiles
   if ((int64_t)(Skv + 64) * k_rs * 2 >= (1ll << 31) || (int64_t)129 * vt_rs * 2 >= (1ll << 31) ||
@@ -393,7 +421,7 @@ static int launch_q64(const char* what, const void* q, const void* k, const void
   static PerDeviceOnce attr_set;
   const int dev_slot = current_device_slot();
   if (!device_done(attr_set, dev_slot)) {
-    if (hipFuncSetAttribute((const void*)flash_attn_d128_q64_kernel<RANGES>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    if (hipFuncSetAttribute((const void*)flash_attn_d128_q64_kernel<RANGES, PREFIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
                             LDS_BYTES) != hipSuccess)
       return 1;
     device_mark(attr_set, dev_slot);
@@ -412,10 +440,11 @@ static int launch_q64(const char* what, const void* q, const void* k, const void
   p.lse = lse;
   p.order = order;
   p.order_len = order ? order_len : 0;
+  p.lse_prefix = lse_prefix;
   // an order table IS the grid: one workgroup per entry (ranges_entry has checked that it holds every unit's place)
   const int64_t grid = order ? (int64_t)order_len : (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
   if (grid > 0x7fffffff) return 1;
-  hipLaunchKernelGGL(flash_attn_d128_q64_kernel<RANGES>, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
+  hipLaunchKernelGGL((flash_attn_d128_q64_kernel<RANGES, PREFIX>), dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
   return check_launch(what);
 }
 
@@ -443,13 +472,14 @@ static int ranges_entry(const char* what, const void* q, const void* k, const vo
                         int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride, int64_t vt_bstride,
                         int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, const int32_t* kv_ranges,
                         int max_ranges, int table_heads, float* lse, const int32_t* order, int order_len, bool ordered,
-                        void* stream) {
+                        void* stream, bool prefix = false, float* lse_prefix = nullptr) {
+  const int cap = prefix ? 12 : 4;   // alg_flash_attn_d128_ranges_prefix: the segments of a profile table
   if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
     set_error("%s: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", what, batch, heads, Sq, Skv);
     return ALG_EINVAL;
   }
-  if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > 4) {
-    set_error("%s: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..4 (got %p, %d)", what,
+  if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > cap) {
+    set_error("%s: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..%d (got %p, %d)", what, cap,
               (const void*)kv_ranges, max_ranges);
     return ALG_EINVAL;
   }
@@ -459,6 +489,11 @@ static int ranges_entry(const char* what, const void* q, const void* k, const vo
   }
   if ((uintptr_t)lse & 3) {
     set_error("%s: lse must be 4-byte aligned (got %p)", what, (const void*)lse);
+    return ALG_EINVAL;
+  }
+  if (prefix && (!lse_prefix || ((uintptr_t)lse_prefix & 3))) {
+    set_error("%s: lse_prefix must be a 4-byte aligned device buffer [batch][heads][max_segments][Sq] (got %p)", what,
+              (const void*)lse_prefix);
     return ALG_EINVAL;
   }
   if (q_rstride % 8 || q_bstride % 8 || k_rstride % 8 || k_bstride % 8 || vt_rstride % 8 || vt_bstride % 8 ||
@@ -481,9 +516,13 @@ static int ranges_entry(const char* what, const void* q, const void* k, const vo
   } else {
     order = nullptr, order_len = 0;
   }
-  const int rc = launch_q64<true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                                  vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
-                                  (hipStream_t)stream, table_heads, lse, order, order_len);
+  const int rc =
+      prefix ? launch_q64<true, true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
+                                      vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
+                                      (hipStream_t)stream, table_heads, nullptr, nullptr, 0, lse_prefix)
+             : launch_q64<true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
+                                vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
+                                (hipStream_t)stream, table_heads, lse, order, order_len);
   if (rc == 1) {
     set_error("%s: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large", what);
     return ALG_ELIMIT;
@@ -520,6 +559,18 @@ extern "C" int alg_flash_attn_d128_ranges_order(const void* q, const void* k, co
   return ranges_entry("alg_flash_attn_d128_ranges_order", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
                       k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, order,
                       order_len, true, stream);
+}
+
+// The same launch over a table of up to 12 segments, with the log-sum-exp of the keys visited so far written behind every segment
+// (include/alg_hip.h).  The last prefix is what alg_flash_attn_d128_ranges_heads writes as lse for the same table, bit for bit.
+extern "C" int alg_flash_attn_d128_ranges_prefix(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
+                                                 int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride,
+                                                 int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
+                                                 int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_segments,
+                                                 int table_heads, float* lse_prefix, void* stream) {
+  return ranges_entry("alg_flash_attn_d128_ranges_prefix", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
+                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_segments, table_heads, nullptr,
+                      nullptr, 0, false, stream, true, lse_prefix);
 }
 
 namespace alg {
@@ -561,8 +612,57 @@ __global__ __launch_bounds__(RECALL_THREADS) void lse_recall_kernel(const float*
   }
 }
 
+// Softmax mass per segment (alg_attn_prefix_mass): workgroup (panel, i) forms the mean over the rows [row0, row0 + rows) of
+// 2^(P_i - P_last) - 2^(P_(i-1) - P_last) from the prefixes [panels][segments][Sq] of alg_flash_attn_d128_ranges_prefix.  The
+// exponentials are taken in double (the masses of a row add up to exactly 2^0 minus what cancels, and a sum of them over the
+// segments of a width is compared against one); the reduction is lse_recall_kernel's: per lane in row order, then the lanes.
+__device__ inline double prefix_term(float pre, float last) {
+  return pre == -INFINITY ? 0.0 : exp2((double)pre - (double)last);
+}
+
+__global__ __launch_bounds__(RECALL_THREADS) void prefix_mass_kernel(const float* __restrict__ prefix, double* __restrict__ out,
+                                                                     int segments, int Sq, int row0, int rows) {
+  __shared__ double red[RECALL_THREADS / 64];
+  const int panel = blockIdx.x / segments, i = blockIdx.x - panel * segments;
+  const float* const last = prefix + ((int64_t)panel * segments + segments - 1) * Sq + row0;
+  const float* const cur = prefix + ((int64_t)panel * segments + i) * Sq + row0;
+  const float* const prev = i > 0 ? cur - Sq : nullptr;    // P_(-1) = -inf
+  double acc = 0.0;
+  for (int r = (int)threadIdx.x; r < rows; r += RECALL_THREADS) {
+    const float l = last[r];
+    acc += prefix_term(cur[r], l) - (prev ? prefix_term(prev[r], l) : 0.0);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double tot = 0.0;
+#pragma unroll
+    for (int w = 0; w < RECALL_THREADS / 64; ++w) tot += red[w];
+    out[blockIdx.x] = tot / (double)rows;
+  }
+}
+
 }  // namespace a128q
 }  // namespace alg
+
+extern "C" int alg_attn_prefix_mass(const float* lse_prefix, double* out, int panels, int segments, int Sq, int row0, int rows,
+                                    void* stream) {
+  if (!lse_prefix || !out || ((uintptr_t)lse_prefix & 3) || ((uintptr_t)out & 7)) {
+    set_error("alg_attn_prefix_mass: lse_prefix must be a 4-byte and out an 8-byte aligned device pointer");
+    return ALG_EINVAL;
+  }
+  if (panels <= 0 || segments < 1 || segments > 12 || Sq <= 0 || row0 < 0 || rows <= 0 || (int64_t)row0 + rows > Sq ||
+      (int64_t)panels * segments > 0x7fffffff) {
+    set_error("alg_attn_prefix_mass: bad argument (panels=%d segments=%d Sq=%d row0=%d rows=%d: segments in 1..12, the rows "
+              "inside [0, Sq))", panels, segments, Sq, row0, rows);
+    return ALG_EINVAL;
+  }
+  hipLaunchKernelGGL(a128q::prefix_mass_kernel, dim3((unsigned)(panels * segments)), dim3(a128q::RECALL_THREADS), 0,
+                     (hipStream_t)stream, lse_prefix, out, segments, Sq, row0, rows);
+  return check_launch("alg_attn_prefix_mass");
+}
 
 extern "C" int alg_attn_lse_recall(const float* lse_part, const float* lse_full, double* out, int panels, int Sq, int row0,
                                    int rows, void* stream) {

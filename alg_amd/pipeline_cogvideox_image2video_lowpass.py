@@ -131,7 +131,8 @@ class CogVideoXImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
                         scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False,
-                        step_cache=0.0, attn_window=0, attn_window_recall=0.0, attn_window_balance=False, **_):
+                        step_cache=0.0, attn_window=0, attn_window_recall=0.0, attn_window_balance=False, attn_window_widths=None,
+                        **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
@@ -142,11 +143,15 @@ class CogVideoXImageToVideoPipeline:
         `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost) and needs
         `attn_window` > 0 (ValueError otherwise); `attn_window_balance` (True = "units", "lanes", "units"; needs
         attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
-        order (attn_window.balanced_order), bit-identical output."""
+        order (attn_window.balanced_order), bit-identical output.  `attn_window_widths` (the per-head window WIDTH of the
+        head_dim 128 models) is refused: ValueError."""
         import os
 
         from .attn_window import _balance_policy
 
+        if attn_window_widths is not None:
+            raise ValueError("attn_window_widths=%r: the per-head window width (one-pass calibration) is not built for head_dim 64"
+                             % (attn_window_widths,))
         if attn_window_recall and not int(attn_window) > 0:
             raise ValueError("attn_window_recall=%r needs attn_window > 0: the recall is that of a frame window" % (attn_window_recall,))
         _balance_policy(attn_window_balance)

@@ -106,14 +106,16 @@ class WanImageToVideoPipeline:
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, image_encoder=None, image_processor=None, device="cuda",
                         fp8=False, fp8_attention=False, step_cache=0.0, attn_window=0, attn_window_recall=0.0,
-                        attn_window_balance=False, **_):
+                        attn_window_balance=False, attn_window_widths=None, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
         (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan).
         `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default);
         `attn_window` > 0 its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by
         default); `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost);
         `attn_window_balance` (True = "units", "lanes", "units"; needs attn_window_recall > 0, ValueError otherwise) launches the
-        layers with dense and windowed heads in a coverage-balanced order (attn_window.balanced_order), bit-identical output."""
+        layers with dense and windowed heads in a coverage-balanced order (attn_window.balanced_order), bit-identical output; `attn_window_widths`
+        (a strictly ascending tuple of positive ints ending in attn_window, or "1,2,4"; needs attn_window_recall > 0, ValueError
+        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration."""
         import os
 
         from .attn_window import _balance_policy
@@ -121,6 +123,15 @@ class WanImageToVideoPipeline:
         if attn_window_balance and not attn_window_recall:
             raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
                              "windowed heads" % (attn_window_balance,))
+        if attn_window_widths is not None:
+            from .attn_window import _widths_tuple
+            attn_window_widths = _widths_tuple(attn_window_widths, "attn_window_widths")
+            if attn_window_widths[-1] != int(attn_window):
+                raise ValueError("attn_window_widths %r: the last (largest) width must equal attn_window = %d"
+                                 % (attn_window_widths, int(attn_window)))
+            if not float(attn_window_recall) > 0.0:
+                raise ValueError("attn_window_widths=%r needs attn_window_recall > 0: the width of a head is the narrowest that "
+                                 "reaches the recall" % (attn_window_widths,))
 
         from .image_encoder_clip import CLIPImageProcessor, CLIPVisionModel
         from .schedulers import UniPCMultistepScheduler
@@ -139,6 +150,8 @@ class WanImageToVideoPipeline:
             transformer.attn_window_recall = float(attn_window_recall)
         if attn_window_balance:
             transformer.attn_window_balance = attn_window_balance
+        if attn_window_widths is not None:
+            transformer.attn_window_widths = attn_window_widths
         if text_encoder is None and has("text_encoder"):
             text_encoder = UMT5EncoderModel.from_pretrained(model_path, device=device)
         if tokenizer is None:

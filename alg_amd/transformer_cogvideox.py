@@ -142,7 +142,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         self._attn_ranges = {}    # (frames, hw, T, window, sink) -> KvRanges, or None where the window covers the whole video
         # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall reaches it keep the window
         # (attn_window.HeadWindowHost: attn_window_stats, reset_attn_window_heads).  0.0: the shared window, nothing allocated
-        self._head_window_init()
+        self._head_window_init()      # (attn_window_widths stays None: the property below refuses anything else)
         self._sincos = {}
         dev = self.device
         w = weights
@@ -405,6 +405,17 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         quant(h, F4)
         lin("gemm_ff2", L["wf28"], x, D, F4, D, bias=L["bf2"], R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
+
+    @property
+    def attn_window_widths(self):
+        """The per-head window WIDTH of the head_dim 128 models (attn_window.HeadWindowHost): always None here."""
+        return None
+
+    @attn_window_widths.setter
+    def attn_window_widths(self, value):
+        if value is not None:   # refused, not dropped: alg_flash_attn_d64_ranges_heads has no prefix form
+            raise ValueError("attn_window_widths=%r: the per-head window width (one-pass calibration) is not built for head_dim 64"
+                             % (value,))
 
     def _window_ranges(self, frames, hw, T):
         """The frame-window table of this sequence shape -- T prompt tokens, then `frames` latent frames of hw tokens -- device-

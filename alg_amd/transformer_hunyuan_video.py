@@ -36,7 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import HeadWindowHost, KvRangesHeads, frame_window_ranges
+from .attn_window import HeadWindowHost, KvRangesHeads, frame_profile_segments, frame_window_ranges
 from .transformer_wan import k_scale_bound
 
 BF = torch.bfloat16
@@ -409,10 +409,21 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
             for L in self.single:
                 self._quantize_block(L, self.FP8_SINGLE, drop_bf16=False)
 
-    def _window_ranges(self, frames, hw, valid, J):
+    def _profile_segments(self, frames, hw, valid, J, widths):
+        """The frame_profile_segments table of one sample of this video shape for attn_window_widths (device-resident, built once)."""
+        key = ("profile", frames, hw, valid, J, widths, int(self.attn_sink_frames))
+        if key not in self._attn_ranges:
+            S = frames * hw
+            self._attn_ranges[key] = frame_profile_segments(frames, hw, widths, sink_frames=int(self.attn_sink_frames),
+                                                            tail=(S, S + valid), rows=J)
+            self._attn_ranges[key].on(self.device)
+        return self._attn_ranges[key]
+
+    def _window_ranges(self, frames, hw, valid, J, window=None):
         """The frame-window table of one sample of this video shape (device-resident, built once per key: before any capture that
-        replays it), or None where the window is the dense attention.  Keys: frames * hw latent tokens, then `valid` prompt keys."""
-        window, sink = int(self.attn_window), int(self.attn_sink_frames)
+        replays it), or None where the window is the dense attention.  Keys: frames * hw latent tokens, then `valid` prompt keys.
+        window: attn_window, or one of attn_window_widths."""
+        window, sink = int(self.attn_window if window is None else window), int(self.attn_sink_frames)
         if window < 0 or sink < 0:
             raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
         if self.fp8_attention:
@@ -539,6 +550,11 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
             hwm = self._head_window_mode((F_, first, int(self.attn_window), int(self.attn_sink_frames)),
                                          len(self.dual) + len(self.single), N, heads, J, (N, J, D))
         cal = hwm if hwm not in (None, "dense", "tables") else None
+        kvr0 = kvr
+        widths = self._head_window_widths() if hwm is not None else None
+        if widths is not None:   # attn_window_widths: per sample the tables of every candidate width
+            kvr0 = [self._head_width_bases(widths, lambda w_, b=b: self._window_ranges(F_, first, valid[b], J, window=w_))
+                    for b in range(N)]
 
         def attention(bi=0):
             """bi: index of the block in dual + single order (its K scales, fp8_attention)."""
@@ -558,7 +574,16 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                     continue
                 kv_b = kvr[b]
                 if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
-                    kv_b = None if hwm == "dense" or cal is not None else self._layer_table(kvr[b], bi)
+                    kv_b = None if hwm == "dense" or cal is not None else self._layer_table(kvr0[b], bi)
+                if cal is not None and widths is not None:   # ... in one pass: all keys in rings, a prefix LSE behind every ring
+                    _lib.flash_attn_d128_ranges_prefix(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
+                                                       J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale,
+                                                       self._profile_segments(F_, first, valid[b], J, widths), cal.prefix,
+                                                       q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
+                                                       o_off=b * J * (D + M), prefix_off=b * heads * cal.segments * J)
+                    _lib.attn_prefix_mass(cal.prefix, cal.mass, heads, cal.segments, J, row0=0, rows=S,          # latent queries only
+                                          prefix_off=b * heads * cal.segments * J, out_off=(bi * N + b) * heads * cal.segments)
+                    continue
                 if cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
                     A = (1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad)
                     offs = dict(q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad, lse_off=b * heads * J)
@@ -752,7 +777,7 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                   strideR=J * D)
 
         if cal is not None:
-            self._head_window_finish(cal, kvr, batch=1)   # (one launch per sample)
+            self._head_window_finish(cal, kvr0, batch=1)   # (one launch per sample)
 
         # ---- output head: AdaLayerNormContinuous (scale | shift), projection, unpatchify ----
         G(ws.semb1, w.ada_out[0], ws.mod_out, N, 2 * D, D, D, D, 2 * D, bias=w.ada_out[1])

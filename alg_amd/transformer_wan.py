@@ -31,7 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import HeadWindowHost, KvRangesHeads, frame_window_ranges
+from .attn_window import HeadWindowHost, KvRangesHeads, frame_profile_segments, frame_window_ranges
 from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
@@ -379,10 +379,10 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             ws.vt8s = torch.empty(N, D, dtype=torch.float32, device=dev)
         return ws
 
-    def _window_ranges(self, frames, hw):
+    def _window_ranges(self, frames, hw, window=None):
         """The frame-window table of this video shape (device-resident, built once per (F, hw, window, sink): before any capture
-        that replays it), or None where the window is the dense attention."""
-        window, sink = int(self.attn_window), int(self.attn_sink_frames)
+        that replays it), or None where the window is the dense attention.  window: attn_window, or one of attn_window_widths."""
+        window, sink = int(self.attn_window if window is None else window), int(self.attn_sink_frames)
         if window < 0 or sink < 0:
             raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
         if self.fp8_attention:
@@ -393,6 +393,14 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             if r is not None:
                 r.on(self.device)   # uploaded here, once
             self._attn_ranges[key] = r
+        return self._attn_ranges[key]
+
+    def _profile_segments(self, frames, hw, widths):
+        """The frame_profile_segments table of this video shape for attn_window_widths (device-resident, built once)."""
+        key = ("profile", frames, hw, widths, int(self.attn_sink_frames))
+        if key not in self._attn_ranges:
+            self._attn_ranges[key] = frame_profile_segments(frames, hw, widths, sink_frames=int(self.attn_sink_frames))
+            self._attn_ranges[key].on(self.device)
         return self._attn_ranges[key]
 
     # ---- forward -----------------------------------------------------------------------------------------------------
@@ -488,6 +496,9 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         cal = hwm if hwm not in (None, "dense", "tables") else None
         full = self._head_full(S, S) if cal is not None else None
         kvr0 = kvr
+        widths = self._head_window_widths() if hwm is not None else None
+        if widths is not None:   # attn_window_widths: the tables of every candidate width, one profile table for the calibration
+            kvr0 = self._head_width_bases(widths, lambda w_: self._window_ranges(F_, S // F_, window=w_))
         for li, L in enumerate(self.blocks):
             if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
                 break                 # hit: x = x1 + the cached tail, straight to the head
@@ -520,7 +531,13 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                 if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
                     kvr = None if hwm == "dense" or cal is not None else self._layer_table(kvr0, li)
                 order = self._layer_order(kvr, N) if isinstance(kvr, KvRangesHeads) else None      # attn_window_balance
-                if cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
+                if cal is not None and widths is not None:   # ... in one pass: all keys in rings, a prefix LSE behind every ring
+                    A = (N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale)
+                    T("attn_self", _lib.flash_attn_d128_ranges_prefix, ws.qk, ws.qk, ws.vt, ws.att, *A,
+                      self._profile_segments(F_, S // F_, widths), cal.prefix, k_off=D)
+                    T("attn_calib", _lib.attn_prefix_mass, cal.prefix, cal.mass, N * heads, cal.segments, S,
+                      out_off=li * N * heads * cal.segments)
+                elif cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
                     A = (N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale)
                     T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, *A, full, lse=cal.lse_full, k_off=D)
                     T("attn_calib", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, cal.o, *A, kvr0, lse=cal.lse_part, k_off=D)

@@ -405,6 +405,36 @@ int alg_flash_attn_d128_ranges_order(const void* q, const void* k, const void* v
                                      const int32_t* kv_ranges, int max_ranges, int table_heads, float* lse, const int32_t* order,
                                      int order_len, void* stream);
 
+/* alg_flash_attn_d128_ranges_heads over a table of up to 12 SEGMENTS that writes, instead of one lse, the log-sum-exp of the keys
+ * visited SO FAR behind every segment: the one-pass calibration of the per-head window width (alg_amd/attn_window.py:
+ * frame_profile_segments, decide_widths).  Same frame, operands, checks, defensive reading of the table and shape limits; an
+ * instantiation of its own, so the kernels of the other entries are what they were.
+ *   kv_ranges    : DEVICE table int32 [table_heads][q_blocks][max_segments][2], max_segments in 1..12 (the other entries: 1..4).
+ *                  The kernel visits a row's segments in table order; empty entries (end <= begin) may stand ANYWHERE and are
+ *                  skipped.
+ *   lse_prefix   : DEVICE fp32 [batch][heads][max_segments][Sq], contiguous, 4-byte aligned, not NULL (else ALG_EINVAL).  Behind
+ *                  segment i, visited or skipped, the kernel writes once per query
+ *                      lse_prefix[b][h][i][q] = log2( sum over the keys j of the segments 0 .. i of 2^(c * q.k_j) )
+ *                  from its running max and fp32 row sum (m * c + log2(l)), -inf while no key has been visited.
+ * o is written from the final state as in the other entries.  lse_prefix[b][h][max_segments - 1] is BIT FOR BIT the lse of
+ * alg_flash_attn_d128_ranges_heads for the same table, and o is that entry's o (for tables that entry takes).  When the segments
+ * of every row partition [0, Skv) the launch is the dense attention: the exact softmax over all keys in another fp32 summation
+ * grouping than alg_flash_attn_d128's (docs/numerics.md).  Enqueue-only and allocation-free. */
+int alg_flash_attn_d128_ranges_prefix(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
+                                      int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
+                                      int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale,
+                                      const int32_t* kv_ranges, int max_segments, int table_heads, float* lse_prefix,
+                                      void* stream);
+
+/* Softmax mass per segment from the prefixes of alg_flash_attn_d128_ranges_prefix, fp32 [panels][segments][Sq] with panels = batch *
+ * heads.  With P_i = lse_prefix[p][i][q], P_last = P_(segments - 1) and P_(-1) = -inf:
+ *   out[p][i] = mean over q in [row0, row0 + rows) of exp2(P_i - P_last) - exp2(P_(i-1) - P_last),  exp2(-inf - x) being 0
+ * i.e. the fraction of the softmax mass of panel p's queries that lies on the keys of segment i.  out is DEVICE double
+ * [panels][segments], 8-byte aligned.  One launch; double exp2 and double accumulation in a fixed two-level order (per lane in
+ * row order, then across the lanes of the (panel, segment)'s workgroup), no atomics: run-to-run bit-identical.  segments in 1..12,
+ * 0 <= row0, rows >= 1, row0 + rows <= Sq, else ALG_EINVAL. */
+int alg_attn_prefix_mass(const float* lse_prefix, double* out, int panels, int segments, int Sq, int row0, int rows, void* stream);
+
 /* Recall of a key subset from two lse outputs of alg_flash_attn_d128_ranges_heads or of alg_flash_attn_d64_ranges_heads (it knows
  * nothing of the head dimension) over the same queries (lse_part: the subset, lse_full: all keys), both fp32 [panels][Sq] with
  * panels = batch * heads:

@@ -5,6 +5,7 @@ run of this).  One job, arms alternated, package power and shader clock sampled 
     python scripts/attn_window_ab.py --family d64 --out profiles/attn_window_d64_ab.json [--only kernel|steps|accuracy]
     python scripts/attn_window_ab.py --family heads64 --out profiles/attn_window_heads_d64_ab.json [--only kernel|steps]
     python scripts/attn_window_ab.py --family order --out profiles/attn_window_order_ab.json [--only kernel|steps]
+    python scripts/attn_window_ab.py --family widths --out profiles/attn_window_widths_ab.json [--only kernel|steps]
 
   kernel    alg_flash_attn_d128 against alg_flash_attn_d128_ranges at the three launch shapes (C3 32,760 x 40 heads, C5 75,600 x 40,
             C4 119,056 queries x 118,848 keys x 24 heads): the dense entry (first and last arm: their distance is the job's spread),
@@ -45,6 +46,15 @@ predicts no gain).  Each mixed arm is set against 0.5 * (all dense + all windowe
 available saving it realises.  Its steps arms time iterations 0-1 of the bench workloads with attn_window_balance off / on / "lanes" /
 off in one process, attn_window_recall at the workload's recorded mean recall so that about half the heads window.  No bound is set.
 
+--family widths is the per-head window WIDTH from one calibration pass (profiles/attn_window_widths_ab.json;
+alg_flash_attn_d128_ranges_prefix, head_dim 128 only).  Kernel arms at the C3 / C5 / C4 launch shapes: the plain full-range launch,
+the parent's calibration PAIR (full range with lse + the half-coverage window with lse, timed as one unit, without and with
+alg_attn_lse_recall), ONE prefix launch over the 9-segment profile table of the widths (1, 2, half-coverage window) (without and with
+alg_attn_prefix_mass), and the dense entry -- first and last, alternated.  The question: does the prefix launch cost less than the pair
+by more than the job's spread, and how far above the plain full-range launch is it.  Steps arms: iterations 0-1 of the bench
+workloads with attn_window_recall = 0.9 and attn_window_widths off / on / off between two arms with the window off; the calibration
+cost per video is an arm's two steps minus the off arms' mean, over a dense step.  No bound is set.
+
 Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
 import argparse
 import gc
@@ -61,8 +71,8 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from alg_amd import _lib  # noqa: E402
-from alg_amd.attn_window import (balanced_order, frame_window_ranges, full_ranges, head_window_ranges,  # noqa: E402
-                                 unit_costs)
+from alg_amd.attn_window import (balanced_order, frame_profile_segments, frame_window_ranges, full_ranges,  # noqa: E402
+                                 head_window_ranges, unit_costs)
 
 BF = torch.bfloat16
 DEV = torch.device("cuda:0")
@@ -222,6 +232,112 @@ def step_arms_heads(workload, recall=0.9, window=None):
     kvr = [t for t in wl.model._attn_ranges.values() if t is not None]
     out["coverage"] = kvr[0].coverage if kvr else None
     wl.model.attn_window, wl.model.attn_window_recall = 0, 0.0
+    del wl
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+def widths_for(w_half):
+    """The candidate widths of --family widths: 1, 2 and the half-coverage window (a 9-segment profile table)."""
+    return (1, 2, w_half) if w_half > 2 else (1, 2, 4)
+
+
+def kernel_arms_widths(name, iters):
+    F, hw, valid, rows, heads = SHAPES[name]
+    S, D = F * hw, heads * 128
+    Sq, Skv = S + rows, S + valid
+    pad = (Sq + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(Sq, 2 * D, generator=g, device=DEV, dtype=BF)
+    vt = torch.randn(D, pad, generator=g, device=DEV, dtype=BF)
+    o, o2 = torch.empty(Sq, D, dtype=BF, device=DEV), torch.empty(Sq, D, dtype=BF, device=DEV)
+    lse_full, lse_part = (torch.empty(heads, Sq, dtype=torch.float32, device=DEV) for _ in range(2))
+    args = lambda out: (qk, qk, vt, out, 1, heads, Sq, Skv, Sq * 2 * D, 2 * D, Sq * 2 * D, 2 * D, D * pad, pad, Sq * D, D, 1.0 / 128 ** 0.5)
+    w, half = window_for(F, hw, valid, rows, 0.5)
+    widths = widths_for(w)
+    full = full_ranges(Sq, Skv)
+    seg = frame_profile_segments(F, hw, widths, tail=(S, S + valid) if valid else None, rows=S + rows if rows else None)
+    n = seg.segments
+    prefix = torch.empty(heads, n, Sq, dtype=torch.float32, device=DEV)
+    recall, mass = torch.zeros(heads, dtype=torch.float64, device=DEV), torch.zeros(heads * n, dtype=torch.float64, device=DEV)
+    for t in (half, full, seg):
+        t.device_table
+
+    def pair(reduce):
+        _lib.flash_attn_d128_ranges_heads(*args(o), full, lse=lse_full, k_off=D)
+        _lib.flash_attn_d128_ranges_heads(*args(o2), half, lse=lse_part, k_off=D)
+        if reduce:
+            _lib.attn_lse_recall(lse_part, lse_full, recall, heads, Sq, row0=0, rows=S)
+
+    def one_pass(reduce):
+        _lib.flash_attn_d128_ranges_prefix(*args(o), seg, prefix, k_off=D)
+        if reduce:
+            _lib.attn_prefix_mass(prefix, mass, heads, n, Sq, row0=0, rows=S)
+
+    full_range = lambda: _lib.flash_attn_d128_ranges_heads(*args(o), full, k_off=D)
+    arms = [("full_range_first", full_range), ("pair_first", lambda: pair(False)), ("prefix_first", lambda: one_pass(False)),
+            ("dense_entry", lambda: _lib.flash_attn_d128(*args(o), k_off=D)),
+            ("pair_reduced", lambda: pair(True)), ("prefix_reduced", lambda: one_pass(True)),
+            ("prefix_last", lambda: one_pass(False)), ("pair_last", lambda: pair(False)), ("full_range_last", full_range)]
+    out = {"queries": Sq, "keys": Skv, "heads": heads, "frames": F, "tokens_per_frame": hw, "attn_window": w, "widths": list(widths),
+           "segments": n, "window_coverage": half.coverage, "arms": {}}
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        full_range()
+        torch.cuda.synchronize()
+    for label, fn in arms:
+        out["arms"][label] = timed(fn, iters)
+    ms = lambda k: out["arms"][k]["median_ms"]
+    mean, spread = lambda k: (ms(k + "_first") + ms(k + "_last")) / 2, lambda k: abs(ms(k + "_first") - ms(k + "_last"))
+    d, pr, px = mean("full_range"), mean("pair"), mean("prefix")
+    out["full_range_ms_mean"], out["pair_ms_mean"], out["prefix_ms_mean"] = d, pr, px
+    out["spread_ms"] = {"full_range": spread("full_range"), "pair": spread("pair"), "prefix": spread("prefix")}
+    out["prefix_over_pair"], out["prefix_over_full_range"], out["pair_over_full_range"] = px / pr, px / d, pr / d
+    out["pair_minus_prefix_ms"] = pr - px
+    out["prefix_beats_pair_beyond_spread"] = pr - px > max(out["spread_ms"].values())
+    out["reduction_cost_ms"] = {"lse_recall": ms("pair_reduced") - pr, "prefix_mass": ms("prefix_reduced") - px}
+    del qk, vt, o, o2, lse_full, lse_part, prefix
+    torch.cuda.empty_cache()
+    return out
+
+
+def step_arms_widths(workload, recall=0.9):
+    F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40", "c4": "c4_119056x24"}[workload]]
+    w_half = window_for(F, hw, valid, rows, 0.5)[0]
+    widths = widths_for(w_half)
+    args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
+    wl.build()
+    torch.cuda.synchronize()
+    out = {"attn_window": w_half, "attn_window_recall": recall, "attn_window_widths": list(widths), "arms": {}}
+    for label, w, r, ws in (("off_first", 0, 0.0, None), ("widths_off_first", w_half, recall, None), ("widths_on", w_half, recall, widths),
+                            ("widths_off_last", w_half, recall, None), ("off_last", 0, 0.0, None)):
+        wl.model.attn_window, wl.model.attn_window_recall, wl.model.attn_window_widths = w, r, ws
+        bench.run_steps(wl, 1)
+        torch.cuda.synchronize()
+        with bench.SmiSampler(0) as smi:
+            t0 = time.perf_counter()
+            bench.run_steps(wl, 2)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+        sm = smi.summary() or {}
+        out["arms"][label] = {"attn_window": w, "attn_window_recall": r, "attn_window_widths": list(ws) if ws else None,
+                              "seconds_two_steps": s, "finite": bool(torch.isfinite(wl.last_out.float()).all().item()),
+                              "power_w": (sm.get("power_w") or {}).get("mean"), "sclk_mhz": (sm.get("sclk_mhz") or {}).get("mean")}
+        if ws:
+            st = wl.model.attn_window_stats
+            out["layers_calibrated"] = len(st)
+            out["heads_by_width"] = {str(x): sum(rec["width"].count(x) for rec in st) for x in (0,) + tuple(widths)}
+            per_width = [[x[j] for rec in st for smp in rec["recall_by_width"] for x in smp] for j in range(len(widths))]
+            out["recall_by_width_min_mean_max"] = [[min(v), sum(v) / len(v), max(v)] for v in per_width if v]
+    sec = lambda k: out["arms"][k]["seconds_two_steps"]
+    off = out["off_seconds_mean"] = (sec("off_first") + sec("off_last")) / 2
+    two = out["widths_off_seconds_mean"] = (sec("widths_off_first") + sec("widths_off_last")) / 2
+    out["off_spread_seconds"], out["widths_off_spread_seconds"] = abs(sec("off_first") - sec("off_last")), abs(sec("widths_off_first") - sec("widths_off_last"))
+    out["two_launch_calibration_cost_over_dense_step"] = (two - off) / (off / 2)
+    out["one_pass_calibration_cost_over_dense_step"] = (sec("widths_on") - off) / (off / 2)
+    wl.model.attn_window, wl.model.attn_window_recall, wl.model.attn_window_widths = 0, 0.0, None
     del wl
     gc.collect()
     torch.cuda.empty_cache()
@@ -653,9 +769,10 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64", "order"], default="d128",
+    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64", "order", "widths"], default="d128",
                     help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2); heads: the per-head window chosen by recall (d = 128); "
-                         "heads64: the same for d = 64 (CogVideoX, C2); order: the coverage-balanced launch order (both head dims)")
+                         "heads64: the same for d = 64 (CogVideoX, C2); order: the coverage-balanced launch order (both head dims); "
+                         "widths: the per-head window width from one calibration pass (d = 128)")
     ap.add_argument("--workloads", default="c3,c5,c4", help="--family heads / order: the workloads of the steps arms")
     ap.add_argument("--shapes", default=",".join(list(SHAPES) + ["c2_2x48x17776"]), help="--family order: the kernel arms' launch shapes")
     a = ap.parse_args()
@@ -683,6 +800,21 @@ def main():
             res.setdefault("steps", {})
             for wlname in a.workloads.split(","):
                 res["steps"][wlname] = step_arms_order(wlname, window=2 if wlname == "c2" else None)
+                save()
+        print(json.dumps(res))
+        return
+    if a.family == "widths":
+        res["weights"] = ("synthetic Gaussian: recall is about the coverage, so no head reaches a threshold above it and the later "
+                          "steps run dense; which widths the heads of a trained checkpoint choose, and the quality, are unmeasured")
+        if "kernel" in parts:
+            res.setdefault("kernel", {})
+            for name in [n for n in a.shapes.split(",") if n in SHAPES]:
+                res["kernel"][name] = kernel_arms_widths(name, a.iters)
+                save()
+        if "steps" in parts:
+            res.setdefault("steps", {})
+            for wlname in a.workloads.split(","):
+                res["steps"][wlname] = step_arms_widths(wlname)
                 save()
         print(json.dumps(res))
         return
