@@ -37,6 +37,7 @@ EXPORTS = (
     "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall", "alg_flash_attn_d64_ranges_heads",
     "alg_flash_attn_d128_ranges_order", "alg_flash_attn_d64_ranges_order",
     "alg_flash_attn_d128_ranges_prefix", "alg_attn_prefix_mass",
+    "alg_gemm_fp4", "alg_quantize_mxfp4_rows",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -159,6 +160,8 @@ def load_library():
     lib.alg_rms_norm_rows.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]
     lib.alg_softmax_hilo.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int64, ctypes.c_float, c_void_p]
     lib.alg_gemm_fp8.argtypes = [POINTER(GemmArgs), c_void_p]
+    lib.alg_gemm_fp4.argtypes = [POINTER(GemmArgs), c_void_p]
+    lib.alg_quantize_mxfp4_rows.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]
     lib.alg_conv_cl_bf16.argtypes = [c_void_p] * 5 + [c_int] * 7 + [c_void_p]
     lib.alg_vae_groupnorm_workspace.argtypes = [POINTER(VaeGeom)]
     lib.alg_vae_groupnorm_stats.argtypes = [c_void_p, POINTER(VaeGeom), c_float, c_void_p, c_void_p, c_void_p]
@@ -1115,6 +1118,56 @@ def quantize_fp8_rows_batched(x, q, scale, batch, rows, K, x_bstride, x_rstride,
     _check(load_library().alg_quantize_fp8_rows_batched(_p(x, x_off), x_bstride, x_rstride, _p(q, q_off), _p(scale, scale_off),
                                                         batch, rows, K, _stream()), "alg_quantize_fp8_rows_batched")
     return q, scale
+
+
+def _bytes_dev(t, name):
+    _dev(t, name)
+    if t.dtype != torch.uint8 or not t.is_contiguous():
+        raise AlgHipError("%s must be a contiguous uint8 tensor, got %s" % (name, t.dtype))
+    return t
+
+
+def quantize_mxfp4_rows(x, q, scales, rows, K, x_rstride=None, x_off=0, q_off=0, scale_off=0):
+    """Row-wise OCP MXFP4 quantisation (alg_quantize_mxfp4_rows): rows of K bf16 at stride x_rstride -> q [rows, K/2] packed e2m1
+    bytes (element 2i in the low nibble of byte i) and scales [rows, K/32] E8M0 bytes, both uint8, filled in place.  x_off in
+    elements, q_off / scale_off in bytes."""
+    _dev(x, "x")
+    if x.dtype != torch.bfloat16:
+        raise AlgHipError("quantize_mxfp4_rows takes bf16 rows, got %s" % x.dtype)
+    _bytes_dev(q, "q"), _bytes_dev(scales, "scales")
+    x_rstride = K if x_rstride is None else x_rstride
+    if K <= 0 or K % 32 or rows < 0:
+        raise AlgHipError("quantize_mxfp4_rows: K = %d must be a positive multiple of 32 (rows = %d)" % (K, rows))
+    if (rows and x_off + (rows - 1) * x_rstride + K > x.numel()) or q_off + rows * (K // 2) > q.numel() or \
+            scale_off + rows * (K // 32) > scales.numel():
+        raise AlgHipError("quantize_mxfp4_rows: %d rows of K = %d do not fit the tensors" % (rows, K))
+    _check(load_library().alg_quantize_mxfp4_rows(_p(x, x_off), x_rstride, _p(q, q_off), _p(scales, scale_off), rows, K,
+                                                  _stream()), "alg_quantize_mxfp4_rows")
+    return q, scales
+
+
+def gemm_fp4(A, B, C, M, N, K, lda, ldb, ldc, a_scale=None, b_scale=None, a_off=0, b_off=0, a_scale_off=0, b_scale_off=0,
+             strideAScale=0, strideBScale=0, **kw):
+    """`gemm` with OCP MXFP4 operands (alg_gemm_fp4): A [.., M, K/2] and B [.., N, K/2] hold packed e2m1 bytes, a_scale / b_scale
+    the E8M0 bytes [.., rows, K/32] (all uint8).  lda / ldb / strideA / strideB / a_off / b_off count elements (two per byte);
+    the scale offsets and batch strides count bytes.  Every other keyword is `gemm`'s; a PackedB is refused."""
+    if isinstance(B, PackedB) or isinstance(A, PackedB):
+        raise AlgHipError("a packed B holds bf16 weight fragments for GEMM schedule 11: the MXFP4 GEMM takes row-major e2m1 bytes")
+    if a_scale is None or b_scale is None:
+        raise AlgHipError("gemm_fp4 needs a_scale and b_scale (E8M0 bytes, one per 32 elements along K)")
+    for t, name in ((A, "A"), (B, "B"), (a_scale, "a_scale"), (b_scale, "b_scale")):
+        _bytes_dev(t, name)
+    if K <= 0 or K % 256:
+        raise AlgHipError("gemm_fp4: K = %d must be a positive multiple of 256" % K)
+    if a_off % 2 or b_off % 2:
+        raise AlgHipError("gemm_fp4: a_off / b_off count e2m1 elements and must be even (whole bytes)")
+    args, _ = gemm_args(A, B, C, M, N, K, lda, ldb, ldc, **kw)
+    args.A = A.data_ptr() + a_off // 2
+    args.B = B.data_ptr() + b_off // 2
+    args.a_scale = a_scale.data_ptr() + a_scale_off
+    args.b_scale = b_scale.data_ptr() + b_scale_off
+    args.strideAScale, args.strideBScale = strideAScale, strideBScale
+    _check(load_library().alg_gemm_fp4(ctypes.byref(args), _stream()), "alg_gemm_fp4")
 
 
 ATTN_Q_PRESCALED = 1

@@ -146,6 +146,22 @@ __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf2(f, f)
 // fp32 value rounded through bf16 (the reference's bf16 tensors round after every op)
 __device__ __forceinline__ float rbf(float f) { return __uint_as_float(pack_bf2(f, f) << 16); }
 
+// the activations of the GEMM epilogues (gemm_kernel.h, gemm_fp4.hip)
+__device__ __forceinline__ float act_apply(float x, int act) {
+  if (act == ALG_ACT_GELU_TANH) {
+    // 0.5 x (1 + tanh(u)) == x / (1 + exp(-2u)),  u = sqrt(2/pi) (x + 0.044715 x^3).  The reciprocal is the hardware's
+    // v_rcp_f32 (1 ulp): the correctly rounded one costs ten more instructions per output in an epilogue that is VALU-bound,
+    // and the result is rounded to bf16 (2^-9) right after.
+    // exp(-2u) = exp2(x (k1 + k2 x^2)), k1 = -2 log2(e) sqrt(2/pi), k2 = 0.044715 k1: three operations for the argument
+    const float k1 = -2.0f * 1.4426950408889634f * 0.7978845608028654f, k2 = 0.044715f * k1;
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * fmaf(k2, x * x, k1)));
+  }
+  if (act == ALG_ACT_SILU) {
+    return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
+  }
+  return x;
+}
+
 template <typename T>
 __device__ __forceinline__ float load_as_float(const T* p, int64_t i);
 template <>

@@ -131,13 +131,14 @@ class CogVideoXImageToVideoPipeline:
     @classmethod
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
                         scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False,
-                        step_cache=0.0, attn_window=0, attn_window_recall=0.0, attn_window_balance=False, attn_window_widths=None,
+                        fp4=False, step_cache=0.0, attn_window=0, attn_window_recall=0.0, attn_window_balance=False, attn_window_widths=None,
                         **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
         `image_latents` and `output_type="latent"`.  `fp8=True` loads the transformer with e4m3 block linears
-        (CogVideoXTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.  `step_cache` > 0
+        (CogVideoXTransformer3DModel(..., fp8=True)); `fp4=True` with MXFP4 feed-forward
+        linears (CogVideoXTransformer3DModel(..., fp4=True)); neither has an effect on a transformer instance passed in.  `step_cache` > 0
         switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default), `attn_window` > 0
         its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by default);
         `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost) and needs
@@ -166,7 +167,7 @@ class CogVideoXImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = CogVideoXTransformer3DModel.from_pretrained(model_path, torch_dtype=torch_dtype,
-                                                                      device=device, fp8=fp8)
+                                                                      device=device, fp8=fp8, fp4=fp4)
         if step_cache:
             transformer.step_cache = float(step_cache)
         if attn_window:

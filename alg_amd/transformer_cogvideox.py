@@ -25,6 +25,9 @@ fp8 mode only (allocated on the first fp8 forward of a shape):
     q8     [N*S, 4D] bytes  OCP e4m3 copy of the current GEMM input (rows of K = D or 4D bytes, contiguous)
     q8s    [N, S4] float32  its per-token scales, S4 = S rounded up to a multiple of 4 (the V^T GEMM reads them as its B scales,
                             16 bytes at a time, per batch item)
+fp4 mode only (allocated on the first fp4 forward of a shape):
+    q4     [N*S, 2D] bytes  OCP MXFP4 copy of the current feed-forward GEMM input (rows of K/2 bytes, K = D or 4D, contiguous)
+    q4s    [N*S, D/8] bytes its E8M0 block scales (rows of K/32 bytes)
 """
 from __future__ import annotations
 
@@ -87,12 +90,21 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
     # the block linears that fp8 mode quantises, per output channel: Q|K, V, attention out, feed-forward in / out
     FP8_WEIGHTS = ("wqk", "wv", "wo", "wf1", "wf2")
 
-    def __init__(self, config: CogVideoXTransformerConfig, weights: dict, device="cuda", fp8=False):
+    # the two feed-forward linears that fp4 mode runs with MXFP4 weights and activations
+    FP4_WEIGHTS = ("wf1", "wf2")
+
+    def __init__(self, config: CogVideoXTransformerConfig, weights: dict, device="cuda", fp8=False, fp4=False):
         """``fp8=True``: the five block linears (attn1.to_q | to_k, to_v, to_out.0, ff.net.0.proj, ff.net.2) run on the fp8
         MFMA (alg_gemm_fp8) -- weights quantised once to OCP e4m3 with one scale per output channel, activations per token
         in front of each GEMM; embedders, the AdaLN GEMM, proj_out, norms, attention and the residual stream stay bf16.
         Built this way the model keeps no bf16 (or packed) copy of those weights.  ``model.fp8`` may also be flipped on a
-        model built in bf16 (A/B runs): the e4m3 copies are then made on the first fp8 forward and both sets are kept."""
+        model built in bf16 (A/B runs): the e4m3 copies are then made on the first fp8 forward and both sets are kept.
+
+        ``fp4=True`` (an extension, off by default): ff.net.0.proj and ff.net.2 of every block run with OCP MXFP4 weights and
+        activations (W4A4, alg_gemm_fp4: e2m1 elements, one E8M0 scale per 32 along K) -- weights quantised once per output
+        channel, the norm2 output (written bf16 first) and the GELU output per token; everything else as ``fp8`` decides.
+        Built this way the model keeps no bf16, packed or e4m3 copy of those two weights; ``model.fp4`` may be flipped on a
+        model built without it exactly like ``fp8``."""
         cfg = self.config = config
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -107,6 +119,9 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         self.fp8 = bool(fp8)
         if self.fp8:
             self._check_fp8_shapes()
+        self.fp4 = bool(fp4)
+        if self.fp4:
+            self._check_fp4_shapes()
         # fp8: the modulated LayerNorms write the e4m3 tokens + row scales themselves (alg_layernorm_modulate_fp8; bit-identical
         # to the norm into y followed by the quantiser pass, which is what False runs)
         self.fuse_quant = True
@@ -195,11 +210,14 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             L["bf1"] = _bf(w[b + "ff.net.0.proj.bias"], dev)
             L["wf2"] = _bf(w[b + "ff.net.2.weight"], dev)
             L["bf2"] = _bf(w[b + "ff.net.2.bias"], dev)
+            if self.fp4:
+                self._quantize_layer_fp4(L, drop_bf16=True)
             if self.fp8:
                 self._quantize_layer(L, drop_bf16=True)
             else:
                 for nm in ("wo", "wf1", "wf2"):
-                    L["p" + nm] = _lib.PackedB(L[nm])
+                    if nm in L:
+                        L["p" + nm] = _lib.PackedB(L[nm])
             self.layers.append(L)
         # norm_out: chunk order (shift, scale) -> (shift, shift, scale, scale) so both segments are valid
         ow, ob = w["norm_out.linear.weight"], w["norm_out.linear.bias"]
@@ -227,10 +245,33 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             raise ValueError("fp8=True: the e4m3 GEMM needs K %% 128 == 0, this config has inner_dim = %d and a feed-forward "
                              "width of %d" % (D, F4))
 
+    def _check_fp4_shapes(self):
+        cfg = self.config
+        D, F4 = cfg.inner_dim, cfg.ff_inner_mult * cfg.inner_dim
+        if D % 256 or F4 % 256:
+            raise ValueError("fp4=True: the MXFP4 GEMM needs K %% 256 == 0, this config has inner_dim = %d and a feed-forward "
+                             "width of %d" % (D, F4))
+
+    @staticmethod
+    def _quantize_layer_fp4(L, drop_bf16):
+        """MXFP4 copies (packed e2m1 bytes [N, K/2], E8M0 block scales [N, K/32]) of a block's feed-forward weights under "<name>4"."""
+        for nm in CogVideoXTransformer3DModel.FP4_WEIGHTS:
+            wt = L[nm]
+            n, k = wt.shape
+            q = torch.empty(n, k // 2, dtype=torch.uint8, device=wt.device)
+            sc = torch.empty(n, k // 32, dtype=torch.uint8, device=wt.device)
+            _lib.quantize_mxfp4_rows(wt, q, sc, n, k)
+            L[nm + "4"] = (q, sc)
+            if drop_bf16:
+                del L[nm]
+
     @staticmethod
     def _quantize_layer(L, drop_bf16):
-        """e4m3 copies (bytes, per-output-channel float32 scales) of a block's five linears under "<name>8"."""
+        """e4m3 copies (bytes, per-output-channel float32 scales) of a block's five linears under "<name>8" (a model built with
+        fp4=True holds no bf16 feed-forward weights: those two are then left out)."""
         for nm in CogVideoXTransformer3DModel.FP8_WEIGHTS:
+            if nm not in L:
+                continue
             wt = L[nm]
             q = torch.empty(wt.shape, dtype=torch.uint8, device=wt.device)
             sc = torch.empty(wt.shape[0], dtype=torch.float32, device=wt.device)
@@ -293,22 +334,22 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
 
     # ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False, fp8=False):
+    def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False, fp8=False, fp4=False):
         """Seeded synthetic weights at the configured shapes, generated on the device tensor by tensor (the
         real checkpoint cannot be downloaded here).  Matrices N(0, std^2), biases 0, norm gains 1."""
         from .weights import synthetic_state_dict
 
         config = config or CogVideoXTransformerConfig()
         return cls(config, synthetic_state_dict(config, seed=seed, std=std, device=device,
-                                                 randomize_affine=randomize_affine), device=device, fp8=fp8)
+                                                 randomize_affine=randomize_affine), device=device, fp8=fp8, fp4=fp4)
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", fp8=False, **_):
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", fp8=False, fp4=False, **_):
         """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk."""
         from .weights import load_diffusers_transformer
 
         config, sd = load_diffusers_transformer(path, subfolder)
-        return cls(config, sd, device=device, fp8=fp8)
+        return cls(config, sd, device=device, fp8=fp8, fp4=fp4)
 
     def to(self, *args, **kwargs):
         return self
@@ -356,7 +397,40 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
                 self._quantize_layer(L, drop_bf16=False)
         return ws["q8"], ws["q8s"]
 
-    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr=None, cal=None):
+    def _fp4_state(self, ws, N, S):
+        """The MXFP4 operand workspace of a shape (made on its first fp4 forward) and, for a model built without fp4 whose `fp4`
+        attribute was set afterwards, the MXFP4 feed-forward weights next to the ones it was built with."""
+        if "q4" not in ws:
+            F4 = self.config.ff_inner_mult * self.config.inner_dim
+            ws["q4"] = torch.empty(N * S, F4 // 2, dtype=torch.uint8, device=self.device)
+            ws["q4s"] = torch.empty(N * S, F4 // 32, dtype=torch.uint8, device=self.device)
+        if self.layers and "wf14" not in self.layers[0]:
+            if "wf1" not in self.layers[0]:
+                raise _lib.AlgHipError("this model was built with fp8=True and holds no bf16 copy of its feed-forward weights to "
+                                       "quantise to MXFP4: build it with fp4=True (or fp8=False) to run fp4")
+            self._check_fp4_shapes()
+            for L in self.layers:
+                self._quantize_layer_fp4(L, drop_bf16=False)
+        return ws["q4"], ws["q4s"]
+
+    def _ff_fp4(self, L, ws, N, S, T, m2):
+        """The feed-forward half of a block with MXFP4 operands: norm2 into y (bf16), y and then the GELU output quantised per
+        token into q4 / q4s in front of the two alg_gemm_fp4 launches.  No fused norm + quantiser yet."""
+        cfg, TM = self.config, self._timed
+        D = cfg.inner_dim
+        F4 = cfg.ff_inner_mult * D
+        x, y, h, mod, q4, q4s = ws["x"], ws["y"], ws["h"], ws["mod"], ws["q4"], ws["q4s"]
+        TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm2_w"], L["norm2_b"], mod, mod, self.mod_cols, N, S, D,
+           T, cfg.norm_eps, scale_off=m2 + 2 * D, shift_off=m2)
+        TM("quant4", _lib.quantize_mxfp4_rows, y, q4, q4s, N * S, D)
+        TM("gemm_ff1", _lib.gemm_fp4, q4, L["wf14"][0], h, S, F4, D, D, D, F4, a_scale=q4s, b_scale=L["wf14"][1], bias=L["bf1"],
+           act=_lib.ACT_GELU_TANH, batch=N, strideA=S * D, strideAScale=S * (D // 32), strideC=S * F4)
+        TM("quant4", _lib.quantize_mxfp4_rows, h, q4, q4s, N * S, F4)
+        TM("gemm_ff2", _lib.gemm_fp4, q4, L["wf24"][0], x, S, D, F4, F4, F4, D, a_scale=q4s, b_scale=L["wf24"][1], bias=L["bf2"],
+           R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D, strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * F4,
+           strideAScale=S * (F4 // 32), strideC=S * D, strideR=S * D)
+
+    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr=None, cal=None, fp4=False):
         """One transformer block with e4m3 operands on its five linears: the launch order of the bf16 block, each GEMM input
         quantised per token into q8 / q8s first (by the LayerNorm itself where a norm produces it)."""
         cfg, G, TM = self.config, _lib.gemm, self._timed
@@ -400,6 +474,8 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         quant(att, D)
         lin("gemm_out", L["wo8"], x, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
+        if fp4:
+            return self._ff_fp4(L, ws, N, S, T, m2)
         ln_mod(L["norm2_w"], L["norm2_b"], m2)
         lin("gemm_ff1", L["wf18"], h, F4, D, F4, bias=L["bf1"], act=_lib.ACT_GELU_TANH)
         quant(h, F4)
@@ -525,6 +601,12 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         elif self.layers and "wqk" not in self.layers[0]:
             raise _lib.AlgHipError("this model was built with fp8=True and holds no bf16 copy of its block weights: build it "
                                    "with fp8=False to run (or switch between) both modes")
+        fp4 = bool(self.fp4)
+        if fp4:
+            self._fp4_state(ws, N, S)
+        elif self.layers and "wf1" not in self.layers[0] and not (fp8 and "wf18" in self.layers[0]):
+            raise _lib.AlgHipError("this model was built with fp4=True and holds no bf16 (or e4m3) copy of its feed-forward "
+                                   "weights: build it with fp4=False to run (or switch between) both modes")
         S_pad = ws["S_pad"]
         cos, sin = self._rope(image_rotary_emb)
         G = _lib.gemm
@@ -587,7 +669,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
                 kvr = None if hwm == "dense" or calib is not None else self._layer_table(kvr0, li)
                 cal = (calib, li, kvr0, T) if calib is not None else None
             if fp8:
-                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr, cal)
+                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr, cal, fp4)
                 continue
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
                T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
@@ -609,6 +691,9 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             self._attention(ws, kvr, N, S, scale, prescale, cal)
             TM("gemm_out", G, att, L[wo_k], x, S, D, D, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
               strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * D, strideC=S * D, strideR=S * D)
+            if fp4:
+                self._ff_fp4(L, ws, N, S, T, m2)
+                continue
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm2_w"], L["norm2_b"], mod, mod, self.mod_cols, N, S, D,
                T, cfg.norm_eps, scale_off=m2 + 2 * D, shift_off=m2)
             TM("gemm_ff1", G, y, L[wf1_k], h, S, F4, D, D, D, F4, bias=L["bf1"], act=_lib.ACT_GELU_TANH, batch=N, strideA=S * D,

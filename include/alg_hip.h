@@ -179,6 +179,8 @@ typedef struct alg_gemm_args {
   int32_t conv_cin_log2; /* implicit-GEMM convolution (alg_conv_bf16 sets these; 0 = plain GEMM): log2 of the channels per tap */
   const float* a_scale; /* alg_gemm_fp8 only: one scale per row of A, [batch][M] at batch stride strideAScale */
   const float* b_scale; /* alg_gemm_fp8 only: one scale per row of B, [batch][N] at batch stride strideBScale (0 = shared) */
+                        /* alg_gemm_fp4 reinterprets both pointers as E8M0 BYTE arrays, [batch][M][K/32] and [batch][N][K/32] row-major
+                           (one scale per 32 elements along K), with strideAScale / strideBScale in bytes */
   int64_t strideAScale, strideBScale;
   int32_t conv_wp;   /* rows of A between vertically adjacent taps (padded width) */
   int32_t conv_hpwp; /* rows of A between temporally adjacent taps (padded height * padded width) */
@@ -230,6 +232,30 @@ int alg_gemm_fp8(const alg_gemm_args* args, void* stream);
 /* Row-wise dynamic quantisation to OCP e4m3: scale[r] = max|x[r]| / 448 (1 if the row is zero), q = e4m3(x / scale).
  * x: rows of K bf16 at stride x_rstride (elements); q: rows of K bytes, contiguous; scale: [rows] float32. */
 int alg_quantize_fp8_rows(const void* x, int64_t x_rstride, void* q, float* scale, int64_t rows, int K, void* stream);
+/* OCP MXFP4 operands (MX v1.0: e2m1 elements, one E8M0 scale per block of 32 consecutive elements along K) on
+ * v_mfma_scale_f32_32x32x64_f8f6f4 with both format selectors at FP4 and the block scales in the instruction's scale operands:
+ * the contract and epilogues of alg_gemm_fp8 -- C = R + gate * act((A @ B^T) + bias), A and B already scaled by their blocks --
+ * with A [batch][M][K/2 bytes] and B [batch][N][K/2 bytes] holding packed e2m1 (element 2i in the LOW nibble of byte i; lda /
+ * ldb / strideA / strideB count ELEMENTS, two per byte, each a multiple of 32 = 16 bytes, A and B 16-byte aligned) and a_scale /
+ * b_scale reinterpreted as the E8M0 byte arrays [batch][rows][K/32] (8-byte aligned; strideAScale / strideBScale in bytes,
+ * multiples of 8, 0 = shared).  K % 256 == 0; M and N arbitrary (edge tiles clamp loads and guard stores); bias, ALG_ACT_*,
+ * residual (may alias C), bf16 / fp32 gate with seg_split, strideGate and ALG_GEMM_GATE_SEG_STRIDE, batch strides as in
+ * alg_gemm_bf16.  A scale byte of 0xFF (NaN) is outside the contract.  ALG_GEMM_B_PACKED11, ALG_GEMM_BIAS_PER_ROW,
+ * ALG_GEMM_PERMUTE_COLS and the convolution addressing are refused with ALG_EINVAL before anything is launched. */
+int alg_gemm_fp4(const alg_gemm_args* args, void* stream);
+
+/* Row-wise quantisation to OCP MXFP4, the operand form of alg_gemm_fp4 (activations: per token; weights, once at load: per
+ * output channel).  Per block of 32 consecutive elements of a row:
+ *   scale byte (E8M0)  e = clamp(floor(log2(amax)) - 2, -127, 127) + 127; an all-zero block writes 127; 0xFF is never written;
+ *   elements           x * 2^-(e - 127) rounded to nearest, ties to even, onto {0, 0.5, 1, 1.5, 2, 3, 4, 6}, saturating at +-6
+ *                      (codes 0..7, bit 3 = the input's sign bit, kept also where the value rounds to zero);
+ *   packing            two elements per byte, element 2i in the low nibble of byte i.
+ * x: rows of K bf16 at stride x_rstride (elements, >= K, % 8 == 0), 16-byte aligned; q: [rows][K/2] bytes, contiguous, 4-byte
+ * aligned; scales: [rows][K/32] bytes, contiguous.  K % 32 == 0.  NaN and Inf inputs are outside the contract (an Inf block
+ * would need the scale 2^126 and saturate, a NaN compares false everywhere and becomes a signed zero).  A bad call is ALG_EINVAL
+ * before any launch. */
+int alg_quantize_mxfp4_rows(const void* x, int64_t x_rstride, void* q, void* scales, int64_t rows, int K, void* stream);
+
 /* The same quantiser on rows that sit inside a wider, batch-strided bf16 buffer, all batch items in ONE launch: row r of item b
  * starts at x + b * x_bstride + r * x_rstride (elements, both % 8 == 0; a column offset goes through the pointer); q is
  * [batch * rows][K] contiguous, scale [batch * rows].  Bit-identical to alg_quantize_fp8_rows on each item.  K = 3072, 12288 and
