@@ -14,7 +14,12 @@
 //     exchange is a v_permlane32_swap, the fma / row sums are packed.
 // Workgroup = 8 waves x 32 queries; K / V^T tiles of 64 kv rows stream through a 2-slot LDS ring (2 x 32 KiB) with
 // 16-byte global_load_lds; workgroups are ordered so one XCD works on one (batch, head) at a time.
-#include "common.h"
+//
+// Host side (attention128_host.h): this file holds the check and the plan of every bf16 d = 128 entry, and the dense entries.  A
+// call is checked (attn128_check), planned (attn128_plan: the 64-query kernel of attention128_q64.hip, the pipelined 32-query
+// kernel of attention128_pipe.hip, or the kernel above -- the one that takes causal and grouped-query calls, the DUAL form and
+// whatever is too short or too large for the other two) and handed to that kernel's launch step.
+#include "attention128_host.h"
 
 namespace alg {
 
@@ -274,132 +279,191 @@ __global__ __launch_bounds__(NW * 64, 2) void flash_attn_d128_kernel(const P p) 
 }
 
 }  // namespace a128
+
+// ---- check: every refusal of the bf16 entries with one key / value set, once, in the order the entries have always run them.
+// `entry` is the name the message carries; the two refusals only alg_flash_attn_d128_ex can meet carry its name.
+int attn128_check(const Attn128Args& a, const char* entry, Attn128Form form) {
+  const bool ranged = form != Attn128Form::DENSE;
+  if (a.kv_group <= 0 || a.heads % a.kv_group) {
+    set_error("alg_flash_attn_d128_ex: heads=%d must be a multiple of kv_group=%d", a.heads, a.kv_group);
+    return ALG_EINVAL;
+  }
+  if (a.causal && a.Sq != a.Skv) {
+    set_error("alg_flash_attn_d128_ex: causal attention needs Sq == Skv (got %d, %d)", a.Sq, a.Skv);
+    return ALG_EINVAL;
+  }
+  if (attn128_bad_argument(a)) {
+    set_error("%s: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", entry, a.batch, a.heads, a.Sq, a.Skv);
+    return ALG_EINVAL;
+  }
+  if (ranged) {
+    const int cap = form == Attn128Form::PREFIX ? 12 : 4;   // alg_flash_attn_d128_ranges_prefix: the segments of a profile table
+    if (!a.ranges || ((uintptr_t)a.ranges & 3) || a.max_ranges < 1 || a.max_ranges > cap) {
+      set_error("%s: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..%d (got %p, %d)", entry, cap,
+                (const void*)a.ranges, a.max_ranges);
+      return ALG_EINVAL;
+    }
+    if (a.table_heads != 1 && a.table_heads != a.heads) {
+      set_error("%s: table_heads must be 1 (one table for every head) or heads = %d, got %d", entry, a.heads, a.table_heads);
+      return ALG_EINVAL;
+    }
+    if ((uintptr_t)a.lse & 3) {
+      set_error("%s: lse must be 4-byte aligned (got %p)", entry, (const void*)a.lse);
+      return ALG_EINVAL;
+    }
+    if (form == Attn128Form::PREFIX && (!a.lse_prefix || ((uintptr_t)a.lse_prefix & 3))) {
+      set_error("%s: lse_prefix must be a 4-byte aligned device buffer [batch][heads][max_segments][Sq] (got %p)", entry,
+                (const void*)a.lse_prefix);
+      return ALG_EINVAL;
+    }
+  }
+  if (attn128_misaligned(a, 8)) {
+    set_error("%s: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned", entry);
+    return ALG_EINVAL;
+  }
+  if (attn128_pitch_short(a.vt_rs, a.Skv)) {
+    set_error("%s: vt row stride %lld must cover Skv rounded up to %d", entry, (long long)a.vt_rs, ATTN128_KVB);
+    return ALG_EINVAL;
+  }
+  if (form == Attn128Form::RANGES_ORDER) {   // the order table is the grid: it holds every unit's place
+    const int64_t units = (int64_t)a.batch * a.heads * attn128_q_blocks(a, ATTN128_Q64_ROWS);
+    if (!a.order || ((uintptr_t)a.order & 3) || a.order_len <= 0 || a.order_len % 8 || (int64_t)a.order_len < units) {
+      set_error("%s: order must be a 4-byte aligned device int32[order_len] with order_len a multiple of 8 and at least "
+                "batch * heads * q_blocks = %lld (got %p, %d)", entry, (long long)units, (const void*)a.order, a.order_len);
+      return ALG_EINVAL;
+    }
+  }
+  return ALG_OK;
+}
+
+// ---- plan: which kernel a checked call runs, and its grid.  Pure: the shape fields of `a` and the option table.
+static Attn128Plan plan_on(const Attn128Args& a, Attn128Route route, int rows) {
+  Attn128Plan pl;
+  pl.route = route;
+  pl.q_blocks = attn128_q_blocks(a, rows);
+  pl.grid = a.order ? (int64_t)a.order_len : attn128_grid(a, pl.q_blocks);   // an order table IS the grid: one workgroup per entry
+  pl.use_statement = route == Attn128Route::Q64 && opt(OPT_ATTN128_Q64) != 3;
+  pl.within_limits = pl.grid <= 0x7fffffff;
+  return pl;
+}
+
+// ALG_ATTN128_Q64: 1 (default) = calls over at least ATTN128_Q64_POLICY_TILES KV tiles; 2 = every call the kernel can take; 3 = as
+// 2 with the statement switched off; 0 = off.  ALG_ATTN128_PIPE: 1 (default) = what the 64-query kernel leaves, from
+// ATTN128_PIPE_MIN_TILES tiles on; 0 = off.  Both kernels take non-causal, ungrouped calls inside attn128_fits whose grid fits;
+// everything else runs the base kernel.  A ranged call has one kernel, the 64-query frame: outside its limits it is refused.
+Attn128Plan attn128_plan(const Attn128Args& a) {
+  if (a.ranges) {
+    Attn128Plan pl = plan_on(a, Attn128Route::Q64, ATTN128_Q64_ROWS);
+    pl.within_limits = pl.within_limits && attn128_fits(a);
+    return pl;
+  }
+  if (!a.causal && a.kv_group == 1 && attn128_fits(a)) {
+    const int tiles = (a.Skv + ATTN128_KVB - 1) / ATTN128_KVB;
+    const int q64 = opt(OPT_ATTN128_Q64);
+    if (q64 && tiles >= (q64 == 1 ? ATTN128_Q64_POLICY_TILES : ATTN128_Q64_MIN_TILES)) {
+      const Attn128Plan pl = plan_on(a, Attn128Route::Q64, ATTN128_Q64_ROWS);
+      if (pl.within_limits) return pl;
+    }
+    if (opt(OPT_ATTN128_PIPE) && tiles >= ATTN128_PIPE_MIN_TILES) {
+      const Attn128Plan pl = plan_on(a, Attn128Route::PIPE, ATTN128_PIPE_ROWS);
+      if (pl.within_limits) return pl;
+    }
+  }
+  return plan_on(a, Attn128Route::BASE, ATTN128_BASE_ROWS);
+}
+
 }  // namespace alg
 
 using namespace alg;
 
-namespace alg {
-int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                        int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs,
-                        int64_t o_rs, float scale, hipStream_t stream);
-int flash_attn_d128_pipe(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                         int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs,
-                         int64_t o_rs, float scale, hipStream_t stream);
+// ---- launch: the base kernel; `second` = the DUAL form's other key / value set, or NULL
+struct SecondKV {
+  const void* k;
+  const void* vt;
+  int Skv;
+  int64_t k_bs, k_rs, vt_bs, vt_rs;
+};
+
+static int launch_base(const char* entry, const Attn128Args& a, const Attn128Plan& pl, const SecondKV* second) {
+  static_assert(a128::NW * 32 == ATTN128_BASE_ROWS && a128::KVB == ATTN128_KVB, "the plan's tile sizes are the kernel's");
+  a128::P p;
+  attn128_fill(p, a, pl.q_blocks);
+  p.kv_group = a.kv_group;
+  p.k2 = nullptr; p.vt2 = nullptr; p.Skv2 = 0; p.k2_bs = p.k2_rs = p.vt2_bs = p.vt2_rs = 0;
+  if (second) {
+    p.k2 = (const bf16_t*)second->k; p.vt2 = (const bf16_t*)second->vt; p.Skv2 = second->Skv;
+    p.k2_bs = second->k_bs; p.k2_rs = second->k_rs; p.vt2_bs = second->vt_bs; p.vt2_rs = second->vt_rs;
+  }
+  const dim3 grid((unsigned)pl.grid), wg(a128::NW * 64);
+  // (the three instantiations are named in the order the object has always held them: hipcc emits kernels as a file names them)
+  if (a.causal)
+    hipLaunchKernelGGL(a128::flash_attn_d128_kernel<true>, grid, wg, 0, a.stream, p);
+  else if (!second)
+    hipLaunchKernelGGL(a128::flash_attn_d128_kernel<false>, grid, wg, 0, a.stream, p);
+  else
+    hipLaunchKernelGGL((a128::flash_attn_d128_kernel<false, true>), grid, wg, 0, a.stream, p);
+  return check_launch(entry);
 }
 
-static int flash_attn_d128_entry(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
-                                 int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
-                                 int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
-                                 float scale, int kv_group, int causal, void* stream) {
-  if (kv_group <= 0 || heads % kv_group) {
-    set_error("alg_flash_attn_d128_ex: heads=%d must be a multiple of kv_group=%d", heads, kv_group);
-    return ALG_EINVAL;
-  }
-  if (causal && Sq != Skv) {
-    set_error("alg_flash_attn_d128_ex: causal attention needs Sq == Skv (got %d, %d)", Sq, Skv);
-    return ALG_EINVAL;
-  }
-  if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
-    set_error("alg_flash_attn_d128: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", batch, heads, Sq, Skv);
-    return ALG_EINVAL;
-  }
-  if (q_rstride % 8 || q_bstride % 8 || k_rstride % 8 || k_bstride % 8 || vt_rstride % 8 || vt_bstride % 8 ||
-      o_rstride % 4 || o_bstride % 4 || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) ||
-      ((uintptr_t)o & 7)) {
-    set_error("alg_flash_attn_d128: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned");
-    return ALG_EINVAL;
-  }
-  if (vt_rstride < (int64_t)((Skv + a128::KVB - 1) / a128::KVB) * a128::KVB) {
-    set_error("alg_flash_attn_d128: vt row stride %lld must cover Skv rounded up to %d", (long long)vt_rstride,
-              a128::KVB);
-    return ALG_EINVAL;
-  }
-  if (!causal && kv_group == 1) {   // 4,096 keys and more: 64 queries per wave (attention128_q64.hip; default since round 4), 1 = not covered
-    const int rc = flash_attn_d128_q64(q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                                       vt_rstride, o_bstride, o_rstride, scale, (hipStream_t)stream);
-    if (rc <= 0) return rc;
-  }
-  if (!causal && kv_group == 1) {   // shorter: the pipelined 32-query kernel (attention128_pipe.hip), 1 = not covered
-    const int rp = flash_attn_d128_pipe(q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                                        vt_rstride, o_bstride, o_rstride, scale, (hipStream_t)stream);
-    if (rp <= 0) return rp;
-  }
-  a128::P p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (bf16_t*)o;
-  p.batch = batch; p.heads = heads; p.Sq = Sq; p.Skv = Skv;
-  p.q_blocks = (Sq + a128::NW * 32 - 1) / (a128::NW * 32);
-  p.q_bs = q_bstride; p.q_rs = q_rstride; p.k_bs = k_bstride; p.k_rs = k_rstride;
-  p.vt_bs = vt_bstride; p.vt_rs = vt_rstride; p.o_bs = o_bstride; p.o_rs = o_rstride;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  p.kv_group = kv_group;
-  p.k2 = nullptr; p.vt2 = nullptr; p.Skv2 = 0; p.k2_bs = p.k2_rs = p.vt2_bs = p.vt2_rs = 0;
-  const int nbh = batch * heads;
-  const int64_t grid = (int64_t)((nbh + 7) / 8) * 8 * p.q_blocks;
-  if (grid > 0x7fffffff) {
+static int dense_entry(const Attn128Args& a) {
+  const int rc = attn128_check(a, "alg_flash_attn_d128", Attn128Form::DENSE);
+  if (rc != ALG_OK) return rc;
+  const Attn128Plan pl = attn128_plan(a);
+  if (!pl.within_limits) {   // (the base kernel's grid: the other two routes are planned only where theirs fits)
     set_error("alg_flash_attn_d128: grid too large");
     return ALG_ELIMIT;
   }
-  if (causal)
-    hipLaunchKernelGGL(a128::flash_attn_d128_kernel<true>, dim3((unsigned)grid), dim3(a128::NW * 64), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(a128::flash_attn_d128_kernel<false>, dim3((unsigned)grid), dim3(a128::NW * 64), 0, (hipStream_t)stream, p);
-  return check_launch("alg_flash_attn_d128");
+  switch (pl.route) {
+    case Attn128Route::Q64: return launch_d128_q64(a, pl);
+    case Attn128Route::PIPE: return launch_d128_pipe(a, pl);
+    default: return launch_base("alg_flash_attn_d128", a, pl, nullptr);
+  }
 }
 
-// Two key / value sets, one launch (the DUAL form of the kernel above); both sets are short by construction (encoder tokens)
+// Two key / value sets, one launch (the DUAL form of the kernel above); both sets are short by construction (encoder tokens).
+// Its messages name both sets; the predicates are attn128_check's.
 extern "C" int alg_flash_attn_d128_dual(const void* q, const void* k, const void* vt, int Skv, int64_t k_bstride, int64_t k_rstride,
                                         int64_t vt_bstride, int64_t vt_rstride, const void* k2, const void* vt2, int Skv2,
                                         int64_t k2_bstride, int64_t k2_rstride, int64_t vt2_bstride, int64_t vt2_rstride, void* o,
                                         int batch, int heads, int Sq, int64_t q_bstride, int64_t q_rstride, int64_t o_bstride,
                                         int64_t o_rstride, float scale, void* stream) {
-  if (!q || !k || !vt || !k2 || !vt2 || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0 || Skv2 <= 0) {
+  const Attn128Args a{q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride,
+                      o_bstride, o_rstride, scale, 1, 0, (hipStream_t)stream};
+  const SecondKV s{k2, vt2, Skv2, k2_bstride, k2_rstride, vt2_bstride, vt2_rstride};
+  if (attn128_bad_argument(a) || !k2 || !vt2 || Skv2 <= 0) {
     set_error("alg_flash_attn_d128_dual: bad argument (batch=%d heads=%d Sq=%d Skv=%d Skv2=%d)", batch, heads, Sq, Skv, Skv2);
     return ALG_EINVAL;
   }
-  if (q_rstride % 8 || q_bstride % 8 || k_rstride % 8 || k_bstride % 8 || vt_rstride % 8 || vt_bstride % 8 || k2_rstride % 8 ||
-      k2_bstride % 8 || vt2_rstride % 8 || vt2_bstride % 8 || o_rstride % 4 || o_bstride % 4 || ((uintptr_t)q & 15) ||
-      ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)k2 & 15) || ((uintptr_t)vt2 & 15) || ((uintptr_t)o & 7)) {
+  if (attn128_misaligned(a, 8) || s.k_rs % 8 || s.k_bs % 8 || s.vt_rs % 8 || s.vt_bs % 8 || ((uintptr_t)k2 & 15) ||
+      ((uintptr_t)vt2 & 15)) {
     set_error("alg_flash_attn_d128_dual: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned");
     return ALG_EINVAL;
   }
-  if (vt_rstride < (int64_t)((Skv + a128::KVB - 1) / a128::KVB) * a128::KVB ||
-      vt2_rstride < (int64_t)((Skv2 + a128::KVB - 1) / a128::KVB) * a128::KVB) {
+  if (attn128_pitch_short(vt_rstride, Skv) || attn128_pitch_short(vt2_rstride, Skv2)) {
     set_error("alg_flash_attn_d128_dual: vt row strides %lld / %lld must cover Skv / Skv2 rounded up to %d", (long long)vt_rstride,
-              (long long)vt2_rstride, a128::KVB);
+              (long long)vt2_rstride, ATTN128_KVB);
     return ALG_EINVAL;
   }
-  a128::P p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (bf16_t*)o;
-  p.batch = batch; p.heads = heads; p.Sq = Sq; p.Skv = Skv;
-  p.q_blocks = (Sq + a128::NW * 32 - 1) / (a128::NW * 32);
-  p.q_bs = q_bstride; p.q_rs = q_rstride; p.k_bs = k_bstride; p.k_rs = k_rstride;
-  p.vt_bs = vt_bstride; p.vt_rs = vt_rstride; p.o_bs = o_bstride; p.o_rs = o_rstride;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  p.kv_group = 1;
-  p.k2 = (const bf16_t*)k2; p.vt2 = (const bf16_t*)vt2; p.Skv2 = Skv2;
-  p.k2_bs = k2_bstride; p.k2_rs = k2_rstride; p.vt2_bs = vt2_bstride; p.vt2_rs = vt2_rstride;
-  const int nbh = batch * heads;
-  const int64_t grid = (int64_t)((nbh + 7) / 8) * 8 * p.q_blocks;
-  if (grid > 0x7fffffff) {
+  const Attn128Plan pl = plan_on(a, Attn128Route::BASE, ATTN128_BASE_ROWS);
+  if (!pl.within_limits) {
     set_error("alg_flash_attn_d128_dual: grid too large");
     return ALG_ELIMIT;
   }
-  hipLaunchKernelGGL((a128::flash_attn_d128_kernel<false, true>), dim3((unsigned)grid), dim3(a128::NW * 64), 0, (hipStream_t)stream, p);
-  return check_launch("alg_flash_attn_d128_dual");
+  return launch_base("alg_flash_attn_d128_dual", a, pl, &s);
 }
 
 extern "C" int alg_flash_attn_d128(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
                                    int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
                                    int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
                                    float scale, void* stream) {
-  return flash_attn_d128_entry(q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                               vt_rstride, o_bstride, o_rstride, scale, 1, 0, stream);
+  return dense_entry({q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride,
+                      o_bstride, o_rstride, scale, 1, 0, (hipStream_t)stream});
 }
 
 extern "C" int alg_flash_attn_d128_ex(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
                                       int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
                                       int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
                                       float scale, int kv_group, int causal, void* stream) {
-  return flash_attn_d128_entry(q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                               vt_rstride, o_bstride, o_rstride, scale, kv_group, causal, stream);
+  return dense_entry({q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride,
+                      o_bstride, o_rstride, scale, kv_group, causal, (hipStream_t)stream});
 }

@@ -31,9 +31,12 @@
 // the maximum) does not trip the trigger again right after an exact step.  With it, probabilities down to 2^-9 of the running
 // offset are normal e4m3 numbers, down to 2^-12 subnormal, and anything below 2^-13 contributes to l (fp32, unrounded) but
 // not to O.  The scale cancels in O / l.
+//
+// Host side: the entry fills the operand struct of the bf16 entries (attention128_host.h) and reads top to bottom as they do --
+// check (the shared predicates at the e4m3 row modulus, around this entry's own messages), plan (one kernel), launch.
 #include <type_traits>
 
-#include "common.h"
+#include "attention128_host.h"
 
 namespace alg {
 namespace a128f8 {
@@ -406,7 +409,11 @@ extern "C" int alg_flash_attn_d128_fp8(const void* q, const float* q_scale, cons
                                        int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, int kv_group,
                                        int causal, void* stream) {
   using namespace a128f8;
-  if (!q || !k || !vt || !o || !q_scale || !k_scale || !vt_scale || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
+  static_assert(KVB == ATTN128_KVB, "the pitch check's tile is the kernel's");
+  const Attn128Args a{q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride,
+                      o_bstride, o_rstride, scale, kv_group, causal, (hipStream_t)stream};
+  // ---- check: the predicates of attn128_check at the e4m3 row modulus, around this entry's own messages and order
+  if (attn128_bad_argument(a) || !q_scale || !k_scale || !vt_scale) {
     set_error("alg_flash_attn_d128_fp8: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", batch, heads, Sq, Skv);
     return ALG_EINVAL;
   }
@@ -415,40 +422,29 @@ extern "C" int alg_flash_attn_d128_fp8(const void* q, const float* q_scale, cons
               kv_group, causal);
     return ALG_EINVAL;
   }
-  if (q_rstride % 16 || q_bstride % 16 || k_rstride % 16 || k_bstride % 16 || vt_rstride % 16 || vt_bstride % 16 || o_rstride % 4 ||
-      o_bstride % 4 || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) || ((uintptr_t)o & 7) ||
-      ((uintptr_t)vt_scale & 15) || ((uintptr_t)q_scale & 3) || ((uintptr_t)k_scale & 3)) {
+  if (attn128_misaligned(a, 16) || ((uintptr_t)vt_scale & 15) || ((uintptr_t)q_scale & 3) || ((uintptr_t)k_scale & 3)) {
     set_error("alg_flash_attn_d128_fp8: q/k/vt need 16-byte aligned rows (strides %% 16 == 0), vt_scale 16-byte, o 8-byte aligned");
     return ALG_EINVAL;
   }
-  if (vt_rstride < (int64_t)((Skv + KVB - 1) / KVB) * KVB) {
+  if (attn128_pitch_short(vt_rstride, Skv)) {
     set_error("alg_flash_attn_d128_fp8: vt row stride %lld must cover Skv = %d rounded up to %d", (long long)vt_rstride, Skv, KVB);
     return ALG_EINVAL;
   }
+  // ---- plan: one kernel, 256 queries per workgroup
+  const int q_blocks = attn128_q_blocks(a, NW * QW);
+  const int64_t grid = attn128_grid(a, q_blocks);
+  // ---- launch
   static PerDeviceOnce attr_set;
-  const int dev_slot = current_device_slot();
-  if (!device_done(attr_set, dev_slot)) {
-    if (hipFuncSetAttribute((const void*)flash_attn_d128_fp8_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-        hipSuccess) {
-      set_error("alg_flash_attn_d128_fp8: cannot reserve %d bytes of LDS", LDS_BYTES);
-      return ALG_ELAUNCH;
-    }
-    device_mark(attr_set, dev_slot);
-  }
-  P p;
-  p.q = (const uint8_t*)q; p.k = (const uint8_t*)k; p.vt = (const uint8_t*)vt; p.o = (bf16_t*)o;
-  p.q_scale = q_scale; p.k_scale = k_scale; p.vt_scale = vt_scale;
-  p.batch = batch; p.heads = heads; p.Sq = Sq; p.Skv = Skv;
-  p.q_blocks = (Sq + NW * QW - 1) / (NW * QW);
-  p.q_bs = q_bstride; p.q_rs = q_rstride; p.k_bs = k_bstride; p.k_rs = k_rstride; p.vt_bs = vt_bstride; p.vt_rs = vt_rstride;
-  p.o_bs = o_bstride; p.o_rs = o_rstride;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
+  const int rc = opt_in_lds(attr_set, {(const void*)flash_attn_d128_fp8_kernel}, LDS_BYTES, "alg_flash_attn_d128_fp8");
+  if (rc != ALG_OK) return rc;
   if (grid > 0x7fffffff) {
     set_error("alg_flash_attn_d128_fp8: grid too large");
     return ALG_ELIMIT;
   }
-  hipLaunchKernelGGL(flash_attn_d128_fp8_kernel, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, (hipStream_t)stream, p);
+  P p;
+  attn128_fill(p, a, q_blocks);
+  p.q_scale = q_scale; p.k_scale = k_scale; p.vt_scale = vt_scale;
+  hipLaunchKernelGGL(flash_attn_d128_fp8_kernel, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, a.stream, p);
   return check_launch("alg_flash_attn_d128_fp8");
 }
 

@@ -9,15 +9,12 @@
 //     top of iteration t:  s_waitcnt vmcnt(8); s_barrier; DMA K(t+3) -> K slot (t+3) & 3, V^T(t+2) -> V slot (t+2) & 3
 // so the waves of a workgroup may be inside or outside the statement independently.  Four waves x 32 queries per workgroup,
 // one wave per SIMD (the statement names v[64:169] and a[0:127]; O^T travels in 64 operands); K / V^T through two four-slot
-// rings of 16 KiB tiles (128 KiB of LDS).  Used for non-causal, ungrouped attention over at least MIN_TILES KV tiles.  DEFAULT
-// (ALG_ATTN128_PIPE=0 switches back to attention128.hip): C3 +4.4 %, C4 +5.9 %, C5 +4.8 % frames/s
+// rings of 16 KiB tiles (128 KiB of LDS).  Used for non-causal, ungrouped attention over at least ATTN128_PIPE_MIN_TILES KV
+// tiles that the 64-query kernel does not take (attention128.hip: attn128_plan; this file holds the kernel and its launch
+// step).  DEFAULT (ALG_ATTN128_PIPE=0 switches back to attention128.hip): C3 +4.4 %, C4 +5.9 %, C5 +4.8 % frames/s
 // (profiles/r3_attention128_pipe_ab.txt); 0 of 600 fp8 C5 forwards in three fresh processes differ run to run
 // (profiles/r3_attention128_pipe_determinism.jsonl) -- the test the 64-query kernel fails.
-#include <stdlib.h>
-
-#include <atomic>
-
-#include "common.h"
+#include "attention128_host.h"
 #include "attn128_pipe_loop.inc"
 
 namespace alg {
@@ -27,7 +24,6 @@ constexpr int NW = 4;
 constexpr int KVB = 64;
 constexpr int TILE = 16384;               // K tile = V^T tile
 constexpr int LDS_BYTES = 8 * TILE;       // 4 K slots + 4 V^T slots
-constexpr int MIN_TILES = 12;
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -271,34 +267,16 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_pipe_kernel(const P p
 
 }  // namespace a128p
 
-// 0 = launched, 1 = not covered (the caller falls back to attention128.hip), < 0 = error
-int flash_attn_d128_pipe(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                         int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs,
-                         int64_t o_rs, float scale, hipStream_t stream) {
+// The launch step of the PIPE route (attention128.hip: attn128_plan decides that a call is this kernel's)
+int launch_d128_pipe(const Attn128Args& a, const Attn128Plan& pl) {
   using namespace a128p;
-  if (!opt(OPT_ATTN128_PIPE) || (Skv + KVB - 1) / KVB < MIN_TILES) return 1;   // default since round 3; ALG_ATTN128_PIPE=0: attention128.hip
-  // 31-bit BYTE offsets inside one (batch, head) for the DMA's lane offsets; V^T rows cover whole 64-key tiles
-  if ((int64_t)(Skv + 64) * k_rs * 2 >= (1ll << 31) || (int64_t)129 * vt_rs * 2 >= (1ll << 31) ||
-      (int64_t)Sq * q_rs * 2 >= (1ll << 31))
-    return 1;
-  if (vt_rs < (int64_t)((Skv + KVB - 1) / KVB) * KVB) return 1;
+  static_assert(NW * 32 == ATTN128_PIPE_ROWS && KVB == ATTN128_KVB, "the plan's tile sizes are the kernel's");
   static PerDeviceOnce attr_set;
-  const int dev_slot = current_device_slot();
-  if (!device_done(attr_set, dev_slot)) {
-    if (hipFuncSetAttribute((const void*)flash_attn_d128_pipe_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) !=
-        hipSuccess)
-      return 1;
-    device_mark(attr_set, dev_slot);
-  }
+  const int rc = opt_in_lds(attr_set, {(const void*)flash_attn_d128_pipe_kernel}, LDS_BYTES, "alg_flash_attn_d128 (pipelined kernel)");
+  if (rc != ALG_OK) return rc;
   P p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (bf16_t*)o;
-  p.batch = batch; p.heads = heads; p.Sq = Sq; p.Skv = Skv;
-  p.q_blocks = (Sq + NW * 32 - 1) / (NW * 32);
-  p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs; p.vt_bs = vt_bs; p.vt_rs = vt_rs; p.o_bs = o_bs; p.o_rs = o_rs;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  const int64_t grid = (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
-  if (grid > 0x7fffffff) return 1;
-  hipLaunchKernelGGL(flash_attn_d128_pipe_kernel, dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
+  attn128_fill(p, a, pl.q_blocks);
+  hipLaunchKernelGGL(flash_attn_d128_pipe_kernel, dim3((unsigned)pl.grid), dim3(NW * 64), LDS_BYTES, a.stream, p);
   return check_launch("alg_flash_attn_d128");
 }
 

@@ -30,11 +30,11 @@
 // alg_flash_attn_d128_ranges_prefix is an instantiation of its own (PREFIX): the same frame over a table of up to 12 segments,
 // which writes the log-sum-exp of the keys visited SO FAR behind every segment (the one-pass calibration of attn_window.py).
 //
-// DEFAULT for non-causal, ungrouped attention over at least POLICY_TILES KV tiles; ALG_ATTN128_Q64=0 switches it off (the
-// 32-query pipelined kernel takes over), =2 takes every call of at least MIN_TILES tiles (tests).
-#include <stdlib.h>
-
-#include "common.h"
+// DEFAULT for non-causal, ungrouped attention over at least ATTN128_Q64_POLICY_TILES KV tiles; ALG_ATTN128_Q64=0 switches it off
+// (the 32-query pipelined kernel takes over), =2 takes every call of at least ATTN128_Q64_MIN_TILES tiles (tests).  That decision
+// is attn128_plan's (attention128.hip); this file holds the kernel, its launch step and the ranged entries, which are checked
+// and planned by the same two functions (attention128_host.h).
+#include "attention128_host.h"
 #include "attn128_q64_loop.inc"
 
 namespace alg {
@@ -45,8 +45,6 @@ constexpr int QW = 64;                   // queries per wave
 constexpr int KVB = 64;
 constexpr int TILE = 16384;              // K tile = V^T tile
 constexpr int LDS_BYTES = 8 * TILE;      // 4 K slots + 4 V^T slots
-constexpr int MIN_TILES = 8;             // what the kernel can take (ALG_ATTN128_Q64=2)
-constexpr int POLICY_TILES = 64;         // what it takes by default: 4,096 keys and more
 
 typedef const __attribute__((address_space(1))) void* gptr_t;
 typedef __attribute__((address_space(3))) void* lptr_t;
@@ -405,61 +403,34 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_q64_kernel(const P p)
 
 }  // namespace a128q
 
-// Fills P and launches; 1 when the operands are beyond what the kernel addresses (31-bit byte offsets inside one (batch, head)).
-template <bool RANGES, bool PREFIX = false>
-static int launch_q64(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                      int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs, int64_t o_rs,
-                      float scale, const int32_t* ranges, int max_ranges, int use_statement, hipStream_t stream,
-                      int table_heads = 1, float* lse = nullptr, const int32_t* order = nullptr, int order_len = 0,
-                      float* lse_prefix = nullptr) {
+// The launch step of the Q64 route, for the dense and the ranged instantiations: `entry` names the caller in the opt-in's
+// message, `what` in the launch's.  The ranged parts of `a` are NULL / 0 from a dense call, whose instantiation reads none of them.
+template <bool RANGES, bool PREFIX>
+static int launch_q64(const char* entry, const char* what, const Attn128Args& a, const Attn128Plan& pl) {
   using namespace a128q;
-  // 31-bit BYTE offsets inside one (batch, head) for the DMA's lane offsets; V^T rows cover whole 64-key tiles
-  if ((int64_t)(Skv + 64) * k_rs * 2 >= (1ll << 31) || (int64_t)129 * vt_rs * 2 >= (1ll << 31) ||
-      (int64_t)Sq * q_rs * 2 >= (1ll << 31))
-    return 1;
-  if (vt_rs < (int64_t)((Skv + KVB - 1) / KVB) * KVB) return 1;
+  static_assert(NW * QW == ATTN128_Q64_ROWS && KVB == ATTN128_KVB, "the plan's tile sizes are the kernel's");
   static PerDeviceOnce attr_set;
-  const int dev_slot = current_device_slot();
-  if (!device_done(attr_set, dev_slot)) {
-    if (hipFuncSetAttribute((const void*)flash_attn_d128_q64_kernel<RANGES, PREFIX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            LDS_BYTES) != hipSuccess)
-      return 1;
-    device_mark(attr_set, dev_slot);
-  }
+  const int rc = opt_in_lds(attr_set, {(const void*)flash_attn_d128_q64_kernel<RANGES, PREFIX>}, LDS_BYTES, entry);
+  if (rc != ALG_OK) return rc;
   P p;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.vt = (const bf16_t*)vt; p.o = (bf16_t*)o;
-  p.batch = batch; p.heads = heads; p.Sq = Sq; p.Skv = Skv;
-  p.q_blocks = (Sq + NW * QW - 1) / (NW * QW);
-  p.q_bs = q_bs; p.q_rs = q_rs; p.k_bs = k_bs; p.k_rs = k_rs; p.vt_bs = vt_bs; p.vt_rs = vt_rs; p.o_bs = o_bs; p.o_rs = o_rs;
-  p.scale_log2 = scale * 1.4426950408889634f;
-  p.clk = clock_tap_for((hipStream_t)stream, &p.clk_slots);
-  p.use_statement = use_statement;
-  p.ranges = ranges;
-  p.max_ranges = max_ranges;
-  p.head_rows = table_heads == 1 ? 0 : p.q_blocks;
-  p.lse = lse;
-  p.order = order;
-  p.order_len = order ? order_len : 0;
-  p.lse_prefix = lse_prefix;
-  // an order table IS the grid: one workgroup per entry (ranges_entry has checked that it holds every unit's place)
-  const int64_t grid = order ? (int64_t)order_len : (int64_t)((batch * heads + 7) / 8) * 8 * p.q_blocks;
-  if (grid > 0x7fffffff) return 1;
-  hipLaunchKernelGGL((flash_attn_d128_q64_kernel<RANGES, PREFIX>), dim3((unsigned)grid), dim3(NW * 64), LDS_BYTES, stream, p);
+  attn128_fill(p, a, pl.q_blocks);
+  p.clk = clock_tap_for(a.stream, &p.clk_slots);
+  p.use_statement = pl.use_statement;
+  p.ranges = a.ranges;
+  p.max_ranges = a.max_ranges;
+  p.head_rows = a.table_heads == 1 ? 0 : p.q_blocks;
+  p.lse = a.lse;
+  p.order = a.order;
+  p.order_len = a.order ? a.order_len : 0;
+  p.lse_prefix = a.lse_prefix;
+  hipLaunchKernelGGL((flash_attn_d128_q64_kernel<RANGES, PREFIX>), dim3((unsigned)pl.grid), dim3(NW * 64), LDS_BYTES, a.stream, p);
   return check_launch(what);
 }
 
-// Returns ALG_OK when launched, 1 when this call is not covered (the caller goes on to attention128_pipe.hip / attention128.hip).
-int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                        int64_t q_bs, int64_t q_rs, int64_t k_bs, int64_t k_rs, int64_t vt_bs, int64_t vt_rs, int64_t o_bs,
-                        int64_t o_rs, float scale, hipStream_t stream) {
-  using namespace a128q;
-  // ALG_ATTN128_Q64: 1 (default) = calls over at least POLICY_TILES KV tiles; 2 = every call the kernel can take; 3 = as 2 with the
-  // statement switched off (every tile through the frame's C++ body: tests of the frame on its own); 0 = off.
-  const int enabled = opt(OPT_ATTN128_Q64);
-  const int n_tiles = (Skv + KVB - 1) / KVB;
-  if (!enabled || n_tiles < (enabled == 1 ? POLICY_TILES : MIN_TILES)) return 1;
-  return launch_q64<false>("alg_flash_attn_d128", q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_rs, k_bs, k_rs, vt_bs, vt_rs, o_bs,
-                           o_rs, scale, nullptr, 0, enabled != 3, stream);
+// (the three instantiations are named in the order the object has always held them -- dense, PREFIX, ranged: hipcc emits kernels
+// as a file names them)
+int launch_d128_q64(const Attn128Args& a, const Attn128Plan& pl) {
+  return launch_q64<false, false>("alg_flash_attn_d128 (64-query kernel)", "alg_flash_attn_d128", a, pl);
 }
 
 }  // namespace alg
@@ -467,75 +438,26 @@ int flash_attn_d128_q64(const void* q, const void* k, const void* vt, void* o, i
 using namespace alg;
 
 // Each block of 256 queries attends to its row of a table of key ranges (include/alg_hip.h).  This kernel is the only one that
-// takes a table: ALG_ATTN128_Q64 routes these entries nowhere else, and only its value 3 (statement off) is honoured here.
-static int ranges_entry(const char* what, const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq, int Skv,
-                        int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride, int64_t vt_bstride,
-                        int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride, float scale, const int32_t* kv_ranges,
-                        int max_ranges, int table_heads, float* lse, const int32_t* order, int order_len, bool ordered,
-                        void* stream, bool prefix = false, float* lse_prefix = nullptr) {
-  const int cap = prefix ? 12 : 4;   // alg_flash_attn_d128_ranges_prefix: the segments of a profile table
-  if (!q || !k || !vt || !o || batch <= 0 || heads <= 0 || Sq <= 0 || Skv <= 0) {
-    set_error("%s: bad argument (batch=%d heads=%d Sq=%d Skv=%d)", what, batch, heads, Sq, Skv);
-    return ALG_EINVAL;
-  }
-  if (!kv_ranges || ((uintptr_t)kv_ranges & 3) || max_ranges < 1 || max_ranges > cap) {
-    set_error("%s: kv_ranges must be a 4-byte aligned device table and max_ranges in 1..%d (got %p, %d)", what, cap,
-              (const void*)kv_ranges, max_ranges);
-    return ALG_EINVAL;
-  }
-  if (table_heads != 1 && table_heads != heads) {
-    set_error("%s: table_heads must be 1 (one table for every head) or heads = %d, got %d", what, heads, table_heads);
-    return ALG_EINVAL;
-  }
-  if ((uintptr_t)lse & 3) {
-    set_error("%s: lse must be 4-byte aligned (got %p)", what, (const void*)lse);
-    return ALG_EINVAL;
-  }
-  if (prefix && (!lse_prefix || ((uintptr_t)lse_prefix & 3))) {
-    set_error("%s: lse_prefix must be a 4-byte aligned device buffer [batch][heads][max_segments][Sq] (got %p)", what,
-              (const void*)lse_prefix);
-    return ALG_EINVAL;
-  }
-  if (q_rstride % 8 || q_bstride % 8 || k_rstride % 8 || k_bstride % 8 || vt_rstride % 8 || vt_bstride % 8 ||
-      o_rstride % 4 || o_bstride % 4 || ((uintptr_t)q & 15) || ((uintptr_t)k & 15) || ((uintptr_t)vt & 15) ||
-      ((uintptr_t)o & 7)) {
-    set_error("%s: q/k/vt need 16-byte aligned rows (strides %% 8 == 0), o 8-byte aligned", what);
-    return ALG_EINVAL;
-  }
-  if (vt_rstride < (int64_t)((Skv + a128q::KVB - 1) / a128q::KVB) * a128q::KVB) {
-    set_error("%s: vt row stride %lld must cover Skv rounded up to %d", what, (long long)vt_rstride, a128q::KVB);
-    return ALG_EINVAL;
-  }
-  if (ordered) {   // alg_flash_attn_d128_ranges_order: the order table is the grid (the other entries pass NULL)
-    const int64_t units = (int64_t)batch * heads * ((Sq + a128q::NW * a128q::QW - 1) / (a128q::NW * a128q::QW));
-    if (!order || ((uintptr_t)order & 3) || order_len <= 0 || order_len % 8 || (int64_t)order_len < units) {
-      set_error("%s: order must be a 4-byte aligned device int32[order_len] with order_len a multiple of 8 and at least "
-                "batch * heads * q_blocks = %lld (got %p, %d)", what, (long long)units, (const void*)order, order_len);
-      return ALG_EINVAL;
-    }
-  } else {
-    order = nullptr, order_len = 0;
-  }
-  const int rc =
-      prefix ? launch_q64<true, true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                                      vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
-                                      (hipStream_t)stream, table_heads, nullptr, nullptr, 0, lse_prefix)
-             : launch_q64<true>(what, q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride,
-                                vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, opt(OPT_ATTN128_Q64) != 3,
-                                (hipStream_t)stream, table_heads, lse, order, order_len);
-  if (rc == 1) {
-    set_error("%s: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large", what);
+// takes a table: attn128_plan routes a ranged call nowhere else, and of ALG_ATTN128_Q64 only the value 3 (statement off) is
+// honoured here.
+static int ranges_entry(const char* entry, Attn128Form form, const Attn128Args& a) {
+  const int rc = attn128_check(a, entry, form);
+  if (rc != ALG_OK) return rc;
+  const Attn128Plan pl = attn128_plan(a);
+  if (!pl.within_limits) {
+    set_error("%s: operands beyond 31-bit byte offsets inside one (batch, head), or grid too large", entry);
     return ALG_ELIMIT;
   }
-  return rc;
+  return form == Attn128Form::PREFIX ? launch_q64<true, true>(entry, entry, a, pl) : launch_q64<true, false>(entry, entry, a, pl);
 }
 
 extern "C" int alg_flash_attn_d128_ranges(const void* q, const void* k, const void* vt, void* o, int batch, int heads, int Sq,
                                           int Skv, int64_t q_bstride, int64_t q_rstride, int64_t k_bstride, int64_t k_rstride,
                                           int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride, int64_t o_rstride,
                                           float scale, const int32_t* kv_ranges, int max_ranges, void* stream) {
-  return ranges_entry("alg_flash_attn_d128_ranges", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride,
-                      vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, 1, nullptr, nullptr, 0, false, stream);
+  return ranges_entry("alg_flash_attn_d128_ranges", Attn128Form::RANGES,
+                      {q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride, o_bstride,
+                       o_rstride, scale, 1, 0, (hipStream_t)stream, kv_ranges, max_ranges, 1, nullptr, nullptr, 0, nullptr});
 }
 
 // The same launch with a table row per (head, q block) when table_heads == heads, and the log-sum-exp output (include/alg_hip.h).
@@ -544,9 +466,9 @@ extern "C" int alg_flash_attn_d128_ranges_heads(const void* q, const void* k, co
                                                 int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
                                                 int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_ranges,
                                                 int table_heads, float* lse, void* stream) {
-  return ranges_entry("alg_flash_attn_d128_ranges_heads", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
-                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, nullptr, 0,
-                      false, stream);
+  return ranges_entry("alg_flash_attn_d128_ranges_heads", Attn128Form::RANGES,
+                      {q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride, o_bstride,
+                       o_rstride, scale, 1, 0, (hipStream_t)stream, kv_ranges, max_ranges, table_heads, lse, nullptr, 0, nullptr});
 }
 
 // The same launch in the order a device table gives: workgroup b runs the unit order[b] (include/alg_hip.h).  Every workgroup
@@ -556,9 +478,9 @@ extern "C" int alg_flash_attn_d128_ranges_order(const void* q, const void* k, co
                                                 int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
                                                 int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_ranges,
                                                 int table_heads, float* lse, const int32_t* order, int order_len, void* stream) {
-  return ranges_entry("alg_flash_attn_d128_ranges_order", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
-                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_ranges, table_heads, lse, order,
-                      order_len, true, stream);
+  return ranges_entry("alg_flash_attn_d128_ranges_order", Attn128Form::RANGES_ORDER,
+                      {q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride, o_bstride,
+                       o_rstride, scale, 1, 0, (hipStream_t)stream, kv_ranges, max_ranges, table_heads, lse, order, order_len, nullptr});
 }
 
 // The same launch over a table of up to 12 segments, with the log-sum-exp of the keys visited so far written behind every segment
@@ -568,9 +490,10 @@ extern "C" int alg_flash_attn_d128_ranges_prefix(const void* q, const void* k, c
                                                  int64_t k_rstride, int64_t vt_bstride, int64_t vt_rstride, int64_t o_bstride,
                                                  int64_t o_rstride, float scale, const int32_t* kv_ranges, int max_segments,
                                                  int table_heads, float* lse_prefix, void* stream) {
-  return ranges_entry("alg_flash_attn_d128_ranges_prefix", q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride,
-                      k_rstride, vt_bstride, vt_rstride, o_bstride, o_rstride, scale, kv_ranges, max_segments, table_heads, nullptr,
-                      nullptr, 0, false, stream, true, lse_prefix);
+  return ranges_entry("alg_flash_attn_d128_ranges_prefix", Attn128Form::PREFIX,
+                      {q, k, vt, o, batch, heads, Sq, Skv, q_bstride, q_rstride, k_bstride, k_rstride, vt_bstride, vt_rstride, o_bstride,
+                       o_rstride, scale, 1, 0, (hipStream_t)stream, kv_ranges, max_segments, table_heads, nullptr, nullptr, 0,
+                       lse_prefix});
 }
 
 namespace alg {

@@ -48,7 +48,24 @@ const char* alg_last_error(void);
  * ALG_ATTN128_Q64 (1 = the 64-queries-per-wave d = 128 kernel from 4,096 keys on, the default; 2 = for every call it can
  * take; 0 = off: the escape hatch back to the 32-query pipelined kernel), ALG_GEMM_PIPE, ALG_LOWPASS_PATH.  A value must be
  * a whole decimal integer the build knows; anything else (including "off", "1x", an empty string) leaves the default in
- * place. */
+ * place.
+ *
+ * ALG_ATTN128_*: how a d = 128 call is routed.  Every entry checks its arguments, then plans, then launches; the plan is a pure
+ * function of the shape and these two options (KV tiles = ceil(Skv / 64)):
+ *   - causal or kv_group != 1, or an operand beyond 31-bit byte offsets inside one (batch, head) -- (Skv + 64) * k_rstride * 2,
+ *     129 * vt_rstride * 2 or Sq * q_rstride * 2 reaches 2^31 --: the base kernel (attention128.hip);
+ *   - otherwise ALG_ATTN128_Q64 = 1 from 64 KV tiles on, = 2 or 3 from 8 on: the 64-query kernel (3: its generated statement
+ *     off, every tile through the C++ frame; tests), unless its grid exceeds 2^31 - 1;
+ *   - otherwise ALG_ATTN128_PIPE = 1 from 12 KV tiles on: the pipelined 32-query kernel, unless its grid exceeds 2^31 - 1;
+ *   - otherwise the base kernel, whose own grid overflow is ALG_ELIMIT "grid too large".
+ * alg_flash_attn_d128_dual always runs the base kernel; the alg_flash_attn_d128_ranges* entries always run the 64-query frame
+ * (of the option they honour only the value 3) and return ALG_ELIMIT where it cannot address the operands.
+ * The 64-query, the pipelined and the e4m3 kernel need more than 64 KiB of LDS and opt in to it once per device.  A failed
+ * opt-in is ALG_ELAUNCH with the message "<entry>: hipFuncSetAttribute(<bytes> B LDS): <HIP's text>" from every entry -- it is
+ * never answered by running another kernel.  <entry> is the C entry's name, except for the dense entries, whose two routes both
+ * ask for 131,072 B and are named "alg_flash_attn_d128 (64-query kernel)" and "alg_flash_attn_d128 (pipelined kernel)".
+ * (While routing was "try the kernel, 1 = not covered", a failed opt-in sent a dense call on to the next kernel without a word,
+ * a ranged call got ALG_ELIMIT, and alg_flash_attn_d128_fp8 said "cannot reserve <bytes> bytes of LDS".) */
 void alg_reload_env(void);
 
 /* ------------------------------------------------------------------------------------------------

@@ -127,6 +127,30 @@ def test_flash_attn_d128_pipelined_kernel(B, H, Sq, Skv, monkeypatch):
         assert torch.equal(o2, outs["1"])             # deterministic
 
 
+@pytest.mark.parametrize("Skv,forced", [(4096, {"ALG_ATTN128_Q64": "2"}), (4032, {"ALG_ATTN128_Q64": "0"}),
+                                        (704, {"ALG_ATTN128_Q64": "0", "ALG_ATTN128_PIPE": "0"})])
+def test_flash_attn_d128_default_route(Skv, forced, monkeypatch):
+    """Which kernel the default options give a call (attention128.hip: attn128_plan): from 64 KV tiles on the 64-query kernel, from
+    12 on the pipelined 32-query kernel, below that the straight loop -- each observed as bit equality with that kernel forced."""
+    B, H, Sq = 1, 2, 300
+    D = H * 128
+    q, k, v = _rand((B, Sq, D), 11), _rand((B, Skv, D), 12), _rand((B, Skv, D), 13)
+    q[:, : Sq // 2] *= 6.0
+    k[:, Skv // 3] *= 8.0
+    s_pad = (Skv + 63) // 64 * 64
+    vt = make_vt(v, s_pad)
+    outs = []
+    for env in ({}, forced):
+        for name in ("ALG_ATTN128_Q64", "ALG_ATTN128_PIPE"):
+            monkeypatch.delenv(name, raising=False)
+        for name, value in env.items():
+            monkeypatch.setenv(name, value)
+        o = torch.full((B, Sq, D), 7.0, dtype=BF, device=DEV)
+        _lib.flash_attn_d128(q, k, vt, o, B, H, Sq, Skv, Sq * D, D, Skv * D, D, D * s_pad, s_pad, Sq * D, D, 1.0 / math.sqrt(128))
+        outs.append(o)
+    assert torch.equal(outs[0], outs[1])
+
+
 @pytest.mark.parametrize("B,H,Sq,Skv,Skv2", [(1, 2, 300, 512, 257), (2, 3, 777, 257, 512), (1, 1, 31, 64, 1), (1, 2, 1024, 130, 70),
                                                (2, 1, 257, 1, 513)])
 def test_flash_attn_d128_dual_is_two_launches_and_the_add(B, H, Sq, Skv, Skv2):
