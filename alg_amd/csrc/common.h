@@ -31,8 +31,8 @@ enum Opt {
   OPT_GEMM_PIPE,        // ALG_GEMM_PIPE         10 (default since round 6: the asm main loop on v_mfma_f32_16x16x32_bf16) | 9: the asm main
                         //                       loop on 32x32x16 | 6: the 8-wave ping-pong schedule (9 and 6 are bit-identical; 10 sums 32
                         //                       products per instruction: other fp32 rounding points, same error bound)
-  OPT_LOWPASS_PATH,     // ALG_LOWPASS_PATH      0 auto | 1 plane-per-workgroup | 2 lowpass_v2 | 3 lowpass_v3 at any plane
-                        //                       count | 4 global-memory passes (all bit-identical)
+  OPT_LOWPASS_PATH,     // ALG_LOWPASS_PATH      0 auto | 1 plane-per-workgroup | 2 not lowpass_v3 | 3 lowpass_v3 at any plane
+                        //                       count | 4 global-memory passes (all bit-identical; lowpass_host.h: lowpass_plan)
   OPT_COUNT
 };
 int opt(Opt o);

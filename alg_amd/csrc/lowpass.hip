@@ -8,7 +8,7 @@
 // per-output normalisation), so tap sets match ATen's and results agree to fp32 rounding.
 #include <stdlib.h>
 
-#include "common.h"
+#include "lowpass_host.h"
 
 namespace alg {
 
@@ -18,12 +18,6 @@ struct TapTable {
   float* w;     // [n_out][taps]
   int taps;
 };
-
-__host__ __device__ inline int aa_max_taps(int in_size, int out_size) {
-  float scale = (float)in_size / (float)out_size;
-  float support = scale >= 1.0f ? scale : 1.0f;
-  return (int)ceilf(support) * 2 + 1;
-}
 
 // strict fp32, no FMA contraction: __f*_rn intrinsics are never fused
 __device__ void build_taps(const TapTable t, int in_size, int out_size, int tid, int nthreads) {
@@ -165,10 +159,10 @@ __global__ __launch_bounds__(1024) void down_up_kernel(const T* __restrict__ in,
   float* T1 = X + (size_t)H * W;
   float* T2 = T1 + (size_t)H * w1;
   char* p = (char*)(T2 + (size_t)h1 * w1);
-  TapTable dw = carve_taps(p, w1, aa_max_taps(W, w1));   // W  -> w1
-  TapTable dh = carve_taps(p, h1, aa_max_taps(H, h1));   // H  -> h1
-  TapTable uw = carve_taps(p, W, aa_max_taps(w1, W));    // w1 -> W
-  TapTable uh = carve_taps(p, H, aa_max_taps(h1, H));    // h1 -> H
+  TapTable dw = carve_taps(p, w1, aa_taps(W, w1));   // W  -> w1
+  TapTable dh = carve_taps(p, h1, aa_taps(H, h1));   // H  -> h1
+  TapTable uw = carve_taps(p, W, aa_taps(w1, W));    // w1 -> W
+  TapTable uh = carve_taps(p, H, aa_taps(h1, H));    // h1 -> H
 
   build_taps(dw, W, w1, tid, nt);
   build_taps(dh, H, h1, tid, nt);
@@ -194,19 +188,14 @@ static size_t down_up_lds_bytes(int H, int W, int h1, int w1) {
   size_t fl = (size_t)H * W + (size_t)H * w1 + (size_t)h1 * w1;
   size_t b = fl * 4;
   auto tab = [](int n_out, int taps) { return (size_t)n_out * 8 + (size_t)n_out * taps * 4; };
-  b += tab(w1, aa_max_taps(W, w1)) + tab(h1, aa_max_taps(H, h1)) + tab(W, aa_max_taps(w1, W)) +
-       tab(H, aa_max_taps(h1, H));
+  b += tab(w1, aa_taps(W, w1)) + tab(h1, aa_taps(H, h1)) + tab(W, aa_taps(w1, W)) +
+       tab(H, aa_taps(h1, H));
   return (b + 15) & ~(size_t)15;
 }
 
 // ---------------------------------------------------------------------------------------------
 // gaussian blur
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * (n - 1) - i : i;
-}
-
 template <typename T>
 __global__ __launch_bounds__(1024) void gaussian_kernel(const T* __restrict__ in, T* __restrict__ out, int H, int W,
                                                        int ksize, float sigma) {
@@ -268,6 +257,12 @@ __global__ __launch_bounds__(1024) void gaussian_kernel(const T* __restrict__ in
   }
 }
 
+static size_t gaussian_lds_bytes(int H, int W, int ksize) { return (((size_t)2 * H * W + ksize) * 4 + 15) & ~(size_t)15; }
+
+static size_t plane_lds_bytes(const LowpassArgs& a) {
+  return a.filter == LowpassFilter::DOWN_UP ? down_up_lds_bytes(a.H, a.W, a.h1, a.w1) : gaussian_lds_bytes(a.H, a.W, a.ksize);
+}
+
 // threads per plane-workgroup.  Measured (rocprofv3, profiles/): one C2 video (208 planes, a single wave of
 // workgroups) is latency bound -- 1024 threads per plane: 14 us, 256: 24 us; eight videos (1664 planes) are
 // throughput bound and want many small workgroups per CU -- 256 threads: 44 us, 1024: 75 us.
@@ -277,182 +272,185 @@ static int plane_threads(int H, int W, int64_t planes) {
   return n >= 4096 ? 1024 : (n >= 1024 ? 512 : 256);
 }
 
-// planes beyond the LDS budget: same arithmetic through a global workspace (lowpass_big.hip)
-int down_up_big(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype, int round_mid,
-                void* workspace, int64_t workspace_bytes, hipStream_t s);
-int gaussian_big(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma, int dtype,
-                 void* workspace, int64_t workspace_bytes, hipStream_t s);
-int64_t down_up_big_bytes(int64_t planes, int H, int W, int h1, int w1);
-int64_t gaussian_big_bytes(int64_t planes, int H, int W, int ksize);
+// Planes beyond the LDS budget run the same arithmetic through a global workspace (lowpass_big.hip), and so do kernels wider
+// than 255 taps (an integer `lp_blur_kernel_size` on pixel-sized planes; reflect padding needs ksize / 2 < min(H, W), so such
+// planes are at least 128 x 128): the global-memory passes have no tap-count limit.  ALG_LOWPASS_PATH=4: every call.
+static bool takes_global(const LowpassArgs& a, int option) {
+  return option == 4 || plane_lds_bytes(a) > LOWPASS_LDS_CAP || (a.filter == LowpassFilter::GAUSSIAN && a.ksize > 255);
+}
 
-// bandwidth-shaped kernels for 16-byte-granular planes (lowpass_v2.hip); return 1 = shape not covered
-int down_up_v2(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype, int round_mid,
-               const void* tables, hipStream_t s);
-int gaussian_v2(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma, int dtype, hipStream_t s);
-// register-blocked kernels for many-plane batches (lowpass_v3.hip); return 1 = shape not covered
-int gaussian_v3(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma, int dtype, hipStream_t s);
-int down_up_v3(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype, int round_mid,
-               const void* tables, hipStream_t s);
-
-// ALG_LOWPASS_PATH (all paths bit-identical; the tests walk them): 1 = the one-plane-per-workgroup kernels of this file,
-// 4 = LDS-sized planes through the global-memory passes of lowpass_big.hip (2 / 3: see lowpass_v3.hip)
-static bool force_v1() { return opt(OPT_LOWPASS_PATH) == 1; }
-static bool force_global() { return opt(OPT_LOWPASS_PATH) == 4; }
-
-template <typename K>
-static int set_lds_limit(K kernel, size_t bytes) {
-  if (bytes > 160 * 1024) return ALG_ELIMIT;
-  // hipFuncSetAttribute is a per-DEVICE property: the memo is keyed by the current device too (a process that drives
-  // two GPUs launched the > 48 KiB kernels on the second one without the opt-in); an unknown device (-1) is never memoised
-  static thread_local const void* last_fn = nullptr;
-  static thread_local size_t last_bytes = 0;
-  static thread_local int last_dev = -2;
-  const int dev = current_device_slot();
-  if (bytes > 48 * 1024 && !(last_fn == (const void*)kernel && last_bytes >= bytes && dev >= 0 && last_dev == dev)) {
-    last_fn = (const void*)kernel;
-    last_bytes = bytes;
-    last_dev = dev;
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", bytes, hipGetErrorString(e));
-      return ALG_ELAUNCH;
+// ---- check: every refusal of alg_down_up and alg_gaussian_blur, once, in the order the entries have always run them: the
+// arguments (lowpass_check), then, once the call is planned, what its route asks of it (lowpass_check_route).
+// ALG_OK with planes == 0 is the empty batch: nothing to do (pointers may be null), and the entry returns.
+int lowpass_check(const LowpassArgs& a, const char* entry) {
+  const bool down_up = a.filter == LowpassFilter::DOWN_UP;
+  if (a.planes == 0 && a.H > 0 && a.W > 0) return ALG_OK;
+  if (down_up) {
+    if (!a.in || !a.out || a.planes < 0 || a.H <= 0 || a.W <= 0 || a.h1 <= 0 || a.w1 <= 0) {
+      set_error("%s: bad argument (planes=%lld H=%d W=%d h1=%d w1=%d)", entry, (long long)a.planes, a.H, a.W, a.h1, a.w1);
+      return ALG_EINVAL;
+    }
+  } else {
+    if (!a.in || !a.out || a.planes < 0 || a.H <= 0 || a.W <= 0) {
+      set_error("%s: bad argument (planes=%lld H=%d W=%d)", entry, (long long)a.planes, a.H, a.W);
+      return ALG_EINVAL;
+    }
+    if (a.ksize <= 0 || (a.ksize & 1) == 0) {
+      set_error("%s: kernel size must be odd and positive, got %d", entry, a.ksize);
+      return ALG_EINVAL;
+    }
+    if (!(a.sigma > 0.0f)) {
+      set_error("%s: sigma must be positive, got %g", entry, (double)a.sigma);
+      return ALG_EINVAL;
+    }
+    if (a.ksize / 2 >= a.H || a.ksize / 2 >= a.W) {
+      set_error("%s: reflect padding needs ksize/2 < min(H, W) (ksize=%d H=%d W=%d)", entry, a.ksize, a.H, a.W);
+      return ALG_EINVAL;
     }
   }
+  if (a.dtype != ALG_F32 && a.dtype != ALG_BF16) {
+    set_error("%s: unsupported dtype code %d", entry, a.dtype);
+    return ALG_EINVAL;
+  }
+  if (a.in == a.out) {
+    set_error("%s: in and out must not alias", entry);
+    return ALG_EINVAL;
+  }
   return ALG_OK;
+}
+
+int lowpass_check_route(const LowpassArgs& a, const LowpassPlan& pl, int option, const char* entry) {
+  if (pl.route == LowpassRoute::GLOBAL) {
+    if (!pl.within_limits) {
+      set_error("%s: %lld planes of %dx%d exceed the global-memory path's grid", entry, (long long)a.planes, a.H, a.W);
+      return ALG_ELIMIT;
+    }
+    // the intermediates of the global-memory passes live in a workspace the CALLER provides: the library never allocates
+    if (!a.workspace || ((uintptr_t)a.workspace & 15) || a.workspace_bytes < pl.workspace) {
+      set_error("%s: this shape runs through global-memory passes and needs a 16-byte aligned workspace of %zu bytes "
+                "(%s_workspace_bytes); got %p / %lld bytes", entry, (size_t)pl.workspace, entry, a.workspace,
+                (long long)a.workspace_bytes);
+      return ALG_EINVAL;
+    }
+  } else if (a.filter == LowpassFilter::DOWN_UP && option != 1 && a.tables && ((uintptr_t)a.tables & 15)) {
+    set_error("%s: tables must be 16-byte aligned", entry);   // (asked only where a kernel may read them)
+    return ALG_EINVAL;
+  }
+  return ALG_OK;
+}
+
+// ---- plan: which kernel a checked call runs.  Pure: the operands, the device's CU count and ALG_LOWPASS_PATH --
+// 0 auto | 1 the plane-per-workgroup kernels of this file | 2 not the register-blocked kernels | 3 the register-blocked kernels
+// at any plane count | 4 the global-memory passes for LDS-sized planes too (all routes are bit-identical; the tests walk them).
+// A down_up call without the caller's tap tables runs the kernels of this file, which build them in LDS per plane.
+LowpassPlan lowpass_plan(const LowpassArgs& a, int cus, int option) {
+  LowpassPlan pl = {};
+  pl.cus = cus;
+  pl.within_limits = true;
+  if (takes_global(a, option)) {
+    pl.route = LowpassRoute::GLOBAL;
+    pl.threads = 256;
+    pl.workspace = lowpass_global_bytes(a);
+    pl.within_limits = lowpass_global_grid_fits(a);
+    return pl;
+  }
+  if (option != 1 && (a.filter == LowpassFilter::GAUSSIAN || a.tables)) {
+    if (lowpass_blocked_covers(a, cus, option, &pl)) return pl;
+    if (lowpass_persistent_covers(a, cus, &pl)) return pl;
+  }
+  pl.route = LowpassRoute::PLANE;
+  pl.threads = plane_threads(a.H, a.W, a.planes);
+  pl.lds = plane_lds_bytes(a);
+  return pl;
 }
 
 }  // namespace alg
 
 using namespace alg;
 
-static bool global_path_down_up(int H, int W, int h1, int w1) {
-  return down_up_lds_bytes(H, W, h1, w1) > 160 * 1024 || force_global();
+// ---- launch: the plane-per-workgroup kernels, one workgroup per plane
+template <typename T, typename... Filter>
+static int launch_plane_kernel(PerDeviceOnce& once, void (*kernel)(const T*, T*, int, int, Filter...), const LowpassArgs& a,
+                               const LowpassPlan& pl, Filter... filter) {
+  const char* who = lowpass_who(a, pl.route);
+  const int rc = lowpass_opt_in(once, (const void*)kernel, who, a);
+  if (rc != ALG_OK) return rc;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)a.planes), dim3(pl.threads), pl.lds, a.stream, (const T*)a.in, (T*)a.out, a.H, a.W,
+                     filter...);
+  return check_launch(who);
 }
 
-static size_t gaussian_lds_bytes(int H, int W, int ksize) { return (((size_t)2 * H * W + ksize) * 4 + 15) & ~(size_t)15; }
+static int launch_plane(const LowpassArgs& a, const LowpassPlan& pl) {
+  static PerDeviceOnce once[4];
+  const bool f32 = a.dtype == ALG_F32;
+  // (the four instantiations are named in the order the object has always held them: hipcc emits kernels as a file names them)
+  if (a.filter == LowpassFilter::DOWN_UP)
+    return f32 ? launch_plane_kernel(once[0], down_up_kernel<float>, a, pl, a.h1, a.w1, a.round_mid)
+               : launch_plane_kernel(once[1], down_up_kernel<bf16_t>, a, pl, a.h1, a.w1, a.round_mid);
+  return f32 ? launch_plane_kernel(once[2], gaussian_kernel<float>, a, pl, a.ksize, a.sigma)
+             : launch_plane_kernel(once[3], gaussian_kernel<bf16_t>, a, pl, a.ksize, a.sigma);
+}
 
-static bool global_path_gaussian(int H, int W, int ksize) {
-  return gaussian_lds_bytes(H, W, ksize) > 160 * 1024 || ksize > 255 || force_global();
+// device_cus() of the call's device, remembered per device slot: one video is launch-bound, and a second device lookup per
+// call (device_cus() makes its own) was measured as +0.4 us on a 10 us call (profiles/lowpass_host_refactor.txt)
+static int cus_of(int slot) {
+  static std::atomic<int> memo[64];
+  if (slot < 0) return device_cus();
+  int cus = memo[slot].load(std::memory_order_relaxed);
+  if (!cus) memo[slot].store(cus = device_cus(), std::memory_order_relaxed);
+  return cus;
+}
+
+static int filter_entry(LowpassArgs& a, const char* entry) {
+  int rc = lowpass_check(a, entry);
+  if (rc != ALG_OK || a.planes == 0) return rc;
+  const int option = opt(OPT_LOWPASS_PATH);
+  a.device = current_device_slot();
+  const LowpassPlan pl = lowpass_plan(a, cus_of(a.device), option);
+  rc = lowpass_check_route(a, pl, option, entry);
+  if (rc != ALG_OK) return rc;
+  switch (pl.route) {
+    case LowpassRoute::GLOBAL: return launch_lowpass_global(a, pl);
+    case LowpassRoute::BLOCKED: return launch_lowpass_blocked(a, pl);
+    case LowpassRoute::PERSISTENT: return launch_lowpass_persistent(a, pl);
+    default: return launch_plane(a, pl);
+  }
+}
+
+// The two workspace queries: only the global-memory passes have a workspace, and whether a call takes them (the first question
+// of lowpass_plan) depends on its shape and the option alone
+static LowpassArgs shape_only(LowpassFilter filter, int64_t planes, int H, int W) {
+  LowpassArgs a = {};
+  a.filter = filter, a.planes = planes, a.H = H, a.W = W, a.dtype = ALG_F32;
+  return a;
 }
 
 extern "C" int64_t alg_down_up_workspace_bytes(int64_t planes, int H, int W, int h1, int w1) {
-  if (planes <= 0 || H <= 0 || W <= 0 || h1 <= 0 || w1 <= 0 || !global_path_down_up(H, W, h1, w1)) return 0;
-  return down_up_big_bytes(planes, H, W, h1, w1);
+  if (planes <= 0 || H <= 0 || W <= 0 || h1 <= 0 || w1 <= 0) return 0;
+  LowpassArgs a = shape_only(LowpassFilter::DOWN_UP, planes, H, W);
+  a.h1 = h1, a.w1 = w1;
+  return takes_global(a, opt(OPT_LOWPASS_PATH)) ? lowpass_global_bytes(a) : 0;
 }
 
 extern "C" int64_t alg_gaussian_blur_workspace_bytes(int64_t planes, int H, int W, int ksize) {
-  if (planes <= 0 || H <= 0 || W <= 0 || ksize <= 0 || !global_path_gaussian(H, W, ksize)) return 0;
-  return gaussian_big_bytes(planes, H, W, ksize);
+  if (planes <= 0 || H <= 0 || W <= 0 || ksize <= 0) return 0;
+  LowpassArgs a = shape_only(LowpassFilter::GAUSSIAN, planes, H, W);
+  a.ksize = ksize;
+  return takes_global(a, opt(OPT_LOWPASS_PATH)) ? lowpass_global_bytes(a) : 0;
 }
 
 extern "C" int alg_down_up(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype,
                            int round_intermediate, const void* tables, void* workspace, int64_t workspace_bytes,
                            void* stream) {
-  if (planes == 0 && H > 0 && W > 0) return ALG_OK;  // empty batch: nothing to do (pointers may be null)
-  if (!in || !out || planes < 0 || H <= 0 || W <= 0 || h1 <= 0 || w1 <= 0) {
-    set_error("alg_down_up: bad argument (planes=%lld H=%d W=%d h1=%d w1=%d)", (long long)planes, H, W, h1, w1);
-    return ALG_EINVAL;
-  }
-  if (dtype != ALG_F32 && dtype != ALG_BF16) {
-    set_error("alg_down_up: unsupported dtype code %d", dtype);
-    return ALG_EINVAL;
-  }
-  if (in == out) {
-    set_error("alg_down_up: in and out must not alias");
-    return ALG_EINVAL;
-  }
-  if (planes == 0) return ALG_OK;
-  const size_t lds = down_up_lds_bytes(H, W, h1, w1);
-  hipStream_t s = (hipStream_t)stream;
-  if (global_path_down_up(H, W, h1, w1))
-    return down_up_big(in, out, planes, H, W, h1, w1, dtype, round_intermediate ? 1 : 0, workspace, workspace_bytes, s);
-  int rc;
-  if (!force_v1() && tables) {   // without the caller's tap tables: the kernels below, which build them in LDS per plane
-    if ((uintptr_t)tables & 15) {
-      set_error("alg_down_up: tables must be 16-byte aligned");
-      return ALG_EINVAL;
-    }
-    rc = down_up_v3(in, out, planes, H, W, h1, w1, dtype, (dtype == ALG_BF16 && round_intermediate) ? 1 : 0, tables, s);
-    if (rc <= 0) return rc;
-    rc = down_up_v2(in, out, planes, H, W, h1, w1, dtype, (dtype == ALG_BF16 && round_intermediate) ? 1 : 0, tables, s);
-    if (rc <= 0) return rc;
-  }
-  if (dtype == ALG_F32) {
-    rc = set_lds_limit(down_up_kernel<float>, lds);
-    if (rc == ALG_OK)
-      hipLaunchKernelGGL(down_up_kernel<float>, dim3((unsigned)planes), dim3(plane_threads(H, W, planes)), lds, s,
-                         (const float*)in, (float*)out, H, W, h1, w1, 0);
-  } else {
-    rc = set_lds_limit(down_up_kernel<bf16_t>, lds);
-    if (rc == ALG_OK)
-      hipLaunchKernelGGL(down_up_kernel<bf16_t>, dim3((unsigned)planes), dim3(plane_threads(H, W, planes)), lds, s,
-                         (const bf16_t*)in, (bf16_t*)out, H, W, h1, w1, round_intermediate ? 1 : 0);
-  }
-  if (rc == ALG_ELIMIT) {
-    set_error("alg_down_up: plane %dx%d (->%dx%d) needs %zu B of LDS (> 160 KiB); the LDS-resident kernel "
-              "covers latent-sized planes only", H, W, h1, w1, lds);
-    return rc;
-  }
-  if (rc != ALG_OK) return rc;
-  return check_launch("alg_down_up");
+  LowpassArgs a = {LowpassFilter::DOWN_UP, in, out, planes, H, W, dtype, (hipStream_t)stream, 0, workspace, workspace_bytes};
+  a.h1 = h1, a.w1 = w1, a.tables = tables;
+  a.round_mid = (dtype == ALG_BF16 && round_intermediate) ? 1 : 0;
+  return filter_entry(a, "alg_down_up");
 }
 
 extern "C" int alg_gaussian_blur(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma,
                                  int dtype, void* workspace, int64_t workspace_bytes, void* stream) {
-  if (planes == 0 && H > 0 && W > 0) return ALG_OK;
-  if (!in || !out || planes < 0 || H <= 0 || W <= 0) {
-    set_error("alg_gaussian_blur: bad argument (planes=%lld H=%d W=%d)", (long long)planes, H, W);
-    return ALG_EINVAL;
-  }
-  if (ksize <= 0 || (ksize & 1) == 0) {
-    set_error("alg_gaussian_blur: kernel size must be odd and positive, got %d", ksize);
-    return ALG_EINVAL;
-  }
-  if (!(sigma > 0.0f)) {
-    set_error("alg_gaussian_blur: sigma must be positive, got %g", (double)sigma);
-    return ALG_EINVAL;
-  }
-  if (ksize / 2 >= H || ksize / 2 >= W) {
-    set_error("alg_gaussian_blur: reflect padding needs ksize/2 < min(H, W) (ksize=%d H=%d W=%d)", ksize, H, W);
-    return ALG_EINVAL;
-  }
-  if (dtype != ALG_F32 && dtype != ALG_BF16) {
-    set_error("alg_gaussian_blur: unsupported dtype code %d", dtype);
-    return ALG_EINVAL;
-  }
-  if (in == out) {
-    set_error("alg_gaussian_blur: in and out must not alias");
-    return ALG_EINVAL;
-  }
-  if (planes == 0) return ALG_OK;
-  const size_t lds = gaussian_lds_bytes(H, W, ksize);
-  hipStream_t s = (hipStream_t)stream;
-  // kernels wider than 255 taps (an integer `lp_blur_kernel_size` on pixel-sized planes; reflect padding needs ksize / 2 <
-  // min(H, W), so such planes are at least 128 x 128) always take the global-memory passes, which have no tap-count limit
-  if (global_path_gaussian(H, W, ksize))
-    return gaussian_big(in, out, planes, H, W, ksize, sigma, dtype, workspace, workspace_bytes, s);
-  int rc;
-  if (!force_v1()) {
-    rc = gaussian_v3(in, out, planes, H, W, ksize, sigma, dtype, s);
-    if (rc <= 0) return rc;
-    rc = gaussian_v2(in, out, planes, H, W, ksize, sigma, dtype, s);
-    if (rc <= 0) return rc;
-  }
-  if (dtype == ALG_F32) {
-    rc = set_lds_limit(gaussian_kernel<float>, lds);
-    if (rc == ALG_OK)
-      hipLaunchKernelGGL(gaussian_kernel<float>, dim3((unsigned)planes), dim3(plane_threads(H, W, planes)), lds, s,
-                         (const float*)in, (float*)out, H, W, ksize, sigma);
-  } else {
-    rc = set_lds_limit(gaussian_kernel<bf16_t>, lds);
-    if (rc == ALG_OK)
-      hipLaunchKernelGGL(gaussian_kernel<bf16_t>, dim3((unsigned)planes), dim3(plane_threads(H, W, planes)), lds, s,
-                         (const bf16_t*)in, (bf16_t*)out, H, W, ksize, sigma);
-  }
-  if (rc == ALG_ELIMIT) {
-    set_error("alg_gaussian_blur: plane %dx%d needs %zu B of LDS (> 160 KiB)", H, W, lds);
-    return rc;
-  }
-  if (rc != ALG_OK) return rc;
-  return check_launch("alg_gaussian_blur");
+  LowpassArgs a = {LowpassFilter::GAUSSIAN, in, out, planes, H, W, dtype, (hipStream_t)stream, 0, workspace, workspace_bytes};
+  a.ksize = ksize, a.sigma = sigma;
+  return filter_entry(a, "alg_gaussian_blur");
 }

@@ -3,7 +3,7 @@
 // arithmetic, operation for operation (strict fp32 tap weights, acc = s0*w0 then fma over ascending taps, fp32
 // intermediates, optional bf16 rounding between the two interpolate calls), as separable passes through a stream-ordered
 // global workspace; tap weights are recomputed per output instead of tabulated.
-#include "common.h"
+#include "lowpass_host.h"
 
 namespace alg {
 namespace big {
@@ -78,11 +78,6 @@ __global__ __launch_bounds__(256) void cols_kernel(const float* __restrict__ src
   store_from_float<TO>(dst, (p * n_out + o) * cols + c, acc);
 }
 
-__device__ __forceinline__ int reflect(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * (n - 1) - i : i;
-}
-
 // g[j] = exp(-0.5 (x / sigma)^2) / sum, as lowpass.hip's gaussian_kernel builds it
 __global__ void gauss_weights_kernel(float* g, int ksize, float sigma) {   // one workgroup, any ksize
   const int tid = threadIdx.x;
@@ -124,37 +119,35 @@ __global__ __launch_bounds__(256) void gauss_cols_kernel(const float* __restrict
   store_from_float<TO>(dst, (p * H + y) * W + x, acc);
 }
 
-// The intermediates of the global-memory passes live in a workspace the CALLER provides (alg_*_workspace_bytes): the
-// library never allocates.
-static int ws_check(float** p, size_t floats, void* workspace, int64_t workspace_bytes, const char* who) {
-  if (!workspace || ((uintptr_t)workspace & 15) || workspace_bytes < (int64_t)(floats * sizeof(float))) {
-    set_error("%s: this shape runs through global-memory passes and needs a 16-byte aligned workspace of %zu bytes "
-              "(%s_workspace_bytes); got %p / %lld bytes", who, floats * sizeof(float), who, workspace,
-              (long long)workspace_bytes);
-    return ALG_EINVAL;
-  }
-  *p = (float*)workspace;
-  return ALG_OK;
-}
-
 }  // namespace big
 
+// ---- the plan's side: the workspace (T1 | T2 | T3 of a down_up, the row pass and the taps of a blur) and the grid's limit:
+// planes ride in gridDim.z, output rows in gridDim.y
+int64_t lowpass_global_bytes(const LowpassArgs& a) {
+  if (a.filter == LowpassFilter::DOWN_UP)
+    return (int64_t)sizeof(float) * a.planes * ((int64_t)a.H * a.w1 + (int64_t)a.h1 * a.w1 + (int64_t)a.h1 * a.W);
+  return (int64_t)sizeof(float) * (a.planes * a.H * a.W + ((a.ksize + 255) & ~255));
+}
+
+bool lowpass_global_grid_fits(const LowpassArgs& a) {
+  return a.planes <= 65535 && a.H <= 65535 && (a.filter == LowpassFilter::GAUSSIAN || a.h1 <= 65535);
+}
+
+// ---- launch: the workspace was checked (lowpass_check)
 template <typename T>
-static int down_up_big_t(const T* in, T* out, int64_t planes, int H, int W, int h1, int w1, int round_mid, void* workspace,
-                         int64_t workspace_bytes, hipStream_t s) {
-  if (planes > 65535 || H > 65535 || h1 > 65535) {
-    set_error("alg_down_up: %lld planes of %dx%d exceed the global-memory path's grid", (long long)planes, H, W);
-    return ALG_ELIMIT;
-  }
-  float* ws = nullptr;
-  const size_t n1 = (size_t)planes * H * w1, n2 = (size_t)planes * h1 * w1, n3 = (size_t)planes * h1 * W;
-  if (int rc = big::ws_check(&ws, n1 + n2 + n3, workspace, workspace_bytes, "alg_down_up")) return rc;
-  float *T1 = ws, *T2 = ws + n1, *T3 = T2 + n2;
+static int down_up_big_t(const LowpassArgs& a, const char* who) {
+  const T* in = (const T*)a.in;
+  T* out = (T*)a.out;
+  const int64_t planes = a.planes;
+  const int H = a.H, W = a.W, h1 = a.h1, w1 = a.w1;
+  hipStream_t s = a.stream;
+  const size_t n1 = (size_t)planes * H * w1, n2 = (size_t)planes * h1 * w1;
+  float *T1 = (float*)a.workspace, *T2 = T1 + n1, *T3 = T2 + n2;
   const int rpb = 8;
   // first interpolate call (lp:53): W pass, H pass (result optionally rounded to bf16 like the tensor in between)
   hipLaunchKernelGGL(big::rows_kernel<T>, dim3((w1 + 255) / 256, (H + rpb - 1) / rpb, (unsigned)planes), dim3(256), 0, s,
                      in, T1, H, W, w1, rpb);
-  if (round_mid)
+  if (a.round_mid)
     hipLaunchKernelGGL((big::cols_kernel<float, true>), dim3((w1 + 255) / 256, h1, (unsigned)planes), dim3(256), 0, s,
                        (const float*)T1, T2, H, h1, w1);
   else
@@ -165,47 +158,28 @@ static int down_up_big_t(const T* in, T* out, int64_t planes, int H, int W, int 
                      s, (const float*)T2, T3, h1, w1, W, rpb);
   hipLaunchKernelGGL((big::cols_kernel<T, false>), dim3((W + 255) / 256, H, (unsigned)planes), dim3(256), 0, s,
                      (const float*)T3, out, h1, H, W);
-  return check_launch("alg_down_up");
-}
-
-int64_t down_up_big_bytes(int64_t planes, int H, int W, int h1, int w1) {
-  return (int64_t)sizeof(float) * planes * ((int64_t)H * w1 + (int64_t)h1 * w1 + (int64_t)h1 * W);
-}
-
-int64_t gaussian_big_bytes(int64_t planes, int H, int W, int ksize) {
-  return (int64_t)sizeof(float) * (planes * H * W + ((ksize + 255) & ~255));
-}
-
-int down_up_big(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype, int round_mid,
-                void* workspace, int64_t workspace_bytes, hipStream_t s) {
-  if (dtype == ALG_F32)
-    return down_up_big_t<float>((const float*)in, (float*)out, planes, H, W, h1, w1, 0, workspace, workspace_bytes, s);
-  return down_up_big_t<bf16_t>((const bf16_t*)in, (bf16_t*)out, planes, H, W, h1, w1, round_mid, workspace, workspace_bytes, s);
+  return check_launch(who);
 }
 
 template <typename T>
-static int gaussian_big_t(const T* in, T* out, int64_t planes, int H, int W, int ksize, float sigma, void* workspace,
-                          int64_t workspace_bytes, hipStream_t s) {
-  if (planes > 65535 || H > 65535) {
-    set_error("alg_gaussian_blur: %lld planes of %dx%d exceed the global-memory path's grid", (long long)planes, H, W);
-    return ALG_ELIMIT;
-  }
-  float* ws = nullptr;
-  const size_t n = (size_t)planes * H * W;
-  if (int rc = big::ws_check(&ws, n + (size_t)((ksize + 255) & ~255), workspace, workspace_bytes, "alg_gaussian_blur")) return rc;
-  float* g = ws + n;
-  hipLaunchKernelGGL(big::gauss_weights_kernel, dim3(1), dim3(256), 0, s, g, ksize, sigma);
-  const dim3 grid((W + 255) / 256, H, (unsigned)planes);
-  hipLaunchKernelGGL(big::gauss_rows_kernel<T>, grid, dim3(256), 0, s, in, ws, (const float*)g, H, W, ksize);
-  hipLaunchKernelGGL(big::gauss_cols_kernel<T>, grid, dim3(256), 0, s, (const float*)ws, out, (const float*)g, H, W, ksize);
-  return check_launch("alg_gaussian_blur");
+static int gaussian_big_t(const LowpassArgs& a, const char* who) {
+  const int H = a.H, W = a.W, ksize = a.ksize;
+  hipStream_t s = a.stream;
+  float* ws = (float*)a.workspace;
+  float* g = ws + (size_t)a.planes * H * W;
+  hipLaunchKernelGGL(big::gauss_weights_kernel, dim3(1), dim3(256), 0, s, g, ksize, a.sigma);
+  const dim3 grid((W + 255) / 256, H, (unsigned)a.planes);
+  hipLaunchKernelGGL(big::gauss_rows_kernel<T>, grid, dim3(256), 0, s, (const T*)a.in, ws, (const float*)g, H, W, ksize);
+  hipLaunchKernelGGL(big::gauss_cols_kernel<T>, grid, dim3(256), 0, s, (const float*)ws, (T*)a.out, (const float*)g, H, W,
+                     ksize);
+  return check_launch(who);
 }
 
-int gaussian_big(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma, int dtype,
-                 void* workspace, int64_t workspace_bytes, hipStream_t s) {
-  if (dtype == ALG_F32)
-    return gaussian_big_t<float>((const float*)in, (float*)out, planes, H, W, ksize, sigma, workspace, workspace_bytes, s);
-  return gaussian_big_t<bf16_t>((const bf16_t*)in, (bf16_t*)out, planes, H, W, ksize, sigma, workspace, workspace_bytes, s);
+int launch_lowpass_global(const LowpassArgs& a, const LowpassPlan& pl) {
+  const char* who = lowpass_who(a, pl.route);
+  const bool f32 = a.dtype == ALG_F32;
+  if (a.filter == LowpassFilter::DOWN_UP) return f32 ? down_up_big_t<float>(a, who) : down_up_big_t<bf16_t>(a, who);
+  return f32 ? gaussian_big_t<float>(a, who) : gaussian_big_t<bf16_t>(a, who);
 }
 
 }  // namespace alg

@@ -13,14 +13,13 @@
 //   * results are staged in LDS as the output dtype and leave in 16-byte stores (the per-element 2-byte stores of the
 //     column pass were 8x the store instructions).
 //
-// Planes whose byte size is not a multiple of 16 (or misaligned bases) take the original kernels.
+// Planes whose byte size is not a multiple of 16 (or misaligned bases) take the original kernels (lowpass_persistent_covers).
 #include <algorithm>
 
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
-#include "lowpass_tabs.h"
+#include "lowpass_host.h"
 
 namespace alg {
 namespace v2 {
@@ -343,11 +342,6 @@ __global__ __launch_bounds__(NT, WPS) void down_up_v2_kernel(const T* __restrict
 // ---------------------------------------------------------------------------------------------------------------------
 // gaussian blur: reflect-indexed separable passes, taps in registers, same skeleton
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect(int i, int n) {
-  i = i < 0 ? -i : i;
-  return i >= n ? 2 * (n - 1) - i : i;
-}
-
 struct GArgs {
   int H, W, ksize;
   float sigma;
@@ -479,147 +473,132 @@ __global__ __launch_bounds__(NT, WPS) void gaussian_v2_kernel(const T* __restric
   }
 }
 
-static int num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
+// The kernel arguments of a call, and the LDS they stand for
+static size_t du_args(const LowpassArgs& a, DUArgs* k) {
+  const int H = a.H, W = a.W, h1 = a.h1, w1 = a.w1;
+  k->H = H, k->W = W, k->h1 = h1, k->w1 = w1, k->round_mid = a.round_mid, k->planes = a.planes;
+  k->tabs = layout(H, W, h1, w1);
+  const size_t bytes = (size_t)H * W * lowpass_esize(a);
+  const size_t stage = ((size_t)h1 * W + 3) / 4 * 4 + (bytes + 3) / 4;          // T3 + staged output, in floats
+  const size_t a_fl = (std::max((size_t)H * W, stage) + 3) / 4 * 4;
+  k->a_floats = (int)a_fl;
+  // + 16 floats of slack: the batched tap reads run up to 11 floats past a row's last tap
+  return (a_fl + (size_t)H * w1 + (((size_t)h1 * w1 + 3) & ~(size_t)3) + k->tabs.words + 16) * 4;
 }
 
-// Geometry.  Few planes (at most two per CU): a plane's latency is what counts -> as many threads per plane as the
-// plane-per-workgroup kernels used.  Many planes: the kernel is latency-bound per workgroup (six barrier-separated phases
-// per plane), so throughput comes from WAVES PER CU: the thread count is the smallest of 256 / 512 / 1024 that reaches the
-// most resident waves given the LDS the shape needs (all variants are compiled for 8 waves per SIMD: <= 64 VGPRs).
-struct Geo {
-  int threads, pre;
-  unsigned grid;
-};
+static size_t g_lds(const LowpassArgs& a) {
+  const size_t n4 = ((size_t)a.H * a.W + 3) & ~(size_t)3;
+  return ((2 * n4 + a.ksize) * 4 + 15) & ~(size_t)15;
+}
 
-static bool geometry(size_t bytes, int n, int64_t planes, size_t lds, int wps_small, int wps_1024, Geo* g) {
-  const int cus = num_cus();
+// Geometry.  Few planes (at most two per CU): a plane's own latency is the whole run time and the one-plane-per-workgroup
+// kernels of lowpass.hip are as fast or faster (measured: C2 one video 12.9 vs 16.6 us) -> not covered here.  Many planes: the
+// kernel is latency-bound per workgroup (six barrier-separated phases per plane), so throughput comes from WAVES PER CU: the
+// thread count is the smallest of 256 / 512 / 1024 that reaches the most resident waves given the LDS the shape needs (all
+// variants are compiled for 8 waves per SIMD: <= 64 VGPRs).  The grid is one resident round: CUs x workgroups that fit.
+static bool geometry(size_t bytes, int64_t planes, size_t lds, int wps_small, int wps_1024, int cus, LowpassPlan* pl) {
+  if (planes <= 2 * (int64_t)cus) return false;
   int best_t = 0, best_waves = -1, best_wgs = 1;
   for (int t : {256, 512, 1024}) {
     const size_t p = (bytes + (size_t)t * 16 - 1) / ((size_t)t * 16);
     if (p > 4) continue;
-    int wgs = (int)((160 * 1024) / lds);
+    int wgs = (int)(LOWPASS_LDS_CAP / lds);
     wgs = std::min(std::min(wgs, (t == 1024 ? wps_1024 : wps_small) * 256 / t), 8);   // LDS, registers, hardware slots
     if (wgs < 1) continue;
-    // at most two planes per CU: a plane's own latency is the whole run time and the one-plane-per-workgroup kernels of
-    // lowpass.hip are as fast or faster (measured: C2 one video 12.9 vs 16.6 us) -> not covered here
-    if (planes <= 2 * (int64_t)cus) return false;
     const int waves = wgs * t / 64;
     if (waves > best_waves) best_waves = waves, best_t = t, best_wgs = wgs;
   }
   if (!best_t) return false;
-  g->threads = best_t;
-  g->pre = (int)((bytes + (size_t)best_t * 16 - 1) / ((size_t)best_t * 16));
-  const int64_t slots = (int64_t)cus * best_wgs;
-  g->grid = (unsigned)(planes < slots ? planes : slots);
+  pl->route = LowpassRoute::PERSISTENT;
+  pl->threads = best_t;
+  pl->variant = (int)((bytes + (size_t)best_t * 16 - 1) / ((size_t)best_t * 16));
+  pl->lds = lds;
+  pl->wgs_per_cu = best_wgs;
   return true;
 }
 
-template <typename K>
-static int set_lds(K kernel, size_t bytes) {
-  if (bytes > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) {
-      set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", bytes, hipGetErrorString(e));
-      return ALG_ELAUNCH;
-    }
-  }
-  return ALG_OK;
-}
-
 template <typename T, int PRE, int NT>
-static int launch_du(const T* in, T* out, const uint32_t* blob, const DUArgs& a, size_t lds, unsigned grid, hipStream_t s) {
+static int launch_du(const LowpassArgs& a, const LowpassPlan& pl, const DUArgs& k) {
   constexpr int WPS = NT == 1024 ? 4 : 6;   // 76-92 VGPRs: six waves per SIMD for the 256 / 512-thread forms
-  int rc = set_lds(down_up_v2_kernel<T, PRE, NT, WPS>, lds);
+  static PerDeviceOnce once;
+  const char* who = lowpass_who(a, pl.route);
+  const int rc = lowpass_opt_in(once, (const void*)down_up_v2_kernel<T, PRE, NT, WPS>, who, a);
   if (rc != ALG_OK) return rc;
-  hipLaunchKernelGGL((down_up_v2_kernel<T, PRE, NT, WPS>), dim3(grid), dim3(NT), lds, s, in, out, blob, a);
-  return check_launch("alg_down_up");
+  hipLaunchKernelGGL((down_up_v2_kernel<T, PRE, NT, WPS>), dim3(lowpass_persistent_grid(a, pl, pl.wgs_per_cu)), dim3(NT),
+                     pl.lds, a.stream, (const T*)a.in, (T*)a.out, (const uint32_t*)a.tables, k);
+  return check_launch(who);
 }
 
 template <typename T, int PRE, int NT>
-static int launch_g(const T* in, T* out, const GArgs& a, size_t lds, unsigned grid, hipStream_t s) {
+static int launch_g(const LowpassArgs& a, const LowpassPlan& pl, const GArgs& k) {
   constexpr int WPS = 8;                    // <= 47 VGPRs
-  int rc = set_lds(gaussian_v2_kernel<T, PRE, NT, WPS>, lds);
+  static PerDeviceOnce once;
+  const char* who = lowpass_who(a, pl.route);
+  const int rc = lowpass_opt_in(once, (const void*)gaussian_v2_kernel<T, PRE, NT, WPS>, who, a);
   if (rc != ALG_OK) return rc;
-  hipLaunchKernelGGL((gaussian_v2_kernel<T, PRE, NT, WPS>), dim3(grid), dim3(NT), lds, s, in, out, a);
-  return check_launch("alg_gaussian_blur");
+  hipLaunchKernelGGL((gaussian_v2_kernel<T, PRE, NT, WPS>), dim3(lowpass_persistent_grid(a, pl, pl.wgs_per_cu)), dim3(NT),
+                     pl.lds, a.stream, (const T*)a.in, (T*)a.out, k);
+  return check_launch(who);
 }
 
 // (threads, prefetch registers) -> instantiation
-#define ALG_V2_DISPATCH(FN, T, ...)                                                      \
-  switch (geo.threads * 8 + geo.pre) {                                                   \
-    case 256 * 8 + 1: return FN<T, 1, 256>(__VA_ARGS__);                                 \
-    case 256 * 8 + 2: return FN<T, 2, 256>(__VA_ARGS__);                                 \
-    case 256 * 8 + 3: return FN<T, 3, 256>(__VA_ARGS__);                                 \
-    case 256 * 8 + 4: return FN<T, 4, 256>(__VA_ARGS__);                                 \
-    case 512 * 8 + 1: return FN<T, 1, 512>(__VA_ARGS__);                                 \
-    case 512 * 8 + 2: return FN<T, 2, 512>(__VA_ARGS__);                                 \
-    case 512 * 8 + 3: return FN<T, 3, 512>(__VA_ARGS__);                                 \
-    case 512 * 8 + 4: return FN<T, 4, 512>(__VA_ARGS__);                                 \
-    case 1024 * 8 + 1: return FN<T, 1, 1024>(__VA_ARGS__);                               \
-    case 1024 * 8 + 2: return FN<T, 2, 1024>(__VA_ARGS__);                               \
-    case 1024 * 8 + 3: return FN<T, 3, 1024>(__VA_ARGS__);                               \
-    default: return FN<T, 4, 1024>(__VA_ARGS__);                                         \
+#define ALG_V2_DISPATCH(FN, T)                                                           \
+  switch (pl.threads * 8 + pl.variant) {                                                 \
+    case 256 * 8 + 1: return FN<T, 1, 256>(a, pl, k);                                    \
+    case 256 * 8 + 2: return FN<T, 2, 256>(a, pl, k);                                    \
+    case 256 * 8 + 3: return FN<T, 3, 256>(a, pl, k);                                    \
+    case 256 * 8 + 4: return FN<T, 4, 256>(a, pl, k);                                    \
+    case 512 * 8 + 1: return FN<T, 1, 512>(a, pl, k);                                    \
+    case 512 * 8 + 2: return FN<T, 2, 512>(a, pl, k);                                    \
+    case 512 * 8 + 3: return FN<T, 3, 512>(a, pl, k);                                    \
+    case 512 * 8 + 4: return FN<T, 4, 512>(a, pl, k);                                    \
+    case 1024 * 8 + 1: return FN<T, 1, 1024>(a, pl, k);                                  \
+    case 1024 * 8 + 2: return FN<T, 2, 1024>(a, pl, k);                                  \
+    case 1024 * 8 + 3: return FN<T, 3, 1024>(a, pl, k);                                  \
+    default: return FN<T, 4, 1024>(a, pl, k);                                            \
   }
 
 template <typename T>
-static int dispatch_du(const void* in, void* out, const uint32_t* blob, const DUArgs& a, size_t lds, const Geo& geo,
-                       hipStream_t s) {
-  ALG_V2_DISPATCH(launch_du, T, (const T*)in, (T*)out, blob, a, lds, geo.grid, s)
+static int dispatch_du(const LowpassArgs& a, const LowpassPlan& pl, const DUArgs& k) {
+  ALG_V2_DISPATCH(launch_du, T)
 }
 
 template <typename T>
-static int dispatch_g(const void* in, void* out, const GArgs& a, size_t lds, const Geo& geo, hipStream_t s) {
-  ALG_V2_DISPATCH(launch_g, T, (const T*)in, (T*)out, a, lds, geo.grid, s)
+static int dispatch_g(const LowpassArgs& a, const LowpassPlan& pl, const GArgs& k) {
+  ALG_V2_DISPATCH(launch_g, T)
 }
 
 }  // namespace v2
 
-// Returns ALG_OK when the launch was made, 1 when this shape is not covered (the caller falls back to lowpass.hip's kernels).
-int down_up_v2(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype, int round_mid,
-               const void* tables, hipStream_t s) {
+// What the persistent-grid kernels cover: 16-byte-granular planes at 16-byte-aligned bases, more than two of them per CU, whose
+// prefetch registers (at most four 16-byte loads per thread) hold a plane and whose LDS fits a CU.
+bool lowpass_persistent_covers(const LowpassArgs& a, int cus, LowpassPlan* pl) {
   using namespace v2;
-  const size_t esz = dtype == ALG_F32 ? 4 : 2;
-  const size_t bytes = (size_t)H * W * esz;
-  if ((bytes & 15) || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return 1;
-  DUArgs a;
-  a.H = H, a.W = W, a.h1 = h1, a.w1 = w1, a.round_mid = round_mid, a.planes = planes;
-  a.tabs = layout(H, W, h1, w1);
-  const size_t stage = ((size_t)h1 * W + 3) / 4 * 4 + (bytes + 3) / 4;          // T3 + staged output, in floats
-  const size_t a_fl = (std::max((size_t)H * W, stage) + 3) / 4 * 4;
-  a.a_floats = (int)a_fl;
-  // + 16 floats of slack: the batched tap reads run up to 11 floats past a row's last tap
-  const size_t lds = (a_fl + (size_t)H * w1 + (((size_t)h1 * w1 + 3) & ~(size_t)3) + a.tabs.words + 16) * 4;
-  if (lds > 160 * 1024 || a.tabs.dw.taps > 64) return 1;
-  if (((size_t)H * w1) & 3) return 1;                                              // keeps T2 / the blob 16-byte aligned
-  Geo geo;
-  if (!geometry(bytes, H * W, planes, lds, 6, 4, &geo)) return 1;
-  const uint32_t* blob = (const uint32_t*)tables;
-  if (!blob) return 1;
-  return dtype == ALG_F32 ? dispatch_du<float>(in, out, blob, a, lds, geo, s)
-                          : dispatch_du<bf16_t>(in, out, blob, a, lds, geo, s);
+  const size_t bytes = (size_t)a.H * a.W * lowpass_esize(a);
+  if ((bytes & 15) || lowpass_misaligned(a)) return false;
+  if (a.filter == LowpassFilter::GAUSSIAN) {
+    const size_t lds = g_lds(a);
+    return lds <= LOWPASS_LDS_CAP && geometry(bytes, a.planes, lds, 8, 8, cus, pl);
+  }
+  DUArgs k;
+  const size_t lds = du_args(a, &k);
+  if (lds > LOWPASS_LDS_CAP || k.tabs.dw.taps > 64) return false;
+  if (((size_t)a.H * a.w1) & 3) return false;                                      // keeps T2 / the blob 16-byte aligned
+  return geometry(bytes, a.planes, lds, 6, 4, cus, pl);
 }
 
-int gaussian_v2(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma, int dtype, hipStream_t s) {
+// ---- launch: the PERSISTENT route
+int launch_lowpass_persistent(const LowpassArgs& a, const LowpassPlan& pl) {
   using namespace v2;
-  const size_t esz = dtype == ALG_F32 ? 4 : 2;
-  const size_t bytes = (size_t)H * W * esz;
-  if ((bytes & 15) || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return 1;
-  GArgs a;
-  a.H = H, a.W = W, a.ksize = ksize, a.sigma = sigma, a.planes = planes;
-  const size_t n4 = ((size_t)H * W + 3) & ~(size_t)3;
-  const size_t lds = ((2 * n4 + ksize) * 4 + 15) & ~(size_t)15;
-  if (lds > 160 * 1024) return 1;
-  Geo geo;
-  if (!geometry(bytes, H * W, planes, lds, 8, 8, &geo)) return 1;
-  return dtype == ALG_F32 ? dispatch_g<float>(in, out, a, lds, geo, s) : dispatch_g<bf16_t>(in, out, a, lds, geo, s);
+  const bool f32 = a.dtype == ALG_F32;
+  if (a.filter == LowpassFilter::DOWN_UP) {
+    DUArgs k;
+    du_args(a, &k);
+    return f32 ? dispatch_du<float>(a, pl, k) : dispatch_du<bf16_t>(a, pl, k);
+  }
+  GArgs k;
+  k.H = a.H, k.W = a.W, k.ksize = a.ksize, k.sigma = a.sigma, k.planes = a.planes;
+  return f32 ? dispatch_g<float>(a, pl, k) : dispatch_g<bf16_t>(a, pl, k);
 }
 
 }  // namespace alg

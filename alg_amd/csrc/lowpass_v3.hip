@@ -16,15 +16,14 @@
 // packed fma is the same fused operation per half.  The only extra operations are fma(0, finite, acc) at the ends of a
 // pair's chain, which leave acc unchanged (they can turn an all-zero-products result -0 into +0; nothing else).
 // Shapes not covered (odd W, plane sizes that are not a multiple of 4 elements, tap counts without an instantiation, halo
-// too large) return 1 and take v2.
+// too large: lowpass_blocked_covers) take v2.
 #include <algorithm>
 #include <atomic>
 
 #include <math.h>
 #include <stdlib.h>
 
-#include "common.h"
-#include "lowpass_tabs.h"
+#include "lowpass_host.h"
 
 namespace alg {
 namespace v3 {
@@ -478,195 +477,165 @@ __global__ __launch_bounds__(NT) void down_up_v3_kernel(const T* __restrict__ in
   }
 }
 
-static int num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t p;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&p, dev) == hipSuccess) cus = p.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-// planes a launch must have for these kernels to be used (fewer: the plane-per-workgroup kernels of lowpass.hip put up to
-// 1024 threads on a plane and have the lower latency; measured cross-over well below one plane per CU)
-static int64_t min_planes() { return opt(OPT_LOWPASS_PATH) == 3 ? 1 : num_cus() / 2; }   // ALG_LOWPASS_PATH=3: at any plane count
-static bool v3_off() { return opt(OPT_LOWPASS_PATH) == 2; }                               // ALG_LOWPASS_PATH=2: lowpass_v2.hip
-
-static int wgs_cap() {   // EXPERIMENTS tuning knob: resident workgroups per CU the persistent grid is sized for
-  return 1 << 20;
-}
-
 // Workgroups of `kernel` a CU really holds (registers AND LDS): the persistent grid must not be larger than that, or the
 // surplus workgroups wait for a slot and run their planes as a tail (measured: C2 x 8 videos 26.8 us with five workgroups
-// per CU requested, four resident; 22.6 us with four).
-template <typename K>
-static int resident_wgs(K kernel, int nt, size_t lds) {
-  int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kernel, nt, lds) != hipSuccess || n < 1) {
-    (void)hipGetLastError();
-    n = 1;
-  }
-  return n;
-}
-
-static int threads_override() {
-  return 0;
-}
-
-// per kernel instantiation: raise the LDS limit when needed and ask the runtime how many workgroups a CU holds; both are
-// remembered for the largest LDS size seen (first calls may race: they compute the same values)
-struct Prep {
+// per CU requested, four resident; 22.6 us with four).  Asked of the runtime per kernel instantiation and remembered for the
+// last LDS size and device seen (first calls may race: they compute the same values).
+struct Resident {
   std::atomic<size_t> lds{0};
   std::atomic<int> wgs{0};
-  std::atomic<int> dev{-2};   // the device the two values above were set / queried on (both are per-device)
+  std::atomic<int> dev{-2};   // the device the value above was queried on (it is per-device)
 };
 
 template <typename K>
-static int prepare(Prep& p, K kernel, int nt, size_t lds, int* wgs) {
-  const int dev = current_device_slot();
-  if (p.lds.load() != lds || dev < 0 || p.dev.load() != dev) {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) {
-        set_error("hipFuncSetAttribute(max dynamic LDS=%zu): %s", lds, hipGetErrorString(e));
-        return ALG_ELAUNCH;
-      }
+static int resident_wgs(Resident& r, K kernel, int nt, size_t lds, int dev) {
+  if (r.lds.load() != lds || dev < 0 || r.dev.load() != dev) {
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)kernel, nt, lds) != hipSuccess || n < 1) {
+      (void)hipGetLastError();
+      n = 1;
     }
-    p.wgs.store(resident_wgs(kernel, nt, lds));
-    p.dev.store(dev);
-    p.lds.store(lds);
+    r.wgs.store(n);
+    r.dev.store(dev);
+    r.lds.store(lds);
   }
-  *wgs = std::min(std::max(p.wgs.load(), 1), wgs_cap());
-  return ALG_OK;
+  return std::max(r.wgs.load(), 1);
 }
 
+// opt in, then the occupancy query (it is asked with the call's LDS), then the launch
 template <typename T, int K, int NT>
-static int launch_g(const void* in, void* out, const GArgs& a, size_t lds, hipStream_t s) {
-  static Prep prep;
-  int wgs = 1;
-  const int rc = prepare(prep, gaussian_v3_kernel<T, K, NT>, NT, lds, &wgs);
+static int launch_g(const LowpassArgs& a, const LowpassPlan& pl, const GArgs& k) {
+  static PerDeviceOnce once;
+  static Resident resident;
+  const char* who = lowpass_who(a, pl.route);
+  const int rc = lowpass_opt_in(once, (const void*)gaussian_v3_kernel<T, K, NT>, who, a);
   if (rc != ALG_OK) return rc;
-  const unsigned grid = (unsigned)std::min<int64_t>(a.planes, (int64_t)num_cus() * wgs);
-  hipLaunchKernelGGL((gaussian_v3_kernel<T, K, NT>), dim3(grid), dim3(NT), lds, s, (const T*)in, (T*)out, a);
-  return check_launch("alg_gaussian_blur");
+  const unsigned grid = lowpass_persistent_grid(a, pl, resident_wgs(resident, gaussian_v3_kernel<T, K, NT>, NT, pl.lds, a.device));
+  hipLaunchKernelGGL((gaussian_v3_kernel<T, K, NT>), dim3(grid), dim3(NT), pl.lds, a.stream, (const T*)a.in, (T*)a.out, k);
+  return check_launch(who);
 }
 
 template <typename T, int K>
-static int launch_g_nt(const void* in, void* out, const GArgs& a, size_t lds, int nt, hipStream_t s) {
-  return nt == 512 ? launch_g<T, K, 512>(in, out, a, lds, s) : launch_g<T, K, 256>(in, out, a, lds, s);
+static int launch_g_nt(const LowpassArgs& a, const LowpassPlan& pl, const GArgs& k) {
+  return pl.threads == 512 ? launch_g<T, K, 512>(a, pl, k) : launch_g<T, K, 256>(a, pl, k);
 }
 
 template <typename T>
-static int dispatch_g(const void* in, void* out, const GArgs& a, int ksize, size_t lds, int nt, hipStream_t s) {
-  switch (ksize) {
-    case 3: return launch_g_nt<T, 3>(in, out, a, lds, nt, s);
-    case 5: return launch_g_nt<T, 5>(in, out, a, lds, nt, s);
-    case 7: return launch_g_nt<T, 7>(in, out, a, lds, nt, s);
-    case 9: return launch_g_nt<T, 9>(in, out, a, lds, nt, s);
-    case 11: return launch_g_nt<T, 11>(in, out, a, lds, nt, s);
-    case 13: return launch_g_nt<T, 13>(in, out, a, lds, nt, s);
-    case 15: return launch_g_nt<T, 15>(in, out, a, lds, nt, s);
-    case 17: return launch_g_nt<T, 17>(in, out, a, lds, nt, s);
-    case 19: return launch_g_nt<T, 19>(in, out, a, lds, nt, s);
-    default: return 1;
+static int dispatch_g(const LowpassArgs& a, const LowpassPlan& pl, const GArgs& k) {
+  switch (pl.variant) {
+    case 3: return launch_g_nt<T, 3>(a, pl, k);
+    case 5: return launch_g_nt<T, 5>(a, pl, k);
+    case 7: return launch_g_nt<T, 7>(a, pl, k);
+    case 9: return launch_g_nt<T, 9>(a, pl, k);
+    case 11: return launch_g_nt<T, 11>(a, pl, k);
+    case 13: return launch_g_nt<T, 13>(a, pl, k);
+    case 15: return launch_g_nt<T, 15>(a, pl, k);
+    case 17: return launch_g_nt<T, 17>(a, pl, k);
+    default: return launch_g_nt<T, 19>(a, pl, k);
   }
 }
 
-
 template <typename T, int TDW, int NT>
-static int launch_d(const void* in, void* out, const uint32_t* blob, const DArgs& a, size_t lds, hipStream_t s) {
-  static Prep prep;
-  int wgs = 1;
-  const int rc = prepare(prep, down_up_v3_kernel<T, TDW, NT>, NT, lds, &wgs);
+static int launch_d(const LowpassArgs& a, const LowpassPlan& pl, const DArgs& k) {
+  static PerDeviceOnce once;
+  static Resident resident;
+  const char* who = lowpass_who(a, pl.route);
+  const int rc = lowpass_opt_in(once, (const void*)down_up_v3_kernel<T, TDW, NT>, who, a);
   if (rc != ALG_OK) return rc;
-  const unsigned grid = (unsigned)std::min<int64_t>(a.planes, (int64_t)num_cus() * wgs);
-  hipLaunchKernelGGL((down_up_v3_kernel<T, TDW, NT>), dim3(grid), dim3(NT), lds, s, (const T*)in, (T*)out, blob, a);
-  return check_launch("alg_down_up");
+  const unsigned grid = lowpass_persistent_grid(a, pl, resident_wgs(resident, down_up_v3_kernel<T, TDW, NT>, NT, pl.lds, a.device));
+  hipLaunchKernelGGL((down_up_v3_kernel<T, TDW, NT>), dim3(grid), dim3(NT), pl.lds, a.stream, (const T*)a.in, (T*)a.out,
+                     (const uint32_t*)a.tables, k);
+  return check_launch(who);
 }
 
 template <typename T, int TDW>
-static int launch_d_nt(const void* in, void* out, const uint32_t* blob, const DArgs& a, size_t lds, int nt,
-                       hipStream_t s) {
-  switch (nt) {
-    case 256: return launch_d<T, TDW, 256>(in, out, blob, a, lds, s);
-    case 512: return launch_d<T, TDW, 512>(in, out, blob, a, lds, s);
-    default: return launch_d<T, TDW, 1024>(in, out, blob, a, lds, s);
+static int launch_d_nt(const LowpassArgs& a, const LowpassPlan& pl, const DArgs& k) {
+  switch (pl.threads) {
+    case 256: return launch_d<T, TDW, 256>(a, pl, k);
+    case 512: return launch_d<T, TDW, 512>(a, pl, k);
+    default: return launch_d<T, TDW, 1024>(a, pl, k);
   }
 }
 
 template <typename T>
-static int dispatch_d(const void* in, void* out, const uint32_t* blob, const DArgs& a, size_t lds, int nt,
-                      hipStream_t s) {
-  const int taps = a.tabs.dw.taps;
-  if (taps <= 5) return launch_d_nt<T, 5>(in, out, blob, a, lds, nt, s);
-  if (taps <= 7) return launch_d_nt<T, 7>(in, out, blob, a, lds, nt, s);
-  if (taps <= 9) return launch_d_nt<T, 9>(in, out, blob, a, lds, nt, s);
-  return launch_d_nt<T, 11>(in, out, blob, a, lds, nt, s);
+static int dispatch_d(const LowpassArgs& a, const LowpassPlan& pl, const DArgs& k) {
+  switch (pl.variant) {
+    case 5: return launch_d_nt<T, 5>(a, pl, k);
+    case 7: return launch_d_nt<T, 7>(a, pl, k);
+    case 9: return launch_d_nt<T, 9>(a, pl, k);
+    default: return launch_d_nt<T, 11>(a, pl, k);
+  }
 }
 
 }  // namespace v3
 
-// Returns ALG_OK when the launch was made, 1 when this shape is not covered (the caller goes on to lowpass_v2.hip).
-int gaussian_v3(const void* in, void* out, int64_t planes, int H, int W, int ksize, float sigma, int dtype, hipStream_t s) {
+// What the register-blocked kernels cover.  Both filters: even W, planes of a multiple of four elements at 16-byte-aligned
+// bases, whose chunks fit the prefetch registers (MAXPRE per thread), whose LDS fits a CU -- and a launch of at least half as
+// many planes as the device has CUs (fewer: the plane-per-workgroup kernels of lowpass.hip put up to 1024 threads on a plane
+// and have the lower latency; measured cross-over well below one plane per CU).  ALG_LOWPASS_PATH=3: at any plane count;
+// 2: never.
+bool lowpass_blocked_covers(const LowpassArgs& a, int cus, int option, LowpassPlan* pl) {
   using namespace v3;
-  if (v3_off()) return 1;
-  const int pad = ksize / 2, p4 = (pad + 3) & ~3;
-  if ((W & 1) || ((H * W) & 3) || ksize < 3 || ksize > 19 || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return 1;
-  if (pad + 1 >= H || pad + 1 >= W) return 1;                 // the mirrored rows / columns must be distinct from the edge
-  if (planes < min_planes()) return 1;
-  const int ws = (W + 3) & ~3;
-  const size_t lds = ((size_t)H * (ws + 2 * p4) + (size_t)(H + 2 * pad) * ws + ksize + 3) / 4 * 16;
-  if (lds > 160 * 1024) return 1;
-  // thread count (measured, Wan 480p planes): 512 when the launch has more than two planes per CU (16 instead of 8 waves per
-  // CU with two workgroups resident: 37 -> 33 us for 8 videos), 256 for a single video (9.8 vs 10.9 us)
-  int nt = threads_override();
-  if (nt == 1024) nt = 512;
-  if (!nt) nt = planes > 2 * (int64_t)num_cus() ? 512 : 256;
-  if ((int64_t)nt * MAXPRE * 4 < (int64_t)H * W || (int64_t)nt * MAXHALO < (int64_t)H * 2 * pad) {
-    nt = 512;
-    if ((int64_t)nt * MAXPRE * 4 < (int64_t)H * W || (int64_t)nt * MAXHALO < (int64_t)H * 2 * pad) return 1;
-  }
-  GArgs a;
-  a.H = H, a.W = W, a.sigma = sigma, a.planes = planes;
-  return dtype == ALG_F32 ? dispatch_g<float>(in, out, a, ksize, lds, nt, s)
-                          : dispatch_g<bf16_t>(in, out, a, ksize, lds, nt, s);
-}
-
-
-// down_up: returns ALG_OK when the launch was made, 1 when this shape is not covered (the caller goes on to lowpass_v2.hip)
-int down_up_v3(const void* in, void* out, int64_t planes, int H, int W, int h1, int w1, int dtype, int round_mid,
-               const void* tables, hipStream_t s) {
-  using namespace v3;
-  if (v3_off()) return 1;
-  const int n = H * W;
-  if ((W & 1) || (n & 3) || ((uintptr_t)in & 15) || ((uintptr_t)out & 15)) return 1;
-  if (planes < min_planes()) return 1;
-  DArgs a;
-  a.H = H, a.W = W, a.h1 = h1, a.w1 = w1, a.round_mid = round_mid, a.planes = planes;
-  a.tabs = v2::layout(H, W, h1, w1);
-  if (a.tabs.uw.taps != 3 || a.tabs.uh.taps != 3 || a.tabs.dw.taps > 11 || a.tabs.dh.taps > 64) return 1;
-  const int WS = (W + 3) & ~3, VS = (w1 + 3) & ~3, TP = (a.tabs.dh.taps + 1) & ~1;
-  const size_t floats = (size_t)H * WS + 16 + (size_t)H * VS + (size_t)h1 * VS + 16 + ((h1 + 3) & ~3) +
-                        (((size_t)h1 * TP + 3) & ~(size_t)3) + (size_t)H * 4;
-  const size_t lds = floats * 4;
-  if (lds > 160 * 1024) return 1;
-  // thread count (measured): the smallest workgroup whose prefetch registers hold a plane -- several small workgroups per
-  // CU overlap each other's barrier-separated passes -- unless LDS admits only one workgroup per CU: then the largest
-  int nt = threads_override();
-  const int by_lds = (int)((160 * 1024) / lds);
-  if (!nt) {
+  const int H = a.H, W = a.W, n = H * W;
+  if (option == 2) return false;
+  if ((W & 1) || (n & 3) || lowpass_misaligned(a)) return false;
+  if (a.planes < (option == 3 ? 1 : cus / 2)) return false;
+  int nt = 0, variant = 0;
+  size_t lds = 0;
+  if (a.filter == LowpassFilter::GAUSSIAN) {
+    const int ksize = a.ksize, pad = ksize / 2, p4 = (pad + 3) & ~3;
+    if (ksize < 3 || ksize > 19) return false;                   // the instantiations: K = 3, 5, .. 19
+    if (pad + 1 >= H || pad + 1 >= W) return false;              // the mirrored rows / columns must be distinct from the edge
+    const int ws = (W + 3) & ~3;
+    lds = ((size_t)H * (ws + 2 * p4) + (size_t)(H + 2 * pad) * ws + ksize + 3) / 4 * 16;
+    // thread count (measured, Wan 480p planes): 512 when the launch has more than two planes per CU (16 instead of 8 waves
+    // per CU with two workgroups resident: 37 -> 33 us for 8 videos), 256 for a single video (9.8 vs 10.9 us)
+    nt = a.planes > 2 * (int64_t)cus ? 512 : 256;
+    if ((int64_t)nt * MAXPRE * 4 < n || (int64_t)nt * MAXHALO < (int64_t)H * 2 * pad) {
+      nt = 512;
+      if ((int64_t)nt * MAXPRE * 4 < n || (int64_t)nt * MAXHALO < (int64_t)H * 2 * pad) return false;
+    }
+    variant = ksize;
+  } else {
+    const int h1 = a.h1, w1 = a.w1;
+    const v2::Tabs tabs = v2::layout(H, W, h1, w1);
+    if (tabs.uw.taps != 3 || tabs.uh.taps != 3 || tabs.dw.taps > 11 || tabs.dh.taps > 64) return false;
+    const int WS = (W + 3) & ~3, VS = (w1 + 3) & ~3, TP = (tabs.dh.taps + 1) & ~1;
+    const size_t floats = (size_t)H * WS + 16 + (size_t)H * VS + (size_t)h1 * VS + 16 + ((h1 + 3) & ~3) +
+                          (((size_t)h1 * TP + 3) & ~(size_t)3) + (size_t)H * 4;
+    lds = floats * 4;
+    // thread count (measured): the smallest workgroup whose prefetch registers hold a plane -- several small workgroups per
+    // CU overlap each other's barrier-separated passes -- unless LDS admits only one workgroup per CU: then the largest
+    const int by_lds = (int)(LOWPASS_LDS_CAP / lds);
     for (int t : {256, 512, 1024}) {
       if ((int64_t)t * MAXPRE * 4 < n || w1 > t || (WS >> 2) > t) continue;
       if (!nt || by_lds == 1) nt = t;
     }
+    if (!nt) return false;
+    variant = tabs.dw.taps <= 5 ? 5 : tabs.dw.taps <= 7 ? 7 : tabs.dw.taps <= 9 ? 9 : 11;   // pass 1's taps in registers
   }
-  if (!nt || (int64_t)nt * MAXPRE * 4 < n || w1 > nt || (WS >> 2) > nt) return 1;
-  const uint32_t* blob = (const uint32_t*)tables;
-  if (!blob) return 1;
-  return dtype == ALG_F32 ? dispatch_d<float>(in, out, blob, a, lds, nt, s)
-                          : dispatch_d<bf16_t>(in, out, blob, a, lds, nt, s);
+  if (lds > LOWPASS_LDS_CAP) return false;
+  pl->route = LowpassRoute::BLOCKED;
+  pl->threads = nt;
+  pl->variant = variant;
+  pl->lds = lds;
+  pl->wgs_per_cu = 0;
+  return true;
+}
+
+// ---- launch: the BLOCKED route
+int launch_lowpass_blocked(const LowpassArgs& a, const LowpassPlan& pl) {
+  using namespace v3;
+  const bool f32 = a.dtype == ALG_F32;
+  if (a.filter == LowpassFilter::GAUSSIAN) {
+    GArgs k;
+    k.H = a.H, k.W = a.W, k.sigma = a.sigma, k.planes = a.planes;
+    return f32 ? dispatch_g<float>(a, pl, k) : dispatch_g<bf16_t>(a, pl, k);
+  }
+  DArgs k;
+  k.H = a.H, k.W = a.W, k.h1 = a.h1, k.w1 = a.w1, k.round_mid = a.round_mid, k.planes = a.planes;
+  k.tabs = v2::layout(a.H, a.W, a.h1, a.w1);
+  return f32 ? dispatch_d<float>(a, pl, k) : dispatch_d<bf16_t>(a, pl, k);
 }
 
 }  // namespace alg

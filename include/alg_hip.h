@@ -73,6 +73,24 @@ void alg_reload_env(void);
  * lp:31-37).  Planes resident in LDS: one workgroup per plane for small calls, a persistent grid of
  * register-blocked workgroups from 128 planes up (all bit-identical; planes beyond LDS size run
  * through global-memory passes).
+ *
+ * Both entries check their arguments, then plan, then launch.  The plan is a pure function of the operands, the device's
+ * compute units (CUs; 256 on an MI355X) and ALG_LOWPASS_PATH, and the two workspace queries answer from its first rule:
+ *   - "global-memory passes" (lowpass_big.hip): a plane whose plane-per-workgroup kernel would need more than 160 KiB of
+ *     LDS, a blur of more than 255 taps, every call under ALG_LOWPASS_PATH=4.  The only route that needs `workspace`; more
+ *     than 65,535 planes or rows (H, or h1 of a down_up) is ALG_ELIMIT;
+ *   - ALG_LOWPASS_PATH=1, or a down_up call with tables = NULL: the "plane-per-workgroup kernel" (lowpass.hip);
+ *   - otherwise the "register-blocked kernel" (lowpass_v3.hip) unless ALG_LOWPASS_PATH=2: at least CUs / 2 planes (=3: any
+ *     count) of even W and H * W a multiple of four, `in` and `out` 16-byte aligned; a blur of 3..19 taps with ksize / 2 + 1
+ *     below H and W; a down_up whose way back has 3 taps along both axes and whose way down has at most 11 along W and 64
+ *     along H; a plane that fits the kernel's own LDS layout and 8 prefetch loads per thread;
+ *   - otherwise the "persistent-grid kernel" (lowpass_v2.hip): more than 2 * CUs planes whose byte size is a multiple of 16
+ *     and at most 64 KiB, `in` and `out` 16-byte aligned, inside its LDS layout (a down_up also: H * w1 a multiple of four,
+ *     at most 64 taps along W);
+ *   - otherwise the plane-per-workgroup kernel.
+ * No kernel is tried and fallen back from.  Every kernel of the family is opted in to 160 KiB of LDS once per device; a failed
+ * opt-in or launch is ALG_ELAUNCH and names the route: "<entry> (<route name>): hipFuncSetAttribute(<bytes> B LDS): <HIP's
+ * text>" or "<entry> (<route name>): launch failed: <HIP's text>", e.g. "alg_down_up (register-blocked kernel): ...".
  * ---------------------------------------------------------------------------------------------- */
 
 /* lp:49-54  F.interpolate(bilinear, antialias) to (h1, w1) then back to (H, W).

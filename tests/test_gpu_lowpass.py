@@ -265,3 +265,22 @@ def test_bandwidth_shaped_kernels_are_bit_identical_to_the_plane_per_workgroup_k
     assert torch.equal(new, old)
     assert torch.equal(call(), new)                      # deterministic, table cache warm
     assert not torch.equal(new, x)
+
+
+def test_every_route_is_bit_identical(device, monkeypatch):
+    """ALG_LOWPASS_PATH 0..4 on 576 planes of 12 x 16 -- more than two planes per CU, 16-byte-granular planes in both dtypes, even
+    W, H * W a multiple of four -- send these calls through the register-blocked, the plane-per-workgroup, the persistent-grid,
+    again the register-blocked kernel and the global-memory passes (tests/test_lowpass_args_cpu.py asserts exactly that plan for
+    exactly these calls): same bits from all of them."""
+    g = torch.Generator().manual_seed(37)
+    for dt in (torch.float32, torch.bfloat16):
+        x = torch.randn(576, 1, 12, 16, generator=g).to(dt).to(device)
+        for call in (lambda: lp_utils.apply_low_pass_filter(x, "gaussian_blur", 1.2, 5, 1.0),
+                     lambda: lp_utils.apply_low_pass_filter(x, "down_up", 0.0, 0, 0.5)):       # -> 6 x 8: 5 and 3 taps
+            got = []
+            for path in range(5):
+                monkeypatch.setenv("ALG_LOWPASS_PATH", str(path))
+                got.append(call())
+            assert got[0].dtype == dt and got[0].shape == x.shape and not torch.equal(got[0], x)
+            for path in range(1, 5):
+                assert torch.equal(got[path], got[0]), (dt, path)
