@@ -38,6 +38,7 @@ EXPORTS = (
     "alg_flash_attn_d128_ranges_order", "alg_flash_attn_d64_ranges_order",
     "alg_flash_attn_d128_ranges_prefix", "alg_attn_prefix_mass",
     "alg_gemm_fp4", "alg_quantize_mxfp4_rows",
+    "alg_attn_rows_position_major", "alg_attn_vt_position_major",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -135,6 +136,8 @@ def load_library():
     lib.alg_flash_attn_d128_ranges_prefix.argtypes = ([c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 +
                                                       [c_float, c_void_p, c_int, c_int, c_void_p, c_void_p])
     lib.alg_attn_prefix_mass.argtypes = [c_void_p] * 2 + [c_int] * 5 + [c_void_p]
+    lib.alg_attn_rows_position_major.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p] + [c_int] * 6 + [c_void_p]
+    lib.alg_attn_vt_position_major.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p] + [c_int] * 5 + [c_void_p]
     lib.alg_flash_attn_d128_ex.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_int, c_int, c_void_p]
     lib.alg_flash_attn_d128_dual.argtypes = ([c_void_p] * 3 + [c_int] + [c_int64] * 4 + [c_void_p] * 2 + [c_int] + [c_int64] * 4 +
                                              [c_void_p] + [c_int] * 3 + [c_int64] * 4 + [c_float, c_void_p])
@@ -649,6 +652,58 @@ def _ranges_heads_d128(what, order, q, k, vt, o, batch, heads, Sq, Skv, q_bs, q_
                                                 kv_ranges.max_ranges, table_heads, lse_p, _stream()),
            "alg_flash_attn_d128_ranges_heads")
     return o
+
+
+def _head_list_check(what, head_list, head_dim, wide_rstride=None):
+    from .attn_window import HeadList
+    if not isinstance(head_list, HeadList):
+        raise AlgHipError("%s takes an attn_window.HeadList, got %s" % (what, type(head_list).__name__))
+    if head_dim not in (64, 128):
+        raise AlgHipError("%s: head_dim must be 64 or 128, got %r" % (what, head_dim))
+    if wide_rstride is not None and wide_rstride < head_list.heads * head_dim:
+        raise AlgHipError("%s: the list names heads of a tensor with %d heads of %d, its row stride is %d"
+                          % (what, head_list.heads, head_dim, wide_rstride))
+
+
+def attn_rows_position_major(src, dst, head_list, head_dim, batch, frames, hw, src_bs, src_rs, dst_bs, dst_rs, inverse=False,
+                             src_off=0, dst_off=0):
+    """The heads of `head_list` (an attn_window.HeadList: validated on the CPU, device-resident) of a bf16 [batch][frames * hw][heads *
+    head_dim] tensor between the frame-major row order s = f * hw + p and the position-major order p * frames + f: inverse False
+    gathers them from the wide `src` into the compact `dst` ([..][n_sel * head_dim], head_list's order), inverse True scatters the
+    compact `src` back into the wide `dst`, whose other bytes stay (include/alg_hip.h: alg_attn_rows_position_major).  Strides and
+    offsets in elements."""
+    what = "attn_rows_position_major"
+    _head_list_check(what, head_list, head_dim, dst_rs if inverse else src_rs)
+    for t in (src, dst):
+        _dev(t, "layout operand")
+        if t.element_size() != 2:
+            raise AlgHipError("%s moves 2-byte elements (bf16), got %s" % (what, t.dtype))
+    hl = head_list.on(src.device)
+    _check(load_library().alg_attn_rows_position_major(c_void_p(src.data_ptr() + 2 * src_off), src_bs, src_rs,
+                                                       c_void_p(dst.data_ptr() + 2 * dst_off), dst_bs, dst_rs, _ptr(hl), head_list.n_sel,
+                                                       head_dim, batch, frames, hw, int(bool(inverse)), _stream()),
+           "alg_attn_rows_position_major")
+    return dst
+
+
+def attn_vt_position_major(src, dst, head_list, head_dim, batch, frames, hw, src_bs, src_rs, dst_bs, dst_rs, src_off=0, dst_off=0):
+    """The rows of head_list's heads of V^T (bf16 [batch][heads * head_dim][S padded to 64], key axis permuted as the attention entries
+    expect) into the compact `dst` [batch][n_sel * head_dim][..] with the keys in position-major order, padding columns zero
+    (include/alg_hip.h: alg_attn_vt_position_major).  Strides and offsets in elements."""
+    what = "attn_vt_position_major"
+    _head_list_check(what, head_list, head_dim)
+    for t in (src, dst):
+        _dev(t, "layout operand")
+        if t.element_size() != 2:
+            raise AlgHipError("%s moves 2-byte elements (bf16), got %s" % (what, t.dtype))
+    if batch > 1 and src_bs < head_list.heads * head_dim * src_rs:
+        raise AlgHipError("%s: the list names heads of a tensor with %d heads of %d, its batch stride is %d"
+                          % (what, head_list.heads, head_dim, src_bs))
+    hl = head_list.on(src.device)
+    _check(load_library().alg_attn_vt_position_major(c_void_p(src.data_ptr() + 2 * src_off), src_bs, src_rs,
+                                                     c_void_p(dst.data_ptr() + 2 * dst_off), dst_bs, dst_rs, _ptr(hl), head_list.n_sel,
+                                                     head_dim, batch, frames, hw, _stream()), "alg_attn_vt_position_major")
+    return dst
 
 
 def attn_lse_recall(lse_part, lse_full, out, panels, Sq, row0=0, rows=None, part_off=0, full_off=0, out_off=0):

@@ -41,6 +41,17 @@ candidate width; a head then takes the narrowest width that reaches the recall, 
     decide_widths           recall [samples][heads][widths] -> the width per head (0: dense)
     head_width_ranges       the window's rows at each head's own width
 
+The position-major BAND for heads that look at the same spatial position in every frame (Wan attn1; `attn_band`).  In the
+frame-major order s = f hw + p such a head's keys are hw tokens apart; in the position-major order p F + f they are one run per
+query block, so a band head runs alg_flash_attn_d128_ranges on position-major copies of its Q, K and V^T
+(alg_attn_rows_position_major, alg_attn_vt_position_major: attn_layout.hip) and its output is scattered back:
+
+    position_major_index    the permutation pi(f hw + p) = p F + f
+    position_band_ranges    the policy: one range per block, every frame of the positions within `band` of the block's own
+    HeadList                validated, device-resident head indices: the only thing the layout wrappers of _lib take
+    decide_layouts          per head "window" | "band" | "dense": the cheaper of the candidates that reach the recall
+    head_layout_ranges      the main launch's per-head table, band heads ABSENT from it (KvRanges(..., absent_ok=True))
+
 Only the policy is an approximation; its visual quality on a trained checkpoint is unmeasured (README), so it is off by default.
 """
 import math
@@ -62,9 +73,13 @@ ORDER_POLICIES = ("lanes", "units", "natural")
 class KvRanges:
     """A table int32 [q_blocks][max_ranges][2] of (begin, end) key indices for Sq queries and Skv keys, validated on the CPU:
     in each block the used entries come first, sorted and disjoint, begin % 64 == 0, begin < end <= Skv, unused trailing entries
-    are (0, 0), and every block has at least one key.  ValueError names the block and the rule."""
+    are (0, 0), and every block has at least one key.  ValueError names the block and the rule.
 
-    def __init__(self, table, Skv, Sq):
+    absent_ok=True (opt-in: a head that another launch computes, see head_layout_ranges) also takes the table whose EVERY entry is
+    (0, 0): `absent` is then True and the coverage 0; the kernels write zeros and do no other work for such a head.  A table
+    with some blocks empty and others not stays an error."""
+
+    def __init__(self, table, Skv, Sq, absent_ok=False):
         t = torch.as_tensor(table)
         if t.dtype != torch.int32 or t.dim() != 3 or t.shape[2] != 2 or t.device.type != "cpu":
             raise ValueError("KvRanges takes a CPU int32 table [q_blocks][max_ranges][2], got %s %s" % (t.dtype, tuple(t.shape)))
@@ -78,7 +93,8 @@ class KvRanges:
             raise ValueError("max_ranges must be 1..%d, got %d" % (MAX_RANGES, t.shape[1]))
         a = t.numpy().astype(np.int64)
         visited = 0
-        for j in range(q_blocks):
+        self.absent = bool(absent_ok) and not a.any()
+        for j in range(0 if self.absent else q_blocks):
             prev_end, unused_seen = None, False
             for i in range(a.shape[1]):
                 b, e = int(a[j, i, 0]), int(a[j, i, 1])
@@ -130,9 +146,9 @@ class KvRanges:
 class KvRangesHeads:
     """A table int32 [heads][q_blocks][max_ranges][2]: head h's slice is a KvRanges table for (Sq, Skv) and is validated as one
     (ValueError names the head in front of KvRanges' message).  What _lib.flash_attn_d128_ranges_heads takes for table_heads =
-    heads, and _lib.flash_attn_d64_ranges_heads for Sq == Skv."""
+    heads, and _lib.flash_attn_d64_ranges_heads for Sq == Skv.  absent_ok: as in KvRanges, per head."""
 
-    def __init__(self, table, Skv, Sq):
+    def __init__(self, table, Skv, Sq, absent_ok=False):
         t = torch.as_tensor(table)
         if t.dtype != torch.int32 or t.dim() != 4 or t.shape[0] < 1 or t.device.type != "cpu":
             raise ValueError("KvRangesHeads takes a CPU int32 table [heads][q_blocks][max_ranges][2], got %s %s"
@@ -140,7 +156,7 @@ class KvRangesHeads:
         per_head = []
         for h in range(t.shape[0]):
             try:
-                per_head.append(KvRanges(t[h], Skv, Sq))
+                per_head.append(KvRanges(t[h], Skv, Sq, absent_ok=absent_ok))
             except ValueError as e:
                 raise ValueError("head %d: %s" % (h, e)) from None
         self.per_head = tuple(per_head)
@@ -532,6 +548,110 @@ def head_width_ranges(base_by_width, chosen):
     return KvRangesHeads(torch.stack([padded[w] for w in chosen]), used[0].Skv, used[0].Sq)
 
 
+LAYOUTS = ("window", "band", "dense")
+
+
+class HeadList:
+    """The heads a layout move or a band launch works on: DISTINCT indices in [0, heads), in any order, validated on the CPU and
+    uploaded once per device as int32 -- the only thing _lib.attn_rows_position_major / attn_vt_position_major take, so a list
+    that reaches the kernels from Python names heads that exist.  Device-resident: a captured forward replays it."""
+
+    def __init__(self, indices, heads):
+        idx = [int(i) for i in indices]
+        heads = int(heads)
+        if not idx or heads < 1:
+            raise ValueError("HeadList needs at least one head index and heads >= 1 (got %d indices, heads = %d)" % (len(idx), heads))
+        if len(set(idx)) != len(idx):
+            raise ValueError("HeadList: the head indices must be distinct, got %r" % (idx,))
+        if min(idx) < 0 or max(idx) >= heads:
+            raise ValueError("HeadList: head indices must lie in [0, %d), got %r" % (heads, idx))
+        self.indices, self.heads, self.n_sel = tuple(idx), heads, len(idx)
+        self.table = torch.tensor(idx, dtype=torch.int32)
+        self._device = {}
+
+    on = KvRanges.on
+    device_table = KvRanges.device_table
+
+
+def position_major_index(frames, hw):
+    """The permutation pi of the position-major token order as a CPU int64 tensor [frames * hw]: pi[f * hw + p] = p * frames + f.
+    x_pm[pi] = x_fm moves a frame-major tensor over, x_fm = x_pm[pi] reads it back; the inverse of pi is
+    position_major_index(hw, frames)."""
+    F, hw = int(frames), int(hw)
+    if F < 1 or hw < 1:
+        raise ValueError("position_major_index: frames=%d hw=%d" % (F, hw))
+    s = torch.arange(F * hw, dtype=torch.int64)
+    return (s % hw) * F + s // hw
+
+
+def position_band_ranges(frames, hw, band):
+    """The band policy as a KvRanges for Sq = Skv = frames * hw tokens in POSITION-MAJOR order (row p * frames + f), or None where it
+    is the dense attention.  A query at spatial position p is to see every frame of the positions within `band` of p (the
+    distance is taken in the flattened position index, as the frame window takes it in frames).  A block of 256 rows holds the
+    positions p0 .. p1 and gets the ONE range
+
+        [ (max(0, p0 - band) * frames) rounded down to 64,  min(hw, p1 + band + 1) * frames )
+
+    a superset for each of its queries.  In the frame-major order the same keys are hw tokens apart, one run per frame."""
+    F, hw, band = int(frames), int(hw), int(band)
+    if F < 1 or hw < 1 or band < 0:
+        raise ValueError("position_band_ranges: frames=%d hw=%d band=%d" % (F, hw, band))
+    S = F * hw
+    per_block = []
+    for r0 in range(0, S, Q_BLOCK):
+        p0, p1 = r0 // F, (min(r0 + Q_BLOCK, S) - 1) // F
+        per_block.append([((max(0, p0 - band) * F) & ~(KV_ALIGN - 1), min(hw, p1 + band + 1) * F)])
+    return _table(per_block, S, S)
+
+
+def decide_layouts(recall_window, recall_band, cost_window, cost_band, threshold):
+    """Per head one of "window" | "band" | "dense" from the two candidates' recalls [sample][head] (Python floats) and their costs
+    (the mean unit_costs of the candidate's table: one number each, the tables are shared by the heads).  A candidate QUALIFIES
+    when its recall reaches `threshold` on every sample (NaN never does); of the qualifying candidates the cheaper one wins, a
+    tie goes to the window; a head with no qualifying candidate stays dense."""
+    win = decide_heads(recall_window, threshold)
+    ban = decide_heads(recall_band, threshold)
+    if len(win) != len(ban) or len(list(recall_window)) != len(list(recall_band)):
+        raise ValueError("decide_layouts: the two recalls differ in shape")
+    cw, cb = float(cost_window), float(cost_band)
+    if math.isnan(cw) or math.isnan(cb) or cw < 0 or cb < 0:
+        raise ValueError("decide_layouts: costs must be numbers >= 0, got %r and %r" % (cost_window, cost_band))
+    out = []
+    for w, b in zip(win, ban):
+        if w and b:
+            out.append("band" if cb < cw else "window")
+        else:
+            out.append("window" if w else "band" if b else "dense")
+    return out
+
+
+def mean_unit_cost(kv_ranges):
+    """The mean of unit_costs over the blocks of a shared table: what decide_layouts compares."""
+    row = unit_costs(kv_ranges, 1, 1)[0]
+    return sum(row) / float(len(row))
+
+
+def head_layout_ranges(base, layouts):
+    """The MAIN launch's table of a layer whose heads chose `layouts` ("window" | "band" | "dense" each), and the band heads:
+    (table, band_heads).  The band heads run in a launch of their own on position-major operands and are ABSENT from the main
+    table (all (0, 0): the kernels write zeros for them, the scatter behind overwrites those); the others are what
+    head_window_ranges makes them.  With no band head the table is head_window_ranges' (a shared KvRanges, a KvRangesHeads, or
+    None for all dense) and band_heads is (); when every head chose the band the table is None and there is no main launch."""
+    if not isinstance(base, KvRanges):
+        raise ValueError("head_layout_ranges takes a KvRanges, got %s" % type(base).__name__)
+    layouts = list(layouts)
+    if not layouts or any(l not in LAYOUTS for l in layouts):
+        raise ValueError("head_layout_ranges: layouts must be a non-empty list of %s, got %r" % (" | ".join(LAYOUTS), layouts))
+    band_heads = tuple(h for h, l in enumerate(layouts) if l == "band")
+    if not band_heads:
+        return head_window_ranges(base, [l == "window" for l in layouts]), ()
+    if len(band_heads) == len(layouts):
+        return None, band_heads
+    rows = {"window": base.table, "band": torch.zeros_like(base.table), "dense": torch.zeros_like(base.table)}
+    rows["dense"][:, 0, 1] = base.Skv
+    return KvRangesHeads(torch.stack([rows[l] for l in layouts]), base.Skv, base.Sq, absent_ok=True), band_heads
+
+
 def full_ranges(Sq, Skv):
     """The one-range table [0, Skv) for every block: the dense attention through the ranged entry."""
     q_blocks = (Sq + Q_BLOCK - 1) // Q_BLOCK
@@ -655,6 +775,12 @@ class HeadWindowHost:
                              reaches the recall, else it stays dense, and the calibration is ONE launch per layer (below).  The
                              stats records gain "recall_by_width": [[[per width] per head] per sample] and "width": [int per head]
                              (0: dense); "recall" is the recall at the largest width, "windowed" is width > 0
+        attn_band            (WanTransformer3DModel only; the other models do not have the attribute) 0: off -- every buffer, key,
+                             table, record and launch is what it is without it.  An int > 0 (positions on each side; needs
+                             attn_window > 0 and attn_window_recall > 0, ValueError with attn_window_widths): the calibration
+                             forward also measures every head's recall inside the position-major band, decide_layouts gives the
+                             head the window, the band or the dense launch, and the stats records gain "recall_band"
+                             [[per head] per sample] and "layout" [str per head]; "windowed" keeps its meaning, the frame window
         reset_attn_window_heads()   forgets the decisions and the launch orders (the samplers call it at the start of a video)
 
     With attn_window > 0 and attn_window_recall > 0 a forward is dense until the model is calibrated; the calibration forward is the
@@ -693,6 +819,7 @@ class HeadWindowHost:
         self._attn_orders = {}           # (per-head table id, batch, policy) -> (table, LaunchOrder), next to _attn_head_tables
         self.attn_window_widths = None   # None: off; else the candidate widths (see the class docstring)
         self._attn_width_bases = {}      # (table ids per width) -> {width: KvRanges | None}: what _head_table takes with widths
+        self._attn_band_plans = {}       # (base table id, layouts) -> (base, main table | None, HeadList | None): attn_band
 
     @property
     def attn_window_calibrated(self):
@@ -711,6 +838,21 @@ class HeadWindowHost:
                              "reaches the recall" % (self.attn_window_widths,))
         return ws
 
+    def _head_window_band(self):
+        """attn_band validated: 0 (off, also for a model without the attribute) or the positions on each side."""
+        band = getattr(self, "attn_band", 0)
+        if isinstance(band, bool) or not isinstance(band, (int, np.integer)) or band < 0:
+            raise ValueError("attn_band must be a non-negative int (positions on each side; 0 = off), got %r" % (band,))
+        if not band:
+            return 0
+        if not int(getattr(self, "attn_window", 0)) > 0 or not float(self.attn_window_recall) > 0.0:
+            raise ValueError("attn_band=%d needs attn_window > 0 and attn_window_recall > 0: the band is a third candidate of the "
+                             "per-head decision by recall" % band)
+        if self.attn_window_widths is not None:
+            raise ValueError("attn_band=%d does not combine with attn_window_widths=%r: their calibrations differ (two launches "
+                             "against one pass)" % (band, self.attn_window_widths))
+        return int(band)
+
     def _head_width_bases(self, widths, make):
         """{width: make(width)} (make: the model's cached frame_window_ranges table of that width, or None), the SAME dict for the
         same tables: _head_table keys its cache by the dict's identity."""
@@ -724,12 +866,15 @@ class HeadWindowHost:
         self._attn_decided = None
         self._attn_head_tables = {}
         self._attn_orders = {}
+        self._attn_band_plans = {}
         self.attn_window_stats = []
 
-    def _head_window_mode(self, key, layers, samples, heads, rows, o_shape):
+    def _head_window_mode(self, key, layers, samples, heads, rows, o_shape, band=0):
         """How this forward's self-attention launches: None (attn_window_recall is 0: the shared window, nothing else happens),
         "dense" (not calibrated, not asked to), "tables" (calibrated for `key`), or the calibration buffers (this IS the
-        calibration forward).  `key`: what the decisions depend on (video shape, window, sink)."""
+        calibration forward).  `key`: what the decisions depend on (video shape, window, sink).  band > 0 (attn_band, where the
+        band is not the dense attention): the key carries it, and the buffers gain lse_band (the band launch's LSE, position-major
+        rows), lse_band_rows (the same in frame-major row order) and recall_band."""
         thr = float(self.attn_window_recall)
         policy = _balance_policy(self.attn_window_balance)
         widths = self._head_window_widths()
@@ -739,6 +884,8 @@ class HeadWindowHost:
                                  "and windowed heads, which only the recall policy produces" % (self.attn_window_balance,))
             return None
         key = (key, thr) if widths is None else (key, thr, widths)
+        if band:
+            key = key + (("band", int(band)),)
         if self._attn_decided is not None and self._attn_decided[0] != key:
             self.reset_attn_window_heads()       # another video shape, window, sink, threshold or widths: the decisions do not carry over
         if self._attn_decided is not None:
@@ -746,7 +893,7 @@ class HeadWindowHost:
         if not self._attn_calibrate:
             return "dense"
         c = self._attn_cal
-        shape = (layers, samples, heads, rows, tuple(o_shape), widths)
+        shape = (layers, samples, heads, rows, tuple(o_shape), widths) + ((("band", int(band)),) if band else ())
         if widths is not None:     # one pass: the prefixes of one layer and the masses of all; no scratch output, no lse_part
             if c is None or c.shape != shape:
                 c = self._attn_cal = SimpleNamespace(shape=shape, widths=widths, segments=2 * len(widths) + 3)
@@ -764,20 +911,51 @@ class HeadWindowHost:
             c.o = torch.empty(*o_shape, dtype=torch.bfloat16, device=dev)   # the windowed launch's output: not used
             c.recall = torch.zeros(layers, samples, heads, dtype=torch.float64, device=dev)
             c.host = torch.zeros(layers, samples, heads, dtype=torch.float64).pin_memory()
+            c.band = bool(band)
+            if band:
+                c.lse_band = torch.empty(samples, heads, rows, dtype=torch.float32, device=dev)
+                c.lse_band_rows = torch.empty(samples, heads, rows, dtype=torch.float32, device=dev)
+                c.recall_band = torch.zeros(layers, samples, heads, dtype=torch.float64, device=dev)
+                c.host_band = torch.zeros(layers, samples, heads, dtype=torch.float64).pin_memory()
         c.key = key
         return c
 
-    def _head_window_finish(self, c, bases, batch=None):
+    def _head_window_finish(self, c, bases, batch=None, band_table=None):
         """End of the calibration forward: the recalls to the host (one copy, one synchronisation), decide_heads per layer, and
         the per-head tables of `bases` (the window tables this forward used) built and uploaded -- with attn_window_balance, also
         the launch order of every per-head table for launches of `batch` items (default: the forward's samples).  An order for
         another batch size is built by _layer_order on the first eager forward that needs it.
 
         With attn_window_widths: `bases` are the {width: table} dicts of _head_width_bases, the copy brings the segment masses,
-        which are summed per width (width_segments; clipped to 1 like the recall), and decide_widths picks every head's width."""
+        which are summed per width (width_segments; clipped to 1 like the recall), and decide_widths picks every head's width.
+
+        With attn_band (`band_table`: the position_band_ranges table the band launches used): the copy brings recall_band too,
+        decide_layouts picks every head's layout from the two recalls and the two tables' mean unit costs, a layer's decision is
+        its tuple of layouts, the records gain "recall_band" and "layout" ("windowed" stays: the frame window), and the
+        HeadList and the main launch's table of every distinct decision are built and uploaded (_band_plan)."""
         c.host.copy_(c.mass if c.widths is not None else c.recall, non_blocking=True)
+        if band_table is not None:
+            c.host_band.copy_(c.recall_band, non_blocking=True)
         torch.cuda.current_stream().synchronize()
         decided, stats = [], []
+        if band_table is not None:
+            (base,) = bases
+            cost_w, cost_b = mean_unit_cost(base), mean_unit_cost(band_table)
+            clip = lambda rec: [[min(x, 1.0) for x in row] for row in rec]     # as below: NaN stays NaN
+            for li, (rec, rec_b) in enumerate(zip(c.host.tolist(), c.host_band.tolist())):
+                rec, rec_b = clip(rec), clip(rec_b)
+                layouts = decide_layouts(rec, rec_b, cost_w, cost_b, self.attn_window_recall)
+                decided.append(tuple(layouts))
+                stats.append({"layer": li, "recall": rec, "windowed": [l == "window" for l in layouts], "recall_band": rec_b,
+                              "layout": list(layouts)})
+            self._attn_decided = (c.key, decided)
+            self.attn_window_stats = stats
+            batch = c.shape[1] if batch is None else int(batch)
+            for layouts in set(decided):
+                t, _ = self._band_plan(base, layouts)
+                if isinstance(t, KvRangesHeads):
+                    self._layer_order(t, batch)
+            return
         if c.widths is not None:
             counted = width_segments(len(c.widths))
             for li, layer in enumerate(c.host.tolist()):
@@ -803,6 +981,23 @@ class HeadWindowHost:
                 t = self._head_table(base, windowed)
                 if isinstance(t, KvRangesHeads):
                     self._layer_order(t, batch)
+
+    def _band_plan(self, base, layouts):
+        """head_layout_ranges(base, layouts) with the band heads as a HeadList (None: no band head), built and uploaded once."""
+        k = (id(base), tuple(layouts))
+        if k not in self._attn_band_plans:
+            t, band_heads = head_layout_ranges(base, layouts)
+            if t is not None:
+                t.on(self.device)
+            hl = HeadList(band_heads, len(layouts)) if band_heads else None
+            if hl is not None:
+                hl.on(self.device)
+            self._attn_band_plans[k] = (base, t, hl)     # (base is held: its id stays its own)
+        return self._attn_band_plans[k][1:]
+
+    def _layer_band_plan(self, base, layer):
+        """(main table, HeadList | None) layer `layer` launches with once calibrated with attn_band."""
+        return self._band_plan(base, self._attn_decided[1][layer])
 
     def _head_full(self, Sq, Skv):
         if (Sq, Skv) not in self._attn_full:

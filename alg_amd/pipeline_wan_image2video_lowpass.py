@@ -106,7 +106,7 @@ class WanImageToVideoPipeline:
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, image_encoder=None, image_processor=None, device="cuda",
                         fp8=False, fp8_attention=False, step_cache=0.0, attn_window=0, attn_window_recall=0.0,
-                        attn_window_balance=False, attn_window_widths=None, **_):
+                        attn_window_balance=False, attn_window_widths=None, attn_band=0, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
         (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan).
         `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default);
@@ -115,7 +115,10 @@ class WanImageToVideoPipeline:
         `attn_window_balance` (True = "units", "lanes", "units"; needs attn_window_recall > 0, ValueError otherwise) launches the
         layers with dense and windowed heads in a coverage-balanced order (attn_window.balanced_order), bit-identical output; `attn_window_widths`
         (a strictly ascending tuple of positive ints ending in attn_window, or "1,2,4"; needs attn_window_recall > 0, ValueError
-        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration."""
+        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration;
+        `attn_band` (an int, positions on each side; needs attn_window > 0 and attn_window_recall > 0, not with
+        attn_window_widths or fp8_attention, ValueError otherwise) adds the position-major band as a third candidate per head
+        (transformer.attn_band)."""
         import os
 
         from .attn_window import _balance_policy
@@ -132,6 +135,16 @@ class WanImageToVideoPipeline:
             if not float(attn_window_recall) > 0.0:
                 raise ValueError("attn_window_widths=%r needs attn_window_recall > 0: the width of a head is the narrowest that "
                                  "reaches the recall" % (attn_window_widths,))
+        if attn_band:   # (the transformer's own check, before anything is loaded)
+            from types import SimpleNamespace
+
+            from .attn_window import HeadWindowHost
+            HeadWindowHost._head_window_band(SimpleNamespace(attn_band=attn_band, attn_window=attn_window,
+                                                             attn_window_recall=attn_window_recall,
+                                                             attn_window_widths=attn_window_widths))
+            if fp8_attention:
+                raise ValueError("attn_band=%d does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges"
+                                 % attn_band)
 
         from .image_encoder_clip import CLIPImageProcessor, CLIPVisionModel
         from .schedulers import UniPCMultistepScheduler
@@ -142,6 +155,8 @@ class WanImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention)
+        if attn_band:
+            transformer.attn_band = int(attn_band)
         if step_cache:
             transformer.step_cache = float(step_cache)
         if attn_window:

@@ -31,7 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import HeadWindowHost, KvRangesHeads, frame_profile_segments, frame_window_ranges
+from .attn_window import HeadWindowHost, KvRangesHeads, frame_profile_segments, frame_window_ranges, position_band_ranges
 from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
@@ -188,6 +188,12 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall reaches it keep the window
         # (attn_window.HeadWindowHost: attn_window_stats, reset_attn_window_heads).  0.0: the shared window, nothing allocated
         self._head_window_init()
+        # attn_band > 0 (opt-in, with attn_window > 0 and attn_window_recall > 0; Wan only): a third candidate per head, the BAND -- the
+        # same and the `attn_band` neighbouring spatial positions in every frame -- measured on the calibration forward like the
+        # window; a head that chose it runs on position-major copies of its Q, K and V^T (alg_attn_rows_position_major,
+        # alg_attn_vt_position_major), where those keys are one run per query block.  0: nothing allocated, launched or recorded
+        self.attn_band = 0
+        self._band_ws = None      # position-major scratch, allocated on the calibration forward and kept
         if config.qk_norm != "rms_norm_across_heads" or config.attention_head_dim != 128:
             raise NotImplementedError("the Wan DiT path is built for rms_norm_across_heads and head_dim 128")
         if tuple(config.patch_size)[0] != 1:
@@ -395,6 +401,43 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             self._attn_ranges[key] = r
         return self._attn_ranges[key]
 
+    def _band_ranges(self, frames, hw, band):
+        """The position_band_ranges table of this video shape (device-resident, built once), or None where the band is the dense
+        attention."""
+        key = ("band", frames, hw, band)
+        if key not in self._attn_ranges:
+            r = position_band_ranges(frames, hw, band)
+            if r is not None:
+                r.on(self.device)
+            self._attn_ranges[key] = r
+        return self._attn_ranges[key]
+
+    def _band_scratch(self, N, S, D, S_pad):
+        """Position-major Q, K, O [N, S, D] and V^T [N, D, S_pad] for up to all heads; a launch over fewer heads uses the front of
+        each compactly.  Allocated on the calibration forward (never inside a capture) and kept."""
+        b = self._band_ws
+        if b is None or b.shape != (N, S, D, S_pad):
+            if _lib._capturing():
+                raise _lib.AlgHipError("attn_band: the position-major scratch for batch %d has not been allocated yet, which a "
+                                       "capture cannot do -- run one eager forward of this batch size first" % N)
+            e = lambda *s_: torch.empty(*s_, dtype=BF, device=self.device)
+            b = self._band_ws = SimpleNamespace(shape=(N, S, D, S_pad), q=e(N, S, D), k=e(N, S, D), o=e(N, S, D), vt=e(N, D, S_pad))
+        return b
+
+    def _band_attention(self, T, ws, bs, hl, table, N, F_, S, S_pad, scale, lse=None):
+        """The band launch of the heads `hl` (a HeadList): gather Q, K and V^T position-major into the scratch, one ranged launch
+        over the compact buffers into bs.o (with `lse`: the _heads entry, which also writes the LSE)."""
+        D, n, hw = self.config.dim, hl.n_sel, S // F_
+        Dc = n * 128
+        T("attn_layout", _lib.attn_rows_position_major, ws.qk, bs.q, hl, 128, N, F_, hw, S * 2 * D, 2 * D, S * Dc, Dc)
+        T("attn_layout", _lib.attn_rows_position_major, ws.qk, bs.k, hl, 128, N, F_, hw, S * 2 * D, 2 * D, S * Dc, Dc, src_off=D)
+        T("attn_layout", _lib.attn_vt_position_major, ws.vt, bs.vt, hl, 128, N, F_, hw, D * S_pad, S_pad, Dc * S_pad, S_pad)
+        A = (bs.q, bs.k, bs.vt, bs.o, N, n, S, S, S * Dc, Dc, S * Dc, Dc, Dc * S_pad, S_pad, S * Dc, Dc, scale, table)
+        if lse is not None:
+            T("attn_calib", _lib.flash_attn_d128_ranges_heads, *A, lse=lse)
+        else:
+            T("attn_band", _lib.flash_attn_d128_ranges, *A)
+
     def _profile_segments(self, frames, hw, widths):
         """The frame_profile_segments table of this video shape for attn_window_widths (device-resident, built once)."""
         key = ("profile", frames, hw, widths, int(self.attn_sink_frames))
@@ -490,11 +533,17 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         kvr = self._window_ranges(F_, S // F_) if self.attn_window else None    # None: the dense launch
         # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
         hwm = None
+        # attn_band validated (needs the recall policy, excludes the widths); 0: off -- also on a forward the sampler runs with the
+        # window switched off (call_transformer: the dense early steps)
+        band = self._head_window_band() if self.attn_window else 0
+        band_t = self._band_ranges(F_, S // F_, band) if band and kvr is not None else None    # None: off, or the band is dense
         if kvr is not None:
             hwm = self._head_window_mode((F_, S // F_, int(self.attn_window), int(self.attn_sink_frames)), len(self.blocks), N,
-                                         heads, S, (N, S, D))
+                                         heads, S, (N, S, D), band=band if band_t is not None else 0)
         cal = hwm if hwm not in (None, "dense", "tables") else None
         full = self._head_full(S, S) if cal is not None else None
+        if band_t is not None and cal is not None:
+            all_heads = self._band_plan(kvr, ("band",) * heads)[1]
         kvr0 = kvr
         widths = self._head_window_widths() if hwm is not None else None
         if widths is not None:   # attn_window_widths: the tables of every candidate width, one profile table for the calibration
@@ -528,7 +577,10 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             else:
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
-                if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
+                band_heads = None
+                if hwm is not None and band_t is not None:   # ... with attn_band: the main launch's table and the band heads
+                    kvr, band_heads = (None, None) if hwm == "dense" or cal is not None else self._layer_band_plan(kvr0, li)
+                elif hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
                     kvr = None if hwm == "dense" or cal is not None else self._layer_table(kvr0, li)
                 order = self._layer_order(kvr, N) if isinstance(kvr, KvRangesHeads) else None      # attn_window_balance
                 if cal is not None and widths is not None:   # ... in one pass: all keys in rings, a prefix LSE behind every ring
@@ -543,6 +595,15 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                     T("attn_calib", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, cal.o, *A, kvr0, lse=cal.lse_part, k_off=D)
                     T("attn_calib", _lib.attn_lse_recall, cal.lse_part, cal.lse_full, cal.recall, N * heads, S,
                       out_off=li * N * heads)
+                    if band_t is not None:   # the third candidate: every head on position-major operands, for its LSE only
+                        self._band_attention(T, ws, self._band_scratch(N, S, D, S_pad), all_heads, band_t, N, F_, S, S_pad, scale,
+                                             lse=cal.lse_band)
+                        # (rows p F + f -> f hw + p: a torch transpose of the fp32 LSE, once per layer per video)
+                        cal.lse_band_rows.view(N, heads, F_, S // F_).copy_(cal.lse_band.view(N, heads, S // F_, F_).transpose(-1, -2))
+                        T("attn_calib", _lib.attn_lse_recall, cal.lse_band_rows, cal.lse_full, cal.recall_band, N * heads, S,
+                          out_off=li * N * heads)
+                elif band_heads is not None and band_heads.n_sel == heads:   # every head chose the band: no main launch
+                    pass
                 elif order is not None:
                     T("attn_self", _lib.flash_attn_d128_ranges_order, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
                       S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, order, k_off=D)
@@ -555,6 +616,12 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                 else:
                     T("attn_self", _lib.flash_attn_d128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
                       S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D)
+                if band_heads is not None:   # behind the main launch, which wrote zeros to these heads' slices of ws.att
+                    bs = self._band_scratch(N, S, D, S_pad)
+                    self._band_attention(T, ws, bs, band_heads, band_t, N, F_, S, S_pad, scale)
+                    Dc = band_heads.n_sel * 128
+                    T("attn_layout", _lib.attn_rows_position_major, bs.o, ws.att, band_heads, 128, N, F_, S // F_, S * Dc, Dc, S * D, D,
+                      inverse=True)
             lin("gemm_out", ws.att, L.wo, ws.x, S, D, D, D, D, bias=L.bo, R=ws.x, ldr=D, gate=ws.mod,
                 gate_off=m0 + 2 * D, strideGate=mod_bs, batch=N, strideA=S * D, strideC=S * D, strideR=S * D,
                 seg_split=1 << 30, flags=_lib.GEMM_GATE_F32)
@@ -601,7 +668,7 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             T("step_cache", sc.end, ws.x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
 
         if cal is not None:
-            self._head_window_finish(cal, [kvr0])
+            self._head_window_finish(cal, [kvr0], band_table=band_t)
 
         # ---- output head ----
         _lib.layernorm_mod_f32(ws.x, ws.y, None, None, ws.mod_out, ws.mod_out, 2 * D, N, S, D, cfg.eps, scale_off=D,

@@ -506,6 +506,34 @@ int alg_attn_prefix_mass(const float* lse_prefix, double* out, int panels, int s
 int alg_attn_lse_recall(const float* lse_part, const float* lse_full, double* out, int panels, int Sq, int row0, int rows,
                         void* stream);
 
+/* Layout moves under the position-major band attention (alg_amd/attn_window.py: position_band_ranges; attn_layout.hip).  A video
+ * latent's tokens lie frame by frame, s = f * hw + p; in the position-major order pi(s) = p * frames + f the keys "the same and the
+ * neighbouring positions in every frame" are ONE contiguous run, which alg_flash_attn_d128_ranges takes.  Both entries are pure
+ * moves of bf16 (or any 2-byte) elements, bit-exact, for the heads named by
+ *   head_list : DEVICE int32 [n_sel], 4-byte aligned: DISTINCT head indices of the wide tensor, in any order (the kernels do not
+ *               check its contents: alg_amd/attn_window.py: HeadList validates them before the upload).
+ * head_dim (hd) is 64 or 128; S = frames * hw.  Strides in elements, multiples of 8; src / dst 16-byte aligned.  Null or
+ * misaligned pointers, head_dim, n_sel / batch / frames / hw < 1, inverse outside {0, 1} and strides that cannot hold the
+ * tensors are ALG_EINVAL before any launch.  16-byte accesses, a capped grid with a grid-stride loop, no atomics; enqueue-only
+ * and allocation-free.
+ *
+ * alg_attn_rows_position_major: Q, K (inside a [Q | K] buffer: a base offset and the row stride) and O.
+ *   inverse = 0 (gather into a compact buffer):  dst[b][pi(s)][j*hd + d] = src[b][s][head_list[j]*hd + d]
+ *   inverse = 1 (scatter back):                  dst[b][s][head_list[j]*hd + d] = src[b][pi(s)][j*hd + d]
+ *   Element (b, row, c) of either tensor is at base + b*bstride + row*rstride + c.  inverse = 1 writes the selected heads' slices
+ *   only: every other byte of dst keeps its value.  Row strides >= n_sel * hd.
+ *
+ * alg_attn_vt_position_major: V^T, whose key axis carries perm (index bits 2 and 3 swapped: ALG_GEMM_PERMUTE_COLS).
+ *   dst[b][j*hd + d][perm(pi(s))] = src[b][head_list[j]*hd + d][perm(s)]  for s < S;  the columns S .. S rounded up to 64 of dst
+ *   are written as ZERO.  Row strides >= S rounded up to 64; the columns of src up to S rounded up to 16 are read.  The key axis
+ *   is transposed through LDS, so reads and writes both go out as whole 16-byte chunks along a row. */
+int alg_attn_rows_position_major(const void* src, int64_t src_bstride, int64_t src_rstride, void* dst, int64_t dst_bstride,
+                                 int64_t dst_rstride, const int32_t* head_list, int n_sel, int head_dim, int batch, int frames,
+                                 int hw, int inverse, void* stream);
+int alg_attn_vt_position_major(const void* src, int64_t src_bstride, int64_t src_rstride, void* dst, int64_t dst_bstride,
+                               int64_t dst_rstride, const int32_t* head_list, int n_sel, int head_dim, int batch, int frames,
+                               int hw, void* stream);
+
 /* Opt-in e4m3 form of alg_flash_attn_d128 on v_mfma_scale_f32_32x32x64_f8f6f4 (attention128_fp8.hip): non-causal, ungrouped
  * (kv_group != 1 or causal != 0 is ALG_EINVAL), separate Sq / Skv, ragged last tile, bf16 output; strides in elements = bytes.
  *   q  : OCP e4m3, element (b, s, h, d) at q + b*q_bstride + s*q_rstride + h*128 + d;  q_scale: float32 [batch][Sq][heads]

@@ -6,6 +6,7 @@ run of this).  One job, arms alternated, package power and shader clock sampled 
     python scripts/attn_window_ab.py --family heads64 --out profiles/attn_window_heads_d64_ab.json [--only kernel|steps]
     python scripts/attn_window_ab.py --family order --out profiles/attn_window_order_ab.json [--only kernel|steps]
     python scripts/attn_window_ab.py --family widths --out profiles/attn_window_widths_ab.json [--only kernel|steps]
+    python scripts/attn_window_ab.py --family band --out profiles/attn_band_ab.json [--only kernel|steps]
 
   kernel    alg_flash_attn_d128 against alg_flash_attn_d128_ranges at the three launch shapes (C3 32,760 x 40 heads, C5 75,600 x 40,
             C4 119,056 queries x 118,848 keys x 24 heads): the dense entry (first and last arm: their distance is the job's spread),
@@ -55,6 +56,15 @@ by more than the job's spread, and how far above the plain full-range launch is 
 workloads with attn_window_recall = 0.9 and attn_window_widths off / on / off between two arms with the window off; the calibration
 cost per video is an arm's two steps minus the off arms' mean, over a dense step.  No bound is set.
 
+--family band is the position-major band of Wan attn1 (profiles/attn_band_ab.json; alg_attn_rows_position_major,
+alg_attn_vt_position_major, position_band_ranges).  Kernel arms at the C3 and C5 launch shapes, band 8: the dense entry first and
+last, the all-windowed half-coverage launch, gather + band launch + scatter for ALL heads, the same for every second head with the
+others dense through the main launch (band heads absent from its table; once in the kernels' own order and once in the "units"
+order of attn_window_balance), and each layout kernel alone as bytes moved per second
+(read + written) next to alg_lincomb's 2-term in-place add on a tensor of the same size.  Steps: iterations 0-1 of the C3 workload
+with everything off / the recall policy alone / the band on / off.  No bound is set; everything is reported against the spread
+between the repeated arms.  On Gaussian weights the band's recall sits near its coverage, so every head stays dense.
+
 Synthetic weights: the accuracy numbers bound nothing on a trained checkpoint, and nothing here measures visual quality."""
 import argparse
 import gc
@@ -71,8 +81,8 @@ import torch  # noqa: E402
 
 import bench  # noqa: E402
 from alg_amd import _lib  # noqa: E402
-from alg_amd.attn_window import (balanced_order, frame_profile_segments, frame_window_ranges, full_ranges,  # noqa: E402
-                                 head_window_ranges, unit_costs)
+from alg_amd.attn_window import (HeadList, balanced_order, frame_profile_segments, frame_window_ranges, full_ranges,  # noqa: E402
+                                 head_layout_ranges, head_window_ranges, position_band_ranges, unit_costs)
 
 BF = torch.bfloat16
 DEV = torch.device("cuda:0")
@@ -232,6 +242,136 @@ def step_arms_heads(workload, recall=0.9, window=None):
     kvr = [t for t in wl.model._attn_ranges.values() if t is not None]
     out["coverage"] = kvr[0].coverage if kvr else None
     wl.model.attn_window, wl.model.attn_window_recall = 0, 0.0
+    del wl
+    gc.collect()
+    torch.cuda.empty_cache()
+    return out
+
+
+BAND = 8      # positions on each side in the arms of --family band (the issue's C3 example: about 600 of 32,760 keys)
+
+
+def kernel_arms_band(name, iters):
+    F, hw, valid, rows, heads = SHAPES[name]
+    assert not valid and not rows                            # Wan shapes: no prompt tokens in the sequence
+    S, D = F * hw, heads * 128
+    pad = (S + 63) // 64 * 64
+    g = torch.Generator(device=DEV).manual_seed(0)
+    qk = torch.randn(S, 2 * D, generator=g, device=DEV, dtype=BF)
+    vt = torch.randn(D, pad, generator=g, device=DEV, dtype=BF)
+    o = torch.empty(S, D, dtype=BF, device=DEV)
+    qp, kp, op = (torch.empty(S, D, dtype=BF, device=DEV) for _ in range(3))
+    vtp = torch.empty(D, pad, dtype=BF, device=DEV)
+    scale = 1.0 / 128 ** 0.5
+    args = (qk, qk, vt, o, 1, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * pad, pad, S * D, D, scale)
+    w, half = window_for(F, hw, 0, 0, 0.5)
+    band = position_band_ranges(F, hw, BAND)
+    every, second = HeadList(range(heads), heads), HeadList(range(0, heads, 2), heads)
+    main, _ = head_layout_ranges(half, ["band" if h % 2 == 0 else "dense" for h in range(heads)])
+    order = balanced_order(unit_costs(main, 1, heads), "units", heads=heads)
+    for t in (half, band, every, second, main, order):
+        t.device_table
+
+    def gather(hl):
+        Dc = hl.n_sel * 128
+        _lib.attn_rows_position_major(qk, qp, hl, 128, 1, F, hw, S * 2 * D, 2 * D, S * Dc, Dc)
+        _lib.attn_rows_position_major(qk, kp, hl, 128, 1, F, hw, S * 2 * D, 2 * D, S * Dc, Dc, src_off=D)
+        _lib.attn_vt_position_major(vt, vtp, hl, 128, 1, F, hw, D * pad, pad, Dc * pad, pad)
+
+    def band_launch(hl):
+        Dc = hl.n_sel * 128
+        _lib.flash_attn_d128_ranges(qp, kp, vtp, op, 1, hl.n_sel, S, S, S * Dc, Dc, S * Dc, Dc, Dc * pad, pad, S * Dc, Dc, scale, band)
+
+    def scatter(hl):
+        Dc = hl.n_sel * 128
+        _lib.attn_rows_position_major(op, o, hl, 128, 1, F, hw, S * Dc, Dc, S * D, D, inverse=True)
+
+    def band_all():
+        gather(every), band_launch(every), scatter(every)
+
+    def band_half():
+        _lib.flash_attn_d128_ranges_heads(*args, main, k_off=D)
+        gather(second), band_launch(second), scatter(second)
+
+    def band_half_ordered():
+        _lib.flash_attn_d128_ranges_order(*args, main, order, k_off=D)
+        gather(second), band_launch(second), scatter(second)
+
+    dense = lambda: _lib.flash_attn_d128(*args, k_off=D)
+    x, y = torch.randn(S, D, generator=g, device=DEV, dtype=BF), torch.randn(S, D, generator=g, device=DEV, dtype=BF)
+    xv, yv = torch.randn(D, pad, generator=g, device=DEV, dtype=BF), torch.randn(D, pad, generator=g, device=DEV, dtype=BF)
+    rows_bytes, vt_bytes = S * D * 2, D * pad * 2
+    arms = [("dense_first", dense, None), ("window_half_coverage", lambda: _lib.flash_attn_d128_ranges(*args, half, k_off=D), None),
+            ("band_all_heads", band_all, None), ("band_every_second_head", band_half, None),
+            ("band_every_second_head_order_units", band_half_ordered, None),
+            ("band_launch_alone_all_heads", lambda: band_launch(every), None),
+            ("rows_gather_alone", lambda: _lib.attn_rows_position_major(qk, qp, every, 128, 1, F, hw, S * 2 * D, 2 * D, S * D, D), 2 * rows_bytes),
+            ("rows_scatter_alone", lambda: scatter(every), 2 * rows_bytes),
+            ("lincomb_2term_inplace_rows_size", lambda: _lib.lincomb([(1.0, x), (1.0, y)], BF, out=x), 3 * rows_bytes),
+            ("vt_move_alone", lambda: _lib.attn_vt_position_major(vt, vtp, every, 128, 1, F, hw, D * pad, pad, D * pad, pad), 2 * vt_bytes),
+            ("lincomb_2term_inplace_vt_size", lambda: _lib.lincomb([(1.0, xv), (1.0, yv)], BF, out=xv), 3 * vt_bytes),
+            ("dense_last", dense, None)]
+    out = {"queries": S, "keys": S, "heads": heads, "frames": F, "tokens_per_frame": hw, "attn_band": BAND, "attn_window": w,
+           "band_coverage": band.coverage, "window_coverage": half.coverage, "arms": {}}
+    gather(every)                                           # the band launch alone reads real operands
+    t0 = time.perf_counter()
+    while time.perf_counter() - t0 < 2.0:      # not recorded: the first recorded arm meets the chip at its power cap, like the others
+        dense()
+        torch.cuda.synchronize()
+    for label, fn, nbytes in arms:
+        r = timed(fn, iters)
+        if nbytes is not None:
+            r["bytes_moved"] = nbytes
+            r["tb_per_s"] = nbytes / (r["median_ms"] * 1e-3) / 1e12
+        out["arms"][label] = r
+    ms = lambda k: out["arms"][k]["median_ms"]
+    d = out["dense_ms_mean"] = (ms("dense_first") + ms("dense_last")) / 2
+    out["dense_spread_ms"] = abs(ms("dense_first") - ms("dense_last"))
+    for r in out["arms"].values():
+        r["ms_over_dense"] = r["median_ms"] / d
+    out["layout_moves_ms_all_heads"] = ms("band_all_heads") - ms("band_launch_alone_all_heads")
+    del qk, vt, o, qp, kp, op, vtp, x, y, xv, yv
+    torch.cuda.empty_cache()
+    return out
+
+
+def step_arms_band(workload="c3", recall=0.9):
+    F, hw, valid, rows, _ = SHAPES[{"c3": "c3_32760x40", "c5": "c5_75600x40"}[workload]]
+    w_half = window_for(F, hw, valid, rows, 0.5)[0]
+    args = bench.parse_args(["--workload", workload, "--gpus", "1", "--steps", "2", "--warmup", "1"])
+    wl = bench.WORKLOADS[workload](args, DEV, 0, 1, None)
+    wl.build()
+    torch.cuda.synchronize()
+    out = {"attn_window": w_half, "attn_window_recall": recall, "attn_band": BAND, "arms": {}}
+    for label, w, r, b in (("off_first", 0, 0.0, 0), ("recall_policy_alone", w_half, recall, 0), ("band_on", w_half, recall, BAND),
+                           ("off_last", 0, 0.0, 0)):
+        wl.model.attn_window, wl.model.attn_window_recall, wl.model.attn_band = w, r, b
+        bench.run_steps(wl, 1)
+        torch.cuda.synchronize()
+        with bench.SmiSampler(0) as smi:
+            t0 = time.perf_counter()
+            bench.run_steps(wl, 2)
+            torch.cuda.synchronize()
+            s = time.perf_counter() - t0
+        sm = smi.summary() or {}
+        arm = out["arms"][label] = {"attn_window": w, "attn_window_recall": r, "attn_band": b, "seconds_two_steps": s,
+                                    "finite": bool(torch.isfinite(wl.last_out.float()).all().item()),
+                                    "power_w": (sm.get("power_w") or {}).get("mean"), "sclk_mhz": (sm.get("sclk_mhz") or {}).get("mean")}
+        if b:
+            st = wl.model.attn_window_stats
+            flat = [x for rec in st for row in rec["recall_band"] for x in row]
+            arm["layers_calibrated"] = len(st)
+            arm["layouts"] = {l: sum(rec["layout"].count(l) for rec in st) for l in ("window", "band", "dense")}
+            arm["recall_band_min_mean_max"] = [min(flat), sum(flat) / len(flat), max(flat)] if flat else None
+    a, b = out["arms"]["off_first"]["seconds_two_steps"], out["arms"]["off_last"]["seconds_two_steps"]
+    out["off_seconds_mean"], out["off_spread_seconds"] = (a + b) / 2, abs(a - b)
+    for label in ("recall_policy_alone", "band_on"):
+        out[label + "_minus_off_seconds"] = out["arms"][label]["seconds_two_steps"] - out["off_seconds_mean"]
+    out["band_calibration_cost_over_dense_step"] = ((out["arms"]["band_on"]["seconds_two_steps"]
+                                                     - out["arms"]["recall_policy_alone"]["seconds_two_steps"]) / (out["off_seconds_mean"] / 2))
+    band = position_band_ranges(F, hw, BAND)
+    out["band_coverage"] = band.coverage
+    wl.model.attn_window, wl.model.attn_window_recall, wl.model.attn_band = 0, 0.0, 0
     del wl
     gc.collect()
     torch.cuda.empty_cache()
@@ -769,10 +909,11 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--only", choices=["kernel", "steps", "accuracy"], action="append")
     ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64", "order", "widths"], default="d128",
+    ap.add_argument("--family", choices=["d128", "d64", "heads", "heads64", "order", "widths", "band"], default="d128",
                     help="d128: Wan / HunyuanVideo; d64: CogVideoX (C2); heads: the per-head window chosen by recall (d = 128); "
                          "heads64: the same for d = 64 (CogVideoX, C2); order: the coverage-balanced launch order (both head dims); "
-                         "widths: the per-head window width from one calibration pass (d = 128)")
+                         "widths: the per-head window width from one calibration pass (d = 128); band: the position-major band "
+                         "of Wan attn1 (C3 and C5 kernel arms, C3 steps)")
     ap.add_argument("--workloads", default="c3,c5,c4", help="--family heads / order: the workloads of the steps arms")
     ap.add_argument("--shapes", default=",".join(list(SHAPES) + ["c2_2x48x17776"]), help="--family order: the kernel arms' launch shapes")
     a = ap.parse_args()
@@ -788,6 +929,19 @@ def main():
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
 
+    if a.family == "band":
+        res["weights"] = ("synthetic Gaussian: the band's recall sits near its coverage, so every head stays dense; hit rates and "
+                          "quality on a trained checkpoint are unmeasured")
+        if "kernel" in parts:
+            res.setdefault("kernel", {})
+            for name in ("c3_32760x40", "c5_75600x40"):
+                res["kernel"][name] = kernel_arms_band(name, a.iters)
+                save()
+        if "steps" in parts:
+            res["steps"] = {"c3": step_arms_band("c3")}
+            save()
+        print(json.dumps(res))
+        return
     if a.family == "order":
         res["weights"] = ("synthetic Gaussian: which heads window on a trained checkpoint, and so the mix a layer has, is unmeasured; the "
                           "kernel arms fix the mix (every second head dense, three of four windowed)")
