@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "attention128_host.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace a128f8 {
@@ -293,31 +294,7 @@ __global__ __launch_bounds__(NW * 64) void flash_attn_d128_fp8_kernel(const P p)
 }
 
 // ---- producers -----------------------------------------------------------------------------------------------------------------
-// e4m3 conversion of eight bf16 values (two per word) times inv, clamped: the arithmetic of alg_quantize_fp8_rows
-__device__ __forceinline__ uint2 quant8(const uint4 v, float inv) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-  float f[8];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = fminf(fmaxf(__uint_as_float(u[k] << 16) * inv, -448.0f), 448.0f);
-    f[2 * k + 1] = fminf(fmaxf(__uint_as_float(u[k] & 0xffff0000u) * inv, -448.0f), 448.0f);
-  }
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-  return make_uint2((unsigned)lo, (unsigned)hi);
-}
-__device__ __forceinline__ float amax8(const uint4 v, float amax) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    amax = fmaxf(amax, fabsf(__uint_as_float(u[k] << 16)));
-    amax = fmaxf(amax, fabsf(__uint_as_float(u[k] & 0xffff0000u)));
-  }
-  return amax;
-}
+// The quantiser (amax8, e4m3_scale, e4m3x8) is row_ops.h's: the arithmetic of alg_quantize_fp8_rows
 
 // K with one scale per (batch, head).  Pass 1: amax bits (non-negative floats order as unsigned integers) into scale[] by atomic
 // max; pass 2 turns them into scales; pass 3 converts.  16 lanes per (token, head) row of 128.
@@ -337,7 +314,7 @@ __global__ void khead_scale_kernel(float* scale, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) {
     const float amax = scale[i];
-    scale[i] = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
+    scale[i] = e4m3_scale(amax);
   }
 }
 __global__ __launch_bounds__(256) void khead_quant_kernel(const bf16_t* __restrict__ x, int64_t x_bs, int64_t x_rs,
@@ -350,7 +327,7 @@ __global__ __launch_bounds__(256) void khead_quant_kernel(const bf16_t* __restri
     const float inv = 1.0f / scale[b * heads + (hc >> 4)];
     for (int s = s0; s < s1; ++s)
       *(uint2*)(q + (int64_t)b * q_bs + (int64_t)s * q_rs + hc * 8) =
-          quant8(*(const uint4*)(x + (int64_t)b * x_bs + (int64_t)s * x_rs + hc * 8), inv);
+          e4m3x8(*(const uint4*)(x + (int64_t)b * x_bs + (int64_t)s * x_rs + hc * 8), inv);
   }
 }
 
@@ -390,12 +367,10 @@ __global__ __launch_bounds__(256) void vt_quant_kernel(const bf16_t* __restrict_
   };
   float amax = 0.0f;
   for (int o8 = lane * 8; o8 < cols; o8 += 512) amax = amax8(fetch(o8), amax);
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
-  const float sc = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float sc = e4m3_scale(xor_max<64>(amax));
   const float inv = 1.0f / sc;
   if (lane == 0) scale[(int64_t)b * rows + row] = sc;
-  for (int o8 = lane * 8; o8 < cols; o8 += 512) *(uint2*)(qr + o8) = quant8(fetch(o8), inv);
+  for (int o8 = lane * 8; o8 < cols; o8 += 512) *(uint2*)(qr + o8) = e4m3x8(fetch(o8), inv);
 }
 
 }  // namespace a128f8

@@ -1,42 +1,17 @@
 // fp8 (OCP e4m3) operands on the ping-pong schedule (see gemm_kernel.h) + the row-wise quantiser that feeds it.
 #include "gemm_kernel.h"
+#include "row_ops.h"
 
 namespace alg {
 int launch_gemm_p6_fp8(const alg_gemm_args* a, int m_tiles, int n_tiles, int64_t nwg, hipStream_t s) {
   return launch_gemm<6, 4, true>(a, m_tiles, n_tiles, nwg, s);
 }
 
-// one wave per row: amax over the row, then e4m3 conversion of x / scale (v_cvt_pk_fp8_f32 saturates nothing, so clamp)
+// one wave per row: amax over the row, then e4m3 conversion of x / scale -- the quantiser itself is row_ops.h's
 __device__ __forceinline__ float row_scale_store(float amax, int lane, float* __restrict__ scale_out) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
-  const float sc = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
+  const float sc = e4m3_scale(xor_max<64>(amax));
   if (lane == 0) *scale_out = sc;
   return 1.0f / sc;
-}
-__device__ __forceinline__ float amax8(const uint4& v, float amax) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    amax = fmaxf(amax, fabsf(__uint_as_float(u[k] << 16)));
-    amax = fmaxf(amax, fabsf(__uint_as_float(u[k] & 0xffff0000u)));
-  }
-  return amax;
-}
-__device__ __forceinline__ uint2 e4m3x8(const uint4& v, float inv) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-  float f[8];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = fminf(fmaxf(__uint_as_float(u[k] << 16) * inv, -448.0f), 448.0f);
-    f[2 * k + 1] = fminf(fmaxf(__uint_as_float(u[k] & 0xffff0000u) * inv, -448.0f), 448.0f);
-  }
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-  return make_uint2((unsigned)lo, (unsigned)hi);
 }
 // the two-pass form, any K % 8 == 0: xr / qr are the row's first element
 __device__ __forceinline__ void quantize_row_loop(const bf16_t* __restrict__ xr, uint8_t* __restrict__ qr,

@@ -3,22 +3,41 @@
 // q / k fused with the 3-axis rotary embedding of the latent tokens, the masked mean that pools the prompt for the token
 // refiner, SiLU of the conditioning vectors.  Everything else of that forward reuses the CogVideoX / Wan kernels.
 #include "common.h"
+#include "rownorm_host.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace hy {
 
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+// One 128-wide head vector, 16 lanes with 8 elements each (`sub` = the lane's place among them):
+// o = rope( bf16( bf16(x * rsqrt(mean_head(x^2) + eps)) * w ) ) in fp32, before its last rounding.  rope = x * cos + rot(x) * sin
+// over interleaved pairs, fp32 tables [.][128] -- only on tokens < rope_tokens.  Written once for the kernel and its e4m3 twin.
+__device__ __forceinline__ void headnorm_rope_vec(const bf16_t* p, const bf16_t* w, const float* cos_tab, const float* sin_tab,
+                                                  int tok, int sub, int rope_tokens, float eps, float (&o)[8]) {
+  float v[8], wv[8];
+  unpack8(*(const uint4*)p, v);
+  unpack8(*(const uint4*)(w + sub * 8), wv);
+  float q = 0.0f;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
+  for (int k = 0; k < 8; ++k) q = fmaf(v[k], v[k], q);
+  q = xor_sum<16>(q);
+  const float rstd = rsqrtf(q * (1.0f / 128.0f) + eps);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) o[k] = rbf(rbf(v[k] * rstd) * wv[k]);
+  if (cos_tab && tok < rope_tokens) {
+    float cv[8], sv[8];
+    load8(cos_tab + (int64_t)tok * 128 + sub * 8, cv);
+    load8(sin_tab + (int64_t)tok * 128 + sub * 8, sv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float a = o[2 * j], b = o[2 * j + 1];
+      o[2 * j] = a * cv[2 * j] + (-b) * sv[2 * j];
+      o[2 * j + 1] = b * cv[2 * j + 1] + a * sv[2 * j + 1];
+    }
   }
 }
 
-// in place on rows of `heads` 128-wide head vectors: x = rope( bf16( bf16(x * rsqrt(mean_head(x^2) + eps)) * w ) ).
-// 16 lanes own one head vector (8 elements each); rope (x * cos + rot(x) * sin, interleaved pairs, fp32 tables [.][128])
-// only on tokens < rope_tokens of each batch.
+// in place on rows of `heads` 128-wide head vectors; rope only on tokens < rope_tokens of each batch.
 __global__ __launch_bounds__(256) void headnorm_rope_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
                                                             const float* __restrict__ cos_tab,
                                                             const float* __restrict__ sin_tab, int64_t x_rs,
@@ -31,38 +50,13 @@ __global__ __launch_bounds__(256) void headnorm_rope_kernel(bf16_t* __restrict__
   const int head = (int)(vec - row * heads);
   const int tok = (int)(row % rows);
   bf16_t* p = x + (row / rows) * x_bs + (int64_t)tok * x_rs + head * 128 + sub * 8;
-  float v[8], wv[8];
-  unpack8(*(const uint4*)p, v);
-  unpack8(*(const uint4*)(w + sub * 8), wv);
-  float q = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) q = fmaf(v[k], v[k], q);
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
-  const float rstd = rsqrtf(q * (1.0f / 128.0f) + eps);
   float o[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) o[k] = rbf(rbf(v[k] * rstd) * wv[k]);
-  if (cos_tab && tok < rope_tokens) {
-    const float* c = cos_tab + (int64_t)tok * 128 + sub * 8;
-    const float* s = sin_tab + (int64_t)tok * 128 + sub * 8;
-    const float4 c0 = *(const float4*)c, c1 = *(const float4*)(c + 4), s0 = *(const float4*)s, s1 = *(const float4*)(s + 4);
-    const float cv[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-    const float sv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = o[2 * j], b = o[2 * j + 1];
-      o[2 * j] = a * cv[2 * j] + (-b) * sv[2 * j];
-      o[2 * j + 1] = b * cv[2 * j + 1] + a * sv[2 * j + 1];
-    }
-  }
-  uint4 r;
-  r.x = pack_bf2(o[0], o[1]); r.y = pack_bf2(o[2], o[3]); r.z = pack_bf2(o[4], o[5]); r.w = pack_bf2(o[6], o[7]);
-  *(uint4*)p = r;
+  headnorm_rope_vec(p, w, cos_tab, sin_tab, tok, sub, rope_tokens, eps, o);
+  *(uint4*)p = pack8(o);
 }
 
 // headnorm_rope_kernel writing OCP e4m3 for alg_flash_attn_d128_fp8 instead of updating x (x is only read): the bf16-rounded head
-// vector is quantised in registers exactly as a quantiser pass over the bf16 tensor would (gemm_p6_fp8.hip).  head_scale == nullptr:
+// vector is quantised in registers exactly as a quantiser pass over the bf16 tensor would (row_ops.h).  head_scale == nullptr:
 // scale[b * scale_bs + tok * heads + head] = amax / 448 of the head vector (the Q operand); otherwise the given scale of
 // head_scale[b * heads + head] is used (the K operand) and `scale` is not written.
 __global__ __launch_bounds__(256) void headnorm_rope_fp8_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
@@ -80,31 +74,8 @@ __global__ __launch_bounds__(256) void headnorm_rope_fp8_kernel(const bf16_t* __
   const int tok = (int)(row % rows);
   const int64_t bidx = row / rows;
   const bf16_t* p = x + bidx * x_bs + (int64_t)tok * x_rs + head * 128 + sub * 8;
-  float v[8], wv[8];
-  unpack8(*(const uint4*)p, v);
-  unpack8(*(const uint4*)(w + sub * 8), wv);
-  float q = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) q = fmaf(v[k], v[k], q);
-#pragma unroll
-  for (int m = 8; m >= 1; m >>= 1) q += __shfl_xor(q, m, 64);
-  const float rstd = rsqrtf(q * (1.0f / 128.0f) + eps);
   float o[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) o[k] = rbf(rbf(v[k] * rstd) * wv[k]);
-  if (cos_tab && tok < rope_tokens) {
-    const float* c = cos_tab + (int64_t)tok * 128 + sub * 8;
-    const float* s = sin_tab + (int64_t)tok * 128 + sub * 8;
-    const float4 c0 = *(const float4*)c, c1 = *(const float4*)(c + 4), s0 = *(const float4*)s, s1 = *(const float4*)(s + 4);
-    const float cv[8] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
-    const float sv[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float a = o[2 * j], b = o[2 * j + 1];
-      o[2 * j] = a * cv[2 * j] + (-b) * sv[2 * j];
-      o[2 * j + 1] = b * cv[2 * j + 1] + a * sv[2 * j + 1];
-    }
-  }
+  headnorm_rope_vec(p, w, cos_tab, sin_tab, tok, sub, rope_tokens, eps, o);
   float amax = 0.0f;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
@@ -115,21 +86,14 @@ __global__ __launch_bounds__(256) void headnorm_rope_fp8_kernel(const bf16_t* __
   if (head_scale) {
     sc = head_scale[bidx * heads + head];
   } else {
+    // (open-coded, not xor_max<16>: through the template hipcc words one scalar branch of this kernel the other way round, and
+    // this kernel's device code is held byte for byte)
 #pragma unroll
     for (int m = 8; m >= 1; m >>= 1) amax = fmaxf(amax, __shfl_xor(amax, m, 64));
-    sc = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
+    sc = e4m3_scale(amax);
     if (sub == 0) scale[bidx * scale_bs + (int64_t)tok * heads + head] = sc;
   }
-  const float inv = 1.0f / sc;
-  float f[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) f[k] = fminf(fmaxf(o[k] * inv, -448.0f), 448.0f);
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-  *(uint2*)(q8 + bidx * q8_bs + (int64_t)tok * q8_rs + head * 128 + sub * 8) = make_uint2((unsigned)lo, (unsigned)hi);
+  *(uint2*)(q8 + bidx * q8_bs + (int64_t)tok * q8_rs + head * 128 + sub * 8) = e4m3x8(o, 1.0f / sc);
 }
 
 // out[b][d] = bf16( sum_{l < valid[b]} x[b][l][d] / valid[b] )   (HunyuanVideoTokenRefiner pooled prompt)
@@ -159,21 +123,12 @@ using namespace alg;
 extern "C" int alg_headnorm_rope(void* x, const void* weight, const float* cos_tab, const float* sin_tab,
                                  int64_t x_rstride, int64_t x_bstride, int batch, int rows, int heads, int rope_tokens,
                                  float eps, void* stream) {
-  if (batch < 0 || rows < 0 || heads <= 0 || x_rstride % 8 || x_bstride % 8 || x_rstride < (int64_t)heads * 128 ||
-      (cos_tab && !sin_tab)) {
-    set_error("alg_headnorm_rope: bad shape batch=%d rows=%d heads=%d stride=%lld", batch, rows, heads,
-              (long long)x_rstride);
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  if (total == 0) return ALG_OK;
-  if (!x || !weight) {
-    set_error("alg_headnorm_rope: null pointer");
-    return ALG_EINVAL;
-  }
-  const int64_t threads = total * heads * 16;
-  hipLaunchKernelGGL(hy::headnorm_rope_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (bf16_t*)x, (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, x_bstride, total, rows, heads,
+  NormRopeArgs a = {};
+  a.per_head = true; a.x = x; a.weight = weight; a.cos_tab = cos_tab; a.sin_tab = sin_tab;
+  a.x_rstride = x_rstride; a.x_bstride = x_bstride; a.batch = batch; a.rows = rows; a.width = heads;
+  if (const int rc = norm_rope_check(a, "alg_headnorm_rope")) return rc == ROW_EMPTY ? ALG_OK : rc;
+  hipLaunchKernelGGL(hy::headnorm_rope_kernel, dim3((unsigned)norm_rope_blocks(a)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x,
+                     (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, x_bstride, norm_rope_total(a), rows, heads,
                      rope_tokens, eps);
   return check_launch("alg_headnorm_rope");
 }
@@ -182,22 +137,14 @@ extern "C" int alg_headnorm_rope_fp8(const void* x, const void* weight, const fl
                                      int64_t x_rstride, int64_t x_bstride, int batch, int rows, int heads, int rope_tokens,
                                      float eps, void* q8, int64_t q8_rstride, int64_t q8_bstride, float* scale,
                                      int64_t scale_bstride, const float* head_scale, void* stream) {
-  if (batch < 0 || rows < 0 || heads <= 0 || x_rstride % 8 || x_bstride % 8 || x_rstride < (int64_t)heads * 128 ||
-      q8_rstride % 8 || q8_bstride % 8 || q8_rstride < (int64_t)heads * 128 || (cos_tab && !sin_tab)) {
-    set_error("alg_headnorm_rope_fp8: bad shape batch=%d rows=%d heads=%d strides=%lld / %lld", batch, rows, heads,
-              (long long)x_rstride, (long long)q8_rstride);
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  if (total == 0) return ALG_OK;
-  if (!x || !weight || !q8 || (!scale && !head_scale) || ((uintptr_t)x & 15) || ((uintptr_t)q8 & 7)) {
-    set_error("alg_headnorm_rope_fp8: null or misaligned pointer (x 16-byte, q8 8-byte; scale or head_scale is needed)");
-    return ALG_EINVAL;
-  }
-  const int64_t threads = total * heads * 16;
-  hipLaunchKernelGGL(hy::headnorm_rope_fp8_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, x_bstride, total, rows, heads,
-                     rope_tokens, eps, (uint8_t*)q8, q8_rstride, q8_bstride, scale, scale_bstride, head_scale);
+  NormRopeArgs a = {};
+  a.per_head = true; a.x = x; a.weight = weight; a.cos_tab = cos_tab; a.sin_tab = sin_tab;
+  a.x_rstride = x_rstride; a.x_bstride = x_bstride; a.batch = batch; a.rows = rows; a.width = heads;
+  a.fp8 = true; a.q8 = q8; a.q8_rstride = q8_rstride; a.q8_bstride = q8_bstride; a.scale = scale; a.head_scale = head_scale;
+  if (const int rc = norm_rope_check(a, "alg_headnorm_rope_fp8")) return rc == ROW_EMPTY ? ALG_OK : rc;
+  hipLaunchKernelGGL(hy::headnorm_rope_fp8_kernel, dim3((unsigned)norm_rope_blocks(a)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, x_bstride, norm_rope_total(a), rows,
+                     heads, rope_tokens, eps, (uint8_t*)q8, q8_rstride, q8_bstride, scale, scale_bstride, head_scale);
   return check_launch("alg_headnorm_rope_fp8");
 }
 

@@ -5,18 +5,10 @@
 // over [rows][heads][128] bf16 in place, with the rounding points of the eager bf16 graph (each product and the sum are
 // bf16 tensors; cos / sin arrive as the bf16 tables transformers builds, widened to fp32).
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace llama {
-
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-  }
-}
 
 // 8 lanes own one head vector: lane j holds elements [8j, 8j + 8) of the first half AND of the second half
 __global__ __launch_bounds__(256) void rope_half_kernel(bf16_t* __restrict__ x, const float* __restrict__ cos_tab,

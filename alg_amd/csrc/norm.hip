@@ -4,34 +4,24 @@
 //
 // Rounding points mirror the reference's bf16 tensors (every torch op returns bf16): LayerNorm output,
 // (1 + scale), the product and the sum are each rounded.
+#include <algorithm>
+
 #include "common.h"
 #include "qk_norm_rope.h"
+#include "row_ops.h"
+#include "rownorm_host.h"
 
 namespace alg {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-// y = LN(x) * (1 + scale[seg]) + shift[seg]; D = ITERS * 512
+// One row of y = LN(x) [* w + b] [* (1 + scale[seg]) + shift[seg]], D = ITERS * 512, held by one wave: the load, the two-pass
+// statistics, the affine step and the modulation with their rounding points, written once for ln_mod_kernel and its e4m3 twin.
+// Leaves the row in v as the bf16 tensor would hold it (every value already rounded).
 template <int ITERS>
-__global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                     const bf16_t* __restrict__ w, const bf16_t* __restrict__ bs,
-                                                     const bf16_t* __restrict__ scale,
-                                                     const bf16_t* __restrict__ shift, int64_t mod_bs,
-                                                     int64_t x_bs, int64_t y_bs, int64_t total_rows, int rows,
-                                                     int seg_split, int64_t seg_stride, float eps) {
+__device__ __forceinline__ void ln_mod_row(const bf16_t* __restrict__ xr, const bf16_t* __restrict__ w,
+                                           const bf16_t* __restrict__ bs, const bf16_t* __restrict__ scale,
+                                           const bf16_t* __restrict__ shift, int64_t mod_bs, int64_t seg_stride, int bidx,
+                                           int seg, int lane, float eps, float (&v)[ITERS][8]) {
   constexpr int D = ITERS * 512;
-  const int lane = threadIdx.x & 63;
-  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= total_rows) return;
-  const int bidx = (int)(row / rows);
-  const int r = (int)(row - (int64_t)bidx * rows);
-  const int seg = r >= seg_split ? 1 : 0;
-  const bf16_t* xr = x + (int64_t)bidx * x_bs + (int64_t)r * D;
-  float v[ITERS][8];
   float s = 0.0f;
 #pragma unroll
   for (int i = 0; i < ITERS; ++i) {
@@ -51,11 +41,10 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ 
   const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
   const bf16_t* sc = scale ? scale + (int64_t)bidx * mod_bs + (int64_t)seg * seg_stride : nullptr;
   const bf16_t* sh = shift ? shift + (int64_t)bidx * mod_bs + (int64_t)seg * seg_stride : nullptr;
-  bf16_t* yr = y + (int64_t)bidx * y_bs + (int64_t)r * D;
 #pragma unroll
   for (int i = 0; i < ITERS; ++i) {
     const int c0 = i * 512 + lane * 8;
-    float wv[8], bv[8], o[8];
+    float wv[8], bv[8];
     if (w) unpack8(*(const uint4*)(w + c0), wv);
     if (bs) unpack8(*(const uint4*)(bs + c0), bv);
 #pragma unroll
@@ -63,17 +52,38 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ 
       float n = (v[i][k] - mean) * rstd;
       if (w) n = n * wv[k];
       if (bs) n = n + bv[k];
-      o[k] = rbf(n);
+      v[i][k] = rbf(n);
     }
     if (sc) {
       float scv[8], shv[8];
       unpack8(*(const uint4*)(sc + c0), scv);
       unpack8(*(const uint4*)(sh + c0), shv);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = rbf(rbf(o[k] * rbf(1.0f + scv[k])) + shv[k]);
+      for (int k = 0; k < 8; ++k) v[i][k] = rbf(rbf(v[i][k] * rbf(1.0f + scv[k])) + shv[k]);
     }
-    *(uint4*)(yr + c0) = pack8(o);
   }
+}
+
+template <int ITERS>
+__global__ __launch_bounds__(256) void ln_mod_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
+                                                     const bf16_t* __restrict__ w, const bf16_t* __restrict__ bs,
+                                                     const bf16_t* __restrict__ scale,
+                                                     const bf16_t* __restrict__ shift, int64_t mod_bs,
+                                                     int64_t x_bs, int64_t y_bs, int64_t total_rows, int rows,
+                                                     int seg_split, int64_t seg_stride, float eps) {
+  constexpr int D = ITERS * 512;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= total_rows) return;
+  const int bidx = (int)(row / rows);
+  const int r = (int)(row - (int64_t)bidx * rows);
+  const int seg = r >= seg_split ? 1 : 0;
+  const bf16_t* xr = x + (int64_t)bidx * x_bs + (int64_t)r * D;
+  float v[ITERS][8];
+  ln_mod_row<ITERS>(xr, w, bs, scale, shift, mod_bs, seg_stride, bidx, seg, lane, eps, v);
+  bf16_t* yr = y + (int64_t)bidx * y_bs + (int64_t)r * D;
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) *(uint4*)(yr + i * 512 + lane * 8) = pack8(v[i]);
 }
 
 // The same arithmetic, rpw consecutive rows per wave (round 4; round 5: rpw chosen by the launcher so that the whole call is ONE
@@ -178,51 +188,17 @@ __global__ __launch_bounds__(256) void ln_mod_rows_kernel(const bf16_t* __restri
 // quantised there exactly as alg_quantize_fp8_rows would quantise that tensor (gemm_p6_fp8.hip: amax / 448 per row, reciprocal, clamp,
 // v_cvt_pk_fp8_f32): the e4m3 bytes + the row scale are the only stores, the bf16 row never reaches HBM.  8 bytes per lane per store.
 
-// max over the wave of a value >= 0, the same in every lane.  A maximum does not depend on the order it is taken in, so unlike the
-// sums of the statistics (whose butterfly order is part of the bit-identity with ln_mod_kernel) it may take the short way: four
-// DPP steps inside each row of 16 lanes, two row broadcasts, one v_readlane -- no trip through the LDS crossbar.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_max(float v) {
-  const int i = __builtin_bit_cast(int, v);
-  return fmaxf(v, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(i, i, CTRL, ROW_MASK, 0xf, false)));
-}
-__device__ __forceinline__ float wave_max(float v) {
-  v = dpp_max<0xB1, 0xf>(v);    // quad_perm [1, 0, 3, 2]
-  v = dpp_max<0x4E, 0xf>(v);    // quad_perm [2, 3, 0, 1]
-  v = dpp_max<0x141, 0xf>(v);   // row_half_mirror
-  v = dpp_max<0x140, 0xf>(v);   // row_mirror: every lane holds its row's maximum
-  v = dpp_max<0x142, 0xa>(v);   // row_bcast:15 into rows 1 and 3
-  v = dpp_max<0x143, 0xc>(v);   // row_bcast:31 into rows 2 and 3: lane 63 holds the wave's
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
+// (wave_max, the DPP maximum, and the quantiser are row_ops.h's)
 template <int ITERS>
 __device__ __forceinline__ void quantize_row_store(const float (&v)[ITERS][8], int lane, uint8_t* __restrict__ qr,
                                                    float* __restrict__ scale_out) {
   float amax = 0.0f;
 #pragma unroll
-  for (int i = 0; i < ITERS; ++i)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) amax = fmaxf(amax, fabsf(v[i][k]));
-  amax = wave_max(amax);
-  const float qs = amax > 0.0f ? amax * (1.0f / 448.0f) : 1.0f;
-  const float inv = 1.0f / qs;
-  if (lane == 0) *scale_out = qs;
-#pragma unroll
-  for (int i = 0; i < ITERS; ++i) {
-    float f[8];
-#pragma unroll
-    for (int k = 0; k < 8; ++k) f[k] = fminf(fmaxf(v[i][k] * inv, -448.0f), 448.0f);
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
-    *(uint2*)(qr + i * 512 + lane * 8) = make_uint2((unsigned)lo, (unsigned)hi);
-  }
+  for (int i = 0; i < ITERS; ++i) amax = amax8(v[i], amax);
+  e4m3_row_store<ITERS>(v, wave_max(amax), lane, qr, scale_out);
 }
 
-// ln_mod_kernel's arithmetic (one row per wave, any of weight / bias / modulation absent); q8 [total_rows][D], q8_scale [total_rows].
+// ln_mod_kernel's arithmetic (ln_mod_row: one row per wave, any of weight / bias / modulation absent); q8 [total_rows][D], q8_scale [total_rows].
 // Every call takes this form, the many-row AdaLN calls too: with the third reduction and the conversion in the row's dependency
 // chain, the occupancy of this kernel (97 registers at D = 3072) hid more than the rows-per-wave form of ln_mod_rows_kernel saved
 // in parameter traffic (C2 call, 35,552 rows: 95 - 99 us here, 105 - 110 us in that form; profiles/cog_fp8_step_ab.json).
@@ -242,46 +218,7 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
   const int seg = r >= seg_split ? 1 : 0;
   const bf16_t* xr = x + (int64_t)bidx * x_bs + (int64_t)r * D;
   float v[ITERS][8];
-  float s = 0.0f;
-#pragma unroll
-  for (int i = 0; i < ITERS; ++i) {
-    unpack8(*(const uint4*)(xr + i * 512 + lane * 8), v[i]);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) s += v[i][k];
-  }
-  const float mean = wave_sum(s) * (1.0f / D);
-  float q = 0.0f;
-#pragma unroll
-  for (int i = 0; i < ITERS; ++i)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const float d = v[i][k] - mean;
-      q = fmaf(d, d, q);
-    }
-  const float rstd = rsqrtf(wave_sum(q) * (1.0f / D) + eps);
-  const bf16_t* sc = scale ? scale + (int64_t)bidx * mod_bs + (int64_t)seg * seg_stride : nullptr;
-  const bf16_t* sh = shift ? shift + (int64_t)bidx * mod_bs + (int64_t)seg * seg_stride : nullptr;
-#pragma unroll
-  for (int i = 0; i < ITERS; ++i) {
-    const int c0 = i * 512 + lane * 8;
-    float wv[8], bv[8];
-    if (w) unpack8(*(const uint4*)(w + c0), wv);
-    if (bs) unpack8(*(const uint4*)(bs + c0), bv);
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float n = (v[i][k] - mean) * rstd;
-      if (w) n = n * wv[k];
-      if (bs) n = n + bv[k];
-      v[i][k] = rbf(n);
-    }
-    if (sc) {
-      float scv[8], shv[8];
-      unpack8(*(const uint4*)(sc + c0), scv);
-      unpack8(*(const uint4*)(sh + c0), shv);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[i][k] = rbf(rbf(v[i][k] * rbf(1.0f + scv[k])) + shv[k]);
-    }
-  }
+  ln_mod_row<ITERS>(xr, w, bs, scale, shift, mod_bs, seg_stride, bidx, seg, lane, eps, v);
   quantize_row_store<ITERS>(v, lane, q8 + row * D, q8_scale + row);
 }
 
@@ -399,6 +336,111 @@ __global__ __launch_bounds__(256) void qk_norm_rope_token_kernel(bf16_t* __restr
 
 using namespace alg;
 
+// ---- LayerNorm + modulation with bf16 parameters: alg_layernorm_modulate, _seg (y) and _fp8, _seg_fp8 (q8 + q8_scale).
+// One operand struct; check, plan, launch (rownorm_host.h) ----
+struct LnModArgs {
+  bool fp8;                  // the e4m3 twins: q8 + q8_scale instead of y
+  const void* x;
+  void* y;
+  void* q8;
+  float* q8_scale;
+  const void *weight, *bias, *scale, *shift;
+  int64_t mod_bstride, seg_stride;
+  int batch, rows, D;
+  int64_t x_bstride, y_bstride;
+  int seg_split;
+  float eps;
+  hipStream_t stream;
+};
+
+// the widths (D / 512) of ln_mod_kernel / ln_mod_fp8_kernel and of ln_mod_rows_kernel (written downwards: hipcc emits the
+// instantiations a fold names last to first, and the object has always held them upwards)
+using LnIters = IterSet<16, 15, 14, 13, 12, 11, 10, 9, 8, 7, 6, 5, 4, 3, 2, 1>;
+using LnRowsIters = IterSet<6, 5, 4, 3, 2, 1>;
+
+static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
+
+// `entry` is the name the messages carry: the _seg forms report as the entries they extend
+static int ln_mod_check(const LnModArgs& a, const char* entry) {
+  if (!a.x || (a.fp8 ? !a.q8 || !a.q8_scale : !a.y) || a.batch <= 0 || a.rows <= 0 || a.D <= 0 || a.seg_stride % 8) {
+    set_error("%s: bad argument (batch=%d rows=%d D=%d)", entry, a.batch, a.rows, a.D);
+    return ALG_EINVAL;
+  }
+  if (a.D % 512 != 0 || a.D > 8192) {
+    set_error("%s: D=%d must be a multiple of 512 and <= 8192", entry, a.D);
+    return ALG_EINVAL;
+  }
+  if ((a.scale == nullptr) != (a.shift == nullptr)) {
+    set_error("%s: scale and shift must be given together", entry);
+    return ALG_EINVAL;
+  }
+  const bool params_off = misaligned16(a.x) || misaligned16(a.weight) || misaligned16(a.bias) || misaligned16(a.scale) ||
+                          misaligned16(a.shift) || a.mod_bstride % 8 || a.x_bstride % 8;
+  if (a.fp8 ? params_off || ((uintptr_t)a.q8 & 7) || ((uintptr_t)a.q8_scale & 3) : params_off || misaligned16(a.y) || a.y_bstride % 8) {
+    if (a.fp8) set_error("%s: x and the parameter rows must be 16-byte aligned, q8 8-byte aligned", entry);
+    else set_error("%s: pointers must be 16-byte aligned", entry);
+    return ALG_EINVAL;
+  }
+  const int64_t total = (int64_t)a.batch * a.rows;
+  if (!row_blocks_fit((total + 3) / 4)) {
+    const int rc = row_elimit(entry, "batch * rows", total);
+    return a.fp8 ? ALG_EINVAL : rc;   // the e4m3 entries have always refused this, with this code
+  }
+  return ALG_OK;
+}
+
+// Which kernel, how many rows per wave, which grid.  MANY_ROWS -- many rows with all four parameter rows present (every AdaLN of
+// the CogVideoX / HunyuanVideo blocks), up to D = 3072, bf16 output: rpw so that the call is one resident round of waves
+// (CUs x 4 SIMDs x 2 waves of that kernel: 2048 on an MI355X), at least 8.  The e4m3 twins always take one row per wave
+// (ln_mod_fp8_kernel's comment has the measurement).
+static RowPlan ln_mod_plan(const LnModArgs& a, int cus) {
+  const int64_t total = (int64_t)a.batch * a.rows;
+  if (!a.fp8 && a.weight && a.bias && a.scale && a.D <= 3072 && total >= 4096) {
+    const int64_t resident_waves = (int64_t)cus * 8;
+    const int rpw = (int)std::max<int64_t>(8, (total + resident_waves - 1) / resident_waves);
+    return {RowRoute::MANY_ROWS, rpw, (unsigned)((total + 4 * (int64_t)rpw - 1) / (4 * (int64_t)rpw))};
+  }
+  return row_plan_one(RowRoute::ONE_ROW, total);
+}
+
+static int ln_mod_entry(const LnModArgs& a, const char* entry) {
+  if (const int rc = ln_mod_check(a, entry)) return rc;
+  const RowPlan pl = ln_mod_plan(a, device_cus());
+  const dim3 grid(pl.grid), blk(256);
+  const int64_t total = (int64_t)a.batch * a.rows;
+  const bf16_t *x = (const bf16_t*)a.x, *w = (const bf16_t*)a.weight, *bs = (const bf16_t*)a.bias, *sc = (const bf16_t*)a.scale,
+               *sh = (const bf16_t*)a.shift;
+  // (the three width-templated kernels are named in the order the object has always held them)
+  if (pl.route == RowRoute::MANY_ROWS) {
+    dispatch_iters(a.D / 512, LnRowsIters{}, [&](auto it) {
+      hipLaunchKernelGGL((ln_mod_rows_kernel<it.value>), grid, blk, 0, a.stream, x, (bf16_t*)a.y, w, bs, sc, sh, a.mod_bstride,
+                         a.x_bstride, a.y_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps, pl.rpw);
+    });
+  } else if (!a.fp8) {
+    dispatch_iters(a.D / 512, LnIters{}, [&](auto it) {
+      hipLaunchKernelGGL(ln_mod_kernel<it.value>, grid, blk, 0, a.stream, x, (bf16_t*)a.y, w, bs, sc, sh, a.mod_bstride, a.x_bstride,
+                         a.y_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps);
+    });
+  } else {
+    dispatch_iters(a.D / 512, LnIters{}, [&](auto it) {
+      hipLaunchKernelGGL(ln_mod_fp8_kernel<it.value>, grid, blk, 0, a.stream, x, (uint8_t*)a.q8, a.q8_scale, w, bs, sc, sh,
+                         a.mod_bstride, a.x_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps);
+    });
+  }
+  return row_check_launch(entry, pl);
+}
+
+extern "C" int alg_layernorm_modulate_seg(const void* x, void* y, const void* weight, const void* bias,
+                                          const void* scale, const void* shift, int64_t mod_bstride,
+                                          int64_t seg_stride, int batch, int rows, int D, int64_t x_bstride,
+                                          int64_t y_bstride, int seg_split, float eps, void* stream) {
+  LnModArgs a = {};
+  a.fp8 = false; a.x = x; a.y = y; a.weight = weight; a.bias = bias; a.scale = scale; a.shift = shift;
+  a.mod_bstride = mod_bstride; a.seg_stride = seg_stride; a.batch = batch; a.rows = rows; a.D = D;
+  a.x_bstride = x_bstride; a.y_bstride = y_bstride; a.seg_split = seg_split; a.eps = eps; a.stream = (hipStream_t)stream;
+  return ln_mod_entry(a, "alg_layernorm_modulate");
+}
+
 extern "C" int alg_layernorm_modulate(const void* x, void* y, const void* weight, const void* bias,
                                       const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows,
                                       int D, int64_t x_bstride, int64_t y_bstride, int seg_split, float eps,
@@ -407,58 +449,15 @@ extern "C" int alg_layernorm_modulate(const void* x, void* y, const void* weight
                                     seg_split, eps, stream);
 }
 
-extern "C" int alg_layernorm_modulate_seg(const void* x, void* y, const void* weight, const void* bias,
-                                          const void* scale, const void* shift, int64_t mod_bstride,
-                                          int64_t seg_stride, int batch, int rows, int D, int64_t x_bstride,
-                                          int64_t y_bstride, int seg_split, float eps, void* stream) {
-  if (!x || !y || batch <= 0 || rows <= 0 || D <= 0 || seg_stride % 8) {
-    set_error("alg_layernorm_modulate: bad argument (batch=%d rows=%d D=%d)", batch, rows, D);
-    return ALG_EINVAL;
-  }
-  if (D % 512 != 0 || D > 8192) {
-    set_error("alg_layernorm_modulate: D=%d must be a multiple of 512 and <= 8192", D);
-    return ALG_EINVAL;
-  }
-  if ((scale == nullptr) != (shift == nullptr)) {
-    set_error("alg_layernorm_modulate: scale and shift must be given together");
-    return ALG_EINVAL;
-  }
-  if (((uintptr_t)x & 15) || ((uintptr_t)y & 15) || ((uintptr_t)weight & 15) || ((uintptr_t)bias & 15) ||
-      ((uintptr_t)scale & 15) || ((uintptr_t)shift & 15) || (mod_bstride % 8) || (x_bstride % 8) ||
-      (y_bstride % 8)) {
-    set_error("alg_layernorm_modulate: pointers must be 16-byte aligned");
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  const unsigned grid = (unsigned)((total + 3) / 4);
-  hipStream_t s = (hipStream_t)stream;
-  // many rows with all four parameter rows present (every AdaLN of the CogVideoX / HunyuanVideo blocks): the multi-row form
-  if (weight && bias && scale && D <= 3072 && total >= 4096) {
-    const int64_t resident_waves = (int64_t)device_cus() * 8;   // CUs x 4 SIMDs x 2 waves of this kernel (2048 on an MI355X)
-    const int rpw = (int)std::max<int64_t>(8, (total + resident_waves - 1) / resident_waves);
-    const unsigned g2 = (unsigned)((total + 4 * (int64_t)rpw - 1) / (4 * (int64_t)rpw));
-#define LN_ROWS(I)                                                                                                      \
-  case I:                                                                                                               \
-    hipLaunchKernelGGL((ln_mod_rows_kernel<I>), dim3(g2), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y,                 \
-                       (const bf16_t*)weight, (const bf16_t*)bias, (const bf16_t*)scale, (const bf16_t*)shift,          \
-                       mod_bstride, x_bstride, y_bstride, total, rows, seg_split, seg_stride, eps, rpw);                \
-    break;
-    switch (D / 512) { LN_ROWS(1) LN_ROWS(2) LN_ROWS(3) LN_ROWS(4) LN_ROWS(5) LN_ROWS(6) }
-#undef LN_ROWS
-    return check_launch("alg_layernorm_modulate");
-  }
-#define LN_CASE(I)                                                                                                  \
-  case I:                                                                                                           \
-    hipLaunchKernelGGL(ln_mod_kernel<I>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y,                  \
-                       (const bf16_t*)weight, (const bf16_t*)bias, (const bf16_t*)scale, (const bf16_t*)shift,      \
-                       mod_bstride, x_bstride, y_bstride, total, rows, seg_split, seg_stride, eps);                                                   \
-    break;
-  switch (D / 512) {
-    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
-    LN_CASE(9) LN_CASE(10) LN_CASE(11) LN_CASE(12) LN_CASE(13) LN_CASE(14) LN_CASE(15) LN_CASE(16)
-  }
-#undef LN_CASE
-  return check_launch("alg_layernorm_modulate");
+extern "C" int alg_layernorm_modulate_seg_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
+                                              const void* scale, const void* shift, int64_t mod_bstride, int64_t seg_stride,
+                                              int batch, int rows, int D, int64_t x_bstride, int seg_split, float eps,
+                                              void* stream) {
+  LnModArgs a = {};
+  a.fp8 = true; a.x = x; a.q8 = q8; a.q8_scale = q8_scale; a.weight = weight; a.bias = bias; a.scale = scale; a.shift = shift;
+  a.mod_bstride = mod_bstride; a.seg_stride = seg_stride; a.batch = batch; a.rows = rows; a.D = D;
+  a.x_bstride = x_bstride; a.seg_split = seg_split; a.eps = eps; a.stream = (hipStream_t)stream;
+  return ln_mod_entry(a, "alg_layernorm_modulate_fp8");
 }
 
 extern "C" int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
@@ -466,48 +465,6 @@ extern "C" int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_sca
                                           int D, int64_t x_bstride, int seg_split, float eps, void* stream) {
   return alg_layernorm_modulate_seg_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstride, D, batch, rows, D, x_bstride,
                                         seg_split, eps, stream);
-}
-
-extern "C" int alg_layernorm_modulate_seg_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
-                                              const void* scale, const void* shift, int64_t mod_bstride, int64_t seg_stride,
-                                              int batch, int rows, int D, int64_t x_bstride, int seg_split, float eps,
-                                              void* stream) {
-  if (!x || !q8 || !q8_scale || batch <= 0 || rows <= 0 || D <= 0 || seg_stride % 8) {
-    set_error("alg_layernorm_modulate_fp8: bad argument (batch=%d rows=%d D=%d)", batch, rows, D);
-    return ALG_EINVAL;
-  }
-  if (D % 512 != 0 || D > 8192) {
-    set_error("alg_layernorm_modulate_fp8: D=%d must be a multiple of 512 and <= 8192", D);
-    return ALG_EINVAL;
-  }
-  if ((scale == nullptr) != (shift == nullptr)) {
-    set_error("alg_layernorm_modulate_fp8: scale and shift must be given together");
-    return ALG_EINVAL;
-  }
-  if (((uintptr_t)x & 15) || ((uintptr_t)q8 & 7) || ((uintptr_t)q8_scale & 3) || ((uintptr_t)weight & 15) ||
-      ((uintptr_t)bias & 15) || ((uintptr_t)scale & 15) || ((uintptr_t)shift & 15) || (mod_bstride % 8) || (x_bstride % 8)) {
-    set_error("alg_layernorm_modulate_fp8: x and the parameter rows must be 16-byte aligned, q8 8-byte aligned");
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  if ((total + 3) / 4 > 0x7fffffff) {
-    set_error("alg_layernorm_modulate_fp8: batch * rows = %lld is more than one launch covers", (long long)total);
-    return ALG_EINVAL;
-  }
-  const unsigned grid = (unsigned)((total + 3) / 4);
-  hipStream_t s = (hipStream_t)stream;
-#define LN_CASE(I)                                                                                                  \
-  case I:                                                                                                           \
-    hipLaunchKernelGGL(ln_mod_fp8_kernel<I>, dim3(grid), dim3(256), 0, s, (const bf16_t*)x, (uint8_t*)q8, q8_scale,  \
-                       (const bf16_t*)weight, (const bf16_t*)bias, (const bf16_t*)scale, (const bf16_t*)shift,      \
-                       mod_bstride, x_bstride, total, rows, seg_split, seg_stride, eps);                            \
-    break;
-  switch (D / 512) {
-    LN_CASE(1) LN_CASE(2) LN_CASE(3) LN_CASE(4) LN_CASE(5) LN_CASE(6) LN_CASE(7) LN_CASE(8)
-    LN_CASE(9) LN_CASE(10) LN_CASE(11) LN_CASE(12) LN_CASE(13) LN_CASE(14) LN_CASE(15) LN_CASE(16)
-  }
-#undef LN_CASE
-  return check_launch("alg_layernorm_modulate_fp8");
 }
 
 extern "C" int alg_qk_norm_rope_scaled(void* qk, const void* wq, const void* bq, const void* wk, const void* bk,

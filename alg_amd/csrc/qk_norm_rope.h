@@ -9,6 +9,7 @@
 // two xor-shuffles over four lanes followed by one add of the two half-vectors give.
 #pragma once
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 
@@ -18,21 +19,6 @@ struct QkNormRope {           // device-side copy of alg_qk_norm_rope_args
   int heads, text_len;
   float eps, q_scale;
 };
-
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-  }
-}
-
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint4 v;
-  v.x = pack_bf2(f[0], f[1]); v.y = pack_bf2(f[2], f[3]); v.z = pack_bf2(f[4], f[5]); v.w = pack_bf2(f[6], f[7]);
-  return v;
-}
 
 __device__ __forceinline__ float qk_chunk_sum(const float (&v)[8]) {
 #pragma clang fp contract(off)

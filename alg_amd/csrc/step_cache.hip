@@ -10,6 +10,7 @@
 // by shuffle, the waves of a block through LDS, one partial pair per block into the caller's workspace, and a second launch of
 // one block sums the workspace.  No atomics.
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 
@@ -19,15 +20,6 @@ constexpr int64_t SC_MAX_BLOCKS = 2048;   // 8 resident blocks on each of 256 co
 inline int64_t sc_blocks(int64_t nvec) {
   const int64_t want = (nvec + SC_THREADS - 1) / SC_THREADS;
   return want < 1 ? 1 : (want > SC_MAX_BLOCKS ? SC_MAX_BLOCKS : want);
-}
-
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-  }
 }
 
 // one 8-element vector: returns r packed, adds this vector's terms (fp32, chain of 8) to the double accumulators

@@ -7,20 +7,10 @@
 //                       op rounded as the eager bf16 graph does (scores, + bias, fp32 softmax -> bf16 P, P @ V)
 //   alg_mul_bf16        gated-GELU product
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace t5 {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
 
 __global__ __launch_bounds__(256) void embed_kernel(const int64_t* __restrict__ ids, const bf16_t* __restrict__ table,
                                                     bf16_t* __restrict__ out, int64_t n, int D, int vocab) {
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(256) void attn_bias_kernel(const bf16_t* __restrict
       acc[c] = s;
       m = fmaxf(m, s);
     }
-    m = wave_max(m);
+    m = xor_max<64>(m);
     float sum = 0.0f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
@@ -163,11 +153,6 @@ __global__ __launch_bounds__(256) void mul_kernel(const bf16_t* __restrict__ a, 
     o[e] = f2bf(bf2f(a[e]) * bf2f(b[e]));
 }
 
-static unsigned grid_for(int64_t total) {
-  const int64_t want = (total + 255) / 256;
-  return (unsigned)(want < 1 ? 1 : (want > 8192 ? 8192 : want));
-}
-
 }  // namespace t5
 }  // namespace alg
 
@@ -183,7 +168,7 @@ extern "C" int alg_embed_rows(const int64_t* ids, const void* table, void* out, 
     set_error("alg_embed_rows: null pointer");
     return ALG_EINVAL;
   }
-  hipLaunchKernelGGL(t5::embed_kernel, dim3(t5::grid_for(n * (D >> 3))), dim3(256), 0, (hipStream_t)stream, ids,
+  hipLaunchKernelGGL(t5::embed_kernel, dim3(grid_for(n * (D >> 3))), dim3(256), 0, (hipStream_t)stream, ids,
                      (const bf16_t*)table, (bf16_t*)out, n, D, vocab);
   return check_launch("alg_embed_rows");
 }
@@ -254,7 +239,7 @@ extern "C" int alg_quick_gelu(void* x, int64_t numel, void* stream) {
     set_error("alg_quick_gelu: null pointer");
     return ALG_EINVAL;
   }
-  hipLaunchKernelGGL(t5::quick_gelu_kernel, dim3(t5::grid_for(numel)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, numel);
+  hipLaunchKernelGGL(t5::quick_gelu_kernel, dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, numel);
   return check_launch("alg_quick_gelu");
 }
 
@@ -268,7 +253,7 @@ extern "C" int alg_mul_bf16(const void* a, const void* b, void* out, int64_t num
     set_error("alg_mul_bf16: null pointer");
     return ALG_EINVAL;
   }
-  hipLaunchKernelGGL(t5::mul_kernel, dim3(t5::grid_for(numel)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a,
+  hipLaunchKernelGGL(t5::mul_kernel, dim3(grid_for(numel)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)a,
                      (const bf16_t*)b, (bf16_t*)out, numel);
   return check_launch("alg_mul_bf16");
 }

@@ -8,16 +8,10 @@
 // The published decoder runs in batches of latent frames (3 first, then 2) and GroupNorm takes its statistics over one
 // batch: `first_len` / `seg_len` carry those segments, so the whole video is normalised in one launch with the same numbers.
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace vae {
-
-__device__ __forceinline__ void unpack8(const uint4 d, float (&f)[8]) {
-  f[0] = __uint_as_float(d.x << 16), f[1] = __uint_as_float(d.x & 0xffff0000u);
-  f[2] = __uint_as_float(d.y << 16), f[3] = __uint_as_float(d.y & 0xffff0000u);
-  f[4] = __uint_as_float(d.z << 16), f[5] = __uint_as_float(d.z & 0xffff0000u);
-  f[6] = __uint_as_float(d.w << 16), f[7] = __uint_as_float(d.w & 0xffff0000u);
-}
 
 __device__ __forceinline__ int segment_of(const alg_vae_geom& g, int t) {
   return t < g.first_len ? 0 : 1 + (t - g.first_len) / g.seg_len;

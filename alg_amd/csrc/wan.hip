@@ -4,31 +4,14 @@
 // module: the FP32LayerNorm / modulation chain is fp32 with ONE rounding to bf16 at the end; RMSNorm rounds once after the
 // normalisation and once after the weight; the rotary product is rounded once (the reference evaluates it in fp64).
 #include "common.h"
+#include "rownorm_host.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace wan {
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-  }
-}
-
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint4 v;
-  v.x = pack_bf2(f[0], f[1]); v.y = pack_bf2(f[2], f[3]); v.z = pack_bf2(f[4], f[5]); v.w = pack_bf2(f[6], f[7]);
-  return v;
-}
-
+// (The e4m3 epilogues of the two LayerNorm kernels and the rmsnorm_rope pair below keep their own text of the row quantiser: written
+// through row_ops.h's e4m3_row_store / a shared front hipcc scheduled them differently, and their device code is held byte for byte.)
 // y = bf16( LN_fp32(x) [* w + b] [* (1 + scale[b]) + shift[b]] )
 // q8 != nullptr (fp8 mode): the bf16-rounded row is quantised in registers as alg_quantize_fp8_rows would (amax / 448 per
 // row, OCP e4m3) and ONLY the bytes + the row scale are written: the separate quantiser pass over y disappears.
@@ -188,11 +171,9 @@ __global__ __launch_bounds__(256) void ln_mod_f32_rows_kernel(const bf16_t* __re
 #pragma unroll
     for (int i = 0; i < ITERS; ++i) {
       const int c0 = i * 512 + lane * 8;
-      const float4 s0 = *(const float4*)(prm + c0), s1 = *(const float4*)(prm + c0 + 4);
-      const float4 h0 = *(const float4*)(prm + D + c0), h1 = *(const float4*)(prm + D + c0 + 4);
-      const float s1v[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-      const float shv[8] = {h0.x, h0.y, h0.z, h0.w, h1.x, h1.y, h1.z, h1.w};
-      float o[8];
+      float s1v[8], shv[8], o[8];
+      load8(prm + c0, s1v);
+      load8(prm + D + c0, shv);
 #pragma unroll
       for (int k = 0; k < 8; ++k) {
         float n = (v[i][k] - mean) * rstd;
@@ -491,141 +472,145 @@ __global__ __launch_bounds__(256) void gelu_erf_kernel(bf16_t* __restrict__ x, i
 
 using namespace alg;
 
-#define DISPATCH_ITERS(ITERS_EXPR, CALL)                                  \
-  switch (ITERS_EXPR) {                                                   \
-    case 1: { constexpr int IT = 1; CALL; } break;                        \
-    case 2: { constexpr int IT = 2; CALL; } break;                        \
-    case 3: { constexpr int IT = 3; CALL; } break;                        \
-    case 4: { constexpr int IT = 4; CALL; } break;                        \
-    case 6: { constexpr int IT = 6; CALL; } break;                        \
-    case 8: { constexpr int IT = 8; CALL; } break;                        \
-    case 10: { constexpr int IT = 10; CALL; } break;                      \
-    case 12: { constexpr int IT = 12; CALL; } break;                      \
-    default: ok = false;                                                  \
-  }
+// the widths (D / 512) every width-templated kernel of this file is instantiated for (written downwards: hipcc emits the
+// instantiations a fold names last to first, and the object has always held them upwards)
+using WanIters = IterSet<12, 10, 8, 6, 4, 3, 2, 1>;
 
-static int layernorm_mod_entry(const char* who, const void* x, void* y, void* q8, float* q8_scale, const float* weight,
-                               const float* bias, const float* scale, const float* shift, int64_t mod_bstride, int batch,
-                               int rows, int D, float eps, void* stream) {
-  if (batch < 0 || rows < 0 || D <= 0) {
-    set_error("%s: bad shape batch=%d rows=%d D=%d", who, batch, rows, D);
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  if (total == 0) return ALG_OK;
-  if (!x || (!y && !q8) || (q8 && !q8_scale)) {
-    set_error("%s: null pointer", who);
-    return ALG_EINVAL;
-  }
-  const dim3 grid((unsigned)((total + 3) / 4)), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  bool ok = D % 512 == 0;
-  const bool mod_only = !weight && !bias && scale && shift, affine_only = weight && bias && !scale && !shift;
-  const float* p0 = mod_only ? scale : weight;
-  const float* p1 = mod_only ? shift : bias;
-  if (ok && (mod_only || affine_only) && total >= 4096 && D <= 6144 && (!mod_only || (mod_bstride & 3) == 0) &&
+// ---- LayerNorm with fp32 parameters: alg_layernorm_mod_f32 (y) and alg_layernorm_mod_f32_fp8 (q8 + q8_scale) ----
+struct LnF32Args {
+  const void* x;
+  void* y;
+  void* q8;
+  float* q8_scale;
+  const float *weight, *bias, *scale, *shift;
+  int64_t mod_bstride;
+  int batch, rows, D;
+  float eps;
+  hipStream_t stream;
+};
+
+// The many-row kernel takes exactly two parameter rows: the modulation alone, or the affine pair alone
+static bool ln_f32_mod_only(const LnF32Args& a) { return !a.weight && !a.bias && a.scale && a.shift; }
+static bool ln_f32_affine_only(const LnF32Args& a) { return a.weight && a.bias && !a.scale && !a.shift; }
+
+// Which kernel, how many rows per wave, which grid.  GENERIC: a width the register kernels are not built for.
+// MANY_ROWS: the parameters in the LDS, rpw rows per wave, about one resident round of workgroups (three of these 256-thread
+// workgroups fit a CU: 768 on an MI355X) -- from 4,096 rows, up to D = 6144, for two 16-byte aligned parameter rows.
+static RowPlan ln_f32_plan(const LnF32Args& a, int cus) {
+  const int64_t total = (int64_t)a.batch * a.rows;
+  if (a.D % 512 || !has_iters(a.D / 512, WanIters{})) return row_plan_one(RowRoute::GENERIC, total);
+  const bool mod_only = ln_f32_mod_only(a);
+  const float* p0 = mod_only ? a.scale : a.weight;
+  const float* p1 = mod_only ? a.shift : a.bias;
+  if ((mod_only || ln_f32_affine_only(a)) && total >= 4096 && a.D <= 6144 && (!mod_only || (a.mod_bstride & 3) == 0) &&
       !(((uintptr_t)p0 | (uintptr_t)p1) & 15)) {
-    // the modulated non-affine form over many rows: parameters in the LDS, rpw rows per wave, about one resident round of workgroups
-    // (three of these 256-thread workgroups fit a CU: 768 on an MI355X)
-    const int64_t resident_wgs = (int64_t)device_cus() * 3;
+    const int64_t resident_wgs = (int64_t)cus * 3;
     const int64_t want = (total + 4 * resident_wgs - 1) / (4 * resident_wgs);
     const int rpw = (int)(want < 8 ? 8 : want);
-    const int bpi = (rows + 4 * rpw - 1) / (4 * rpw);
-    bool built = true;   // (DISPATCH_ITERS clears `ok` for a width that is not instantiated: then the one-row kernel below takes the call)
-    {
-      bool ok = true;
-      DISPATCH_ITERS(D / 512, hipLaunchKernelGGL(wan::ln_mod_f32_rows_kernel<IT>, dim3((unsigned)(bpi * batch)), blk, 0, s,
-                                                 (const bf16_t*)x, (bf16_t*)y, p0, p1, mod_only ? mod_bstride : 0, rows, eps,
-                                                 (uint8_t*)q8, q8_scale, rpw, bpi, mod_only ? 1 : 0));
-      built = ok;
-    }
-    if (built) return check_launch(who);
+    const int bpi = (a.rows + 4 * rpw - 1) / (4 * rpw);   // workgroups per batch item
+    return {RowRoute::MANY_ROWS, rpw, (unsigned)(bpi * a.batch)};
   }
-  if (ok) {
-    DISPATCH_ITERS(D / 512, hipLaunchKernelGGL(wan::ln_mod_f32_kernel<IT>, grid, blk, 0, s, (const bf16_t*)x, (bf16_t*)y,
-                                               weight, bias, scale, shift, mod_bstride, total, rows, eps, (uint8_t*)q8,
-                                               q8_scale));
+  return row_plan_one(RowRoute::ONE_ROW, total);
+}
+
+static int ln_f32_check(const LnF32Args& a, const char* entry) {
+  if (a.batch < 0 || a.rows < 0 || a.D <= 0) {
+    set_error("%s: bad shape batch=%d rows=%d D=%d", entry, a.batch, a.rows, a.D);
+    return ALG_EINVAL;
   }
-  if (!ok) {
-    if (q8) {
-      set_error("%s: the fp8 output needs D %% 512 == 0 and D <= 6144 (D=%d)", who, D);
-      return ALG_EINVAL;
-    }
-    hipLaunchKernelGGL(wan::ln_mod_f32_generic_kernel, grid, blk, 0, s, (const bf16_t*)x, (bf16_t*)y, weight, bias, scale,
-                       shift, mod_bstride, total, rows, D, eps);
+  const int64_t total = (int64_t)a.batch * a.rows;
+  if (total == 0) return ROW_EMPTY;
+  if (!a.x || (!a.y && !a.q8) || (a.q8 && !a.q8_scale)) {
+    set_error("%s: null pointer", entry);
+    return ALG_EINVAL;
   }
-  return check_launch(who);
+  if (!row_blocks_fit((total + 3) / 4)) return row_elimit(entry, "batch * rows", total);
+  if (a.q8 && (a.D % 512 || !has_iters(a.D / 512, WanIters{}))) {
+    set_error("%s: the fp8 output needs D %% 512 == 0 and D <= 6144 (D=%d)", entry, a.D);
+    return ALG_EINVAL;
+  }
+  return ALG_OK;
+}
+
+static int layernorm_mod_entry(const LnF32Args& a, const char* entry) {
+  if (const int rc = ln_f32_check(a, entry)) return rc == ROW_EMPTY ? ALG_OK : rc;
+  const RowPlan pl = ln_f32_plan(a, device_cus());
+  const dim3 grid(pl.grid), blk(256);
+  const int64_t total = (int64_t)a.batch * a.rows;
+  const bf16_t* x = (const bf16_t*)a.x;
+  bf16_t* y = (bf16_t*)a.y;
+  uint8_t* q8 = (uint8_t*)a.q8;
+  // (the two width-templated kernels are named in the order the object has always held them: many rows, then one row)
+  if (pl.route == RowRoute::MANY_ROWS) {
+    const bool mod_only = ln_f32_mod_only(a);
+    dispatch_iters(a.D / 512, WanIters{}, [&](auto it) {
+      hipLaunchKernelGGL(wan::ln_mod_f32_rows_kernel<it.value>, grid, blk, 0, a.stream, x, y, mod_only ? a.scale : a.weight,
+                         mod_only ? a.shift : a.bias, mod_only ? a.mod_bstride : 0, a.rows, a.eps, q8, a.q8_scale, pl.rpw,
+                         (int)(pl.grid / a.batch), mod_only ? 1 : 0);
+    });
+  } else if (pl.route == RowRoute::ONE_ROW) {
+    dispatch_iters(a.D / 512, WanIters{}, [&](auto it) {
+      hipLaunchKernelGGL(wan::ln_mod_f32_kernel<it.value>, grid, blk, 0, a.stream, x, y, a.weight, a.bias, a.scale, a.shift,
+                         a.mod_bstride, total, a.rows, a.eps, q8, a.q8_scale);
+    });
+  } else {
+    hipLaunchKernelGGL(wan::ln_mod_f32_generic_kernel, grid, blk, 0, a.stream, x, y, a.weight, a.bias, a.scale, a.shift,
+                       a.mod_bstride, total, a.rows, a.D, a.eps);
+  }
+  return row_check_launch(entry, pl);
 }
 
 extern "C" int alg_layernorm_mod_f32(const void* x, void* y, const float* weight, const float* bias, const float* scale,
                                      const float* shift, int64_t mod_bstride, int batch, int rows, int D, float eps,
                                      void* stream) {
-  return layernorm_mod_entry("alg_layernorm_mod_f32", x, y, nullptr, nullptr, weight, bias, scale, shift, mod_bstride, batch,
-                             rows, D, eps, stream);
+  return layernorm_mod_entry({x, y, nullptr, nullptr, weight, bias, scale, shift, mod_bstride, batch, rows, D, eps,
+                              (hipStream_t)stream}, "alg_layernorm_mod_f32");
 }
 
 extern "C" int alg_layernorm_mod_f32_fp8(const void* x, void* q8, float* q8_scale, const float* weight, const float* bias,
                                          const float* scale, const float* shift, int64_t mod_bstride, int batch, int rows,
                                          int D, float eps, void* stream) {
-  return layernorm_mod_entry("alg_layernorm_mod_f32_fp8", x, nullptr, q8, q8_scale, weight, bias, scale, shift, mod_bstride,
-                             batch, rows, D, eps, stream);
+  return layernorm_mod_entry({x, nullptr, q8, q8_scale, weight, bias, scale, shift, mod_bstride, batch, rows, D, eps,
+                              (hipStream_t)stream}, "alg_layernorm_mod_f32_fp8");
+}
+
+// ---- RMSNorm + rope: operands and refusals are rownorm_host.h's (NormRopeArgs, norm_rope_check) ----
+static int rmsnorm_rope_not_built(const char* entry, int D) {
+  set_error("%s: D=%d is not built (D/512 in {1,2,3,4,6,8,10,12})", entry, D);
+  return ALG_ELIMIT;
 }
 
 extern "C" int alg_rmsnorm_rope(void* x, const void* weight, const float* cos_tab, const float* sin_tab,
                                 int64_t x_rstride, int batch, int rows, int D, float eps, void* stream) {
-  if (batch < 0 || rows < 0 || D <= 0 || D % 512 || x_rstride % 8 || (cos_tab && (D % 128 || !sin_tab))) {
-    set_error("alg_rmsnorm_rope: bad shape batch=%d rows=%d D=%d stride=%lld", batch, rows, D, (long long)x_rstride);
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  if (total == 0) return ALG_OK;
-  if (!x || !weight) {
-    set_error("alg_rmsnorm_rope: null pointer");
-    return ALG_EINVAL;
-  }
-  const dim3 grid((unsigned)((total + 3) / 4)), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  bool ok = true;
-  DISPATCH_ITERS(D / 512, hipLaunchKernelGGL(wan::rmsnorm_rope_kernel<IT>, grid, blk, 0, s, (bf16_t*)x,
-                                             (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, total, rows, eps));
-  if (!ok) {
-    set_error("alg_rmsnorm_rope: D=%d is not built (D/512 in {1,2,3,4,6,8,10,12})", D);
-    return ALG_ELIMIT;
-  }
+  NormRopeArgs a = {};
+  a.x = x; a.weight = weight; a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.x_rstride = x_rstride;
+  a.batch = batch; a.rows = rows; a.width = D;
+  if (const int rc = norm_rope_check(a, "alg_rmsnorm_rope")) return rc == ROW_EMPTY ? ALG_OK : rc;
+  const dim3 grid((unsigned)norm_rope_blocks(a)), blk(256);
+  if (!dispatch_iters(D / 512, WanIters{}, [&](auto it) {
+        hipLaunchKernelGGL(wan::rmsnorm_rope_kernel<it.value>, grid, blk, 0, (hipStream_t)stream, (bf16_t*)x, (const bf16_t*)weight, cos_tab,
+                           sin_tab, x_rstride, norm_rope_total(a), rows, eps);
+      }))
+    return rmsnorm_rope_not_built("alg_rmsnorm_rope", D);
   return check_launch("alg_rmsnorm_rope");
 }
 
 extern "C" int alg_rmsnorm_rope_fp8(const void* x, const void* weight, const float* cos_tab, const float* sin_tab,
                                     int64_t x_rstride, int batch, int rows, int D, float eps, void* q8, int64_t q8_rstride,
                                     float* scale, const float* head_scale, void* stream) {
-  if (batch < 0 || rows < 0 || D <= 0 || D % 512 || x_rstride % 8 || q8_rstride % 8 || q8_rstride < D ||
-      (cos_tab && (D % 128 || !sin_tab))) {
-    set_error("alg_rmsnorm_rope_fp8: bad shape batch=%d rows=%d D=%d strides=%lld / %lld", batch, rows, D, (long long)x_rstride,
-              (long long)q8_rstride);
-    return ALG_EINVAL;
-  }
-  const int64_t total = (int64_t)batch * rows;
-  if (total == 0) return ALG_OK;
-  if (!x || !weight || !q8 || (!scale && !head_scale) || ((uintptr_t)x & 15) || ((uintptr_t)q8 & 7)) {
-    set_error("alg_rmsnorm_rope_fp8: null or misaligned pointer (x 16-byte, q8 8-byte; scale or head_scale is needed)");
-    return ALG_EINVAL;
-  }
-  const dim3 grid((unsigned)((total + 3) / 4)), blk(256);
-  hipStream_t s = (hipStream_t)stream;
-  bool ok = true;
-  DISPATCH_ITERS(D / 512, hipLaunchKernelGGL(wan::rmsnorm_rope_fp8_kernel<IT>, grid, blk, 0, s, (const bf16_t*)x,
-                                             (const bf16_t*)weight, cos_tab, sin_tab, x_rstride, total, rows, eps, (uint8_t*)q8,
-                                             q8_rstride, scale, head_scale));
-  if (!ok) {
-    set_error("alg_rmsnorm_rope_fp8: D=%d is not built (D/512 in {1,2,3,4,6,8,10,12})", D);
-    return ALG_ELIMIT;
-  }
+  NormRopeArgs a = {};
+  a.x = x; a.weight = weight; a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.x_rstride = x_rstride;
+  a.batch = batch; a.rows = rows; a.width = D;
+  a.fp8 = true; a.q8 = q8; a.q8_rstride = q8_rstride; a.scale = scale; a.head_scale = head_scale;
+  if (const int rc = norm_rope_check(a, "alg_rmsnorm_rope_fp8")) return rc == ROW_EMPTY ? ALG_OK : rc;
+  const dim3 grid((unsigned)norm_rope_blocks(a)), blk(256);
+  if (!dispatch_iters(D / 512, WanIters{}, [&](auto it) {
+        hipLaunchKernelGGL(wan::rmsnorm_rope_fp8_kernel<it.value>, grid, blk, 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)weight,
+                           cos_tab, sin_tab, x_rstride, norm_rope_total(a), rows, eps, (uint8_t*)q8, q8_rstride, scale,
+                           head_scale);
+      }))
+    return rmsnorm_rope_not_built("alg_rmsnorm_rope_fp8", D);
   return check_launch("alg_rmsnorm_rope_fp8");
-}
-
-static unsigned grid_for(int64_t total) {
-  const int64_t want = (total + 255) / 256;
-  return (unsigned)(want < 1 ? 1 : (want > 8192 ? 8192 : want));
 }
 
 extern "C" int alg_wan_modulation(const float* table, const void* vec, float* out, int layers, int batch, int J, int D,

@@ -7,18 +7,10 @@
 //     scores arrive as TWO bf16 matrices, hi = -bf16(-q k^T) and lo = bf16(q k^T - hi) (the second GEMM takes the first
 //     one's output as its residual), so the softmax sees the fp32 scores to 2^-17 instead of bf16-rounded ones.
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace wanvae {
-
-__device__ __forceinline__ void unpack8(const uint4 v, float (&f)[8]) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-  }
-}
 
 // y[r][c] = act( x[r][c] * sqrt(C) / max(||x[r][:C]||, 1e-12) * gamma[c] ) for c < C, 0 for C <= c < Cp.
 // One wave per row; Cp a multiple of 8.  fp32 statistics, one bf16 rounding at the end.
