@@ -37,7 +37,7 @@ EXPORTS = (
     "alg_flash_attn_d128_ranges", "alg_flash_attn_d64_ranges", "alg_flash_attn_d128_ranges_heads", "alg_attn_lse_recall", "alg_flash_attn_d64_ranges_heads",
     "alg_flash_attn_d128_ranges_order", "alg_flash_attn_d64_ranges_order",
     "alg_flash_attn_d128_ranges_prefix", "alg_attn_prefix_mass",
-    "alg_gemm_fp4", "alg_quantize_mxfp4_rows",
+    "alg_gemm_fp4", "alg_quantize_mxfp4_rows", "alg_gemm_fp4_q4out", "alg_layernorm_modulate_mxfp4",
     "alg_attn_rows_position_major", "alg_attn_vt_position_major",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
@@ -165,6 +165,8 @@ def load_library():
     lib.alg_gemm_fp8.argtypes = [POINTER(GemmArgs), c_void_p]
     lib.alg_gemm_fp4.argtypes = [POINTER(GemmArgs), c_void_p]
     lib.alg_quantize_mxfp4_rows.argtypes = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_void_p]
+    lib.alg_gemm_fp4_q4out.argtypes = [POINTER(GemmArgs), c_void_p, c_int64, c_void_p]
+    lib.alg_layernorm_modulate_mxfp4.argtypes = [c_void_p] * 7 + [c_int64, c_int, c_int, c_int, c_int64, c_int, c_float, c_void_p]
     lib.alg_conv_cl_bf16.argtypes = [c_void_p] * 5 + [c_int] * 7 + [c_void_p]
     lib.alg_vae_groupnorm_workspace.argtypes = [POINTER(VaeGeom)]
     lib.alg_vae_groupnorm_stats.argtypes = [c_void_p, POINTER(VaeGeom), c_float, c_void_p, c_void_p, c_void_p]
@@ -1202,10 +1204,14 @@ def quantize_mxfp4_rows(x, q, scales, rows, K, x_rstride=None, x_off=0, q_off=0,
 
 
 def gemm_fp4(A, B, C, M, N, K, lda, ldb, ldc, a_scale=None, b_scale=None, a_off=0, b_off=0, a_scale_off=0, b_scale_off=0,
-             strideAScale=0, strideBScale=0, **kw):
+             strideAScale=0, strideBScale=0, q_out_scales=None, q_out_scales_off=0, strideOutScales=0, **kw):
     """`gemm` with OCP MXFP4 operands (alg_gemm_fp4): A [.., M, K/2] and B [.., N, K/2] hold packed e2m1 bytes, a_scale / b_scale
     the E8M0 bytes [.., rows, K/32] (all uint8).  lda / ldb / strideA / strideB / a_off / b_off count elements (two per byte);
-    the scale offsets and batch strides count bytes.  Every other keyword is `gemm`'s; a PackedB is refused."""
+    the scale offsets and batch strides count bytes.  Every other keyword is `gemm`'s; a PackedB is refused.
+
+    q_out_scales (alg_gemm_fp4_q4out): the output is MXFP4 too -- C is then a uint8 tensor that receives [.., M, N/2] packed e2m1
+    bytes (ldc / strideC / c_off still count elements) and q_out_scales [.., M, N/32] E8M0 bytes (offset and batch stride in
+    bytes), bit for bit what quantize_mxfp4_rows makes of the bf16 C.  N % 32 == 0, no residual, no gate, C must not be A."""
     if isinstance(B, PackedB) or isinstance(A, PackedB):
         raise AlgHipError("a packed B holds bf16 weight fragments for GEMM schedule 11: the MXFP4 GEMM takes row-major e2m1 bytes")
     if a_scale is None or b_scale is None:
@@ -1216,13 +1222,35 @@ def gemm_fp4(A, B, C, M, N, K, lda, ldb, ldc, a_scale=None, b_scale=None, a_off=
         raise AlgHipError("gemm_fp4: K = %d must be a positive multiple of 256" % K)
     if a_off % 2 or b_off % 2:
         raise AlgHipError("gemm_fp4: a_off / b_off count e2m1 elements and must be even (whole bytes)")
+    c_off = 0
+    if q_out_scales is not None:
+        _bytes_dev(C, "C"), _bytes_dev(q_out_scales, "q_out_scales")
+        c_off = kw.pop("c_off", 0)
+        batch = kw.get("batch", 1)
+        if N <= 0 or N % 32 or ldc % 32 or ldc < N or c_off % 2 or kw.get("strideC", 0) % 32:
+            raise AlgHipError("gemm_fp4: an MXFP4 output needs N = %d %% 32 == 0, ldc >= N, ldc / strideC multiples of 32 elements "
+                              "and an even c_off" % N)
+        if kw.get("R") is not None or kw.get("gate") is not None:
+            raise AlgHipError("gemm_fp4: the residual epilogue (R, gate) has no MXFP4 output")
+        if kw.get("act", ACT_NONE) not in (ACT_NONE, ACT_GELU_TANH):
+            raise AlgHipError("gemm_fp4: the MXFP4 output is built for ACT_NONE and ACT_GELU_TANH")
+        if c_off // 2 + (batch - 1) * (kw.get("strideC", 0) // 2) + (M - 1) * (ldc // 2) + N // 2 > C.numel() or \
+                q_out_scales_off + (batch - 1) * strideOutScales + M * (N // 32) > q_out_scales.numel():
+            raise AlgHipError("gemm_fp4: %d x %d rows of N = %d do not fit the MXFP4 output tensors" % (batch, M, N))
+        if C.data_ptr() == A.data_ptr() or q_out_scales.data_ptr() == a_scale.data_ptr():
+            raise AlgHipError("gemm_fp4: the MXFP4 output cannot be written over the A operand it is computed from")
     args, _ = gemm_args(A, B, C, M, N, K, lda, ldb, ldc, **kw)
     args.A = A.data_ptr() + a_off // 2
     args.B = B.data_ptr() + b_off // 2
     args.a_scale = a_scale.data_ptr() + a_scale_off
     args.b_scale = b_scale.data_ptr() + b_scale_off
     args.strideAScale, args.strideBScale = strideAScale, strideBScale
-    _check(load_library().alg_gemm_fp4(ctypes.byref(args), _stream()), "alg_gemm_fp4")
+    if q_out_scales is None:
+        _check(load_library().alg_gemm_fp4(ctypes.byref(args), _stream()), "alg_gemm_fp4")
+        return
+    args.C = C.data_ptr() + c_off // 2
+    _check(load_library().alg_gemm_fp4_q4out(ctypes.byref(args), _p(q_out_scales, q_out_scales_off), strideOutScales, _stream()),
+           "alg_gemm_fp4_q4out")
 
 
 ATTN_Q_PRESCALED = 1
@@ -1342,6 +1370,29 @@ def layernorm_modulate_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstr
                                                      _p(scale, scale_off), _p(shift, shift_off), mod_bstride, batch, rows, D,
                                                      x_bstride, seg_split, float(eps), _stream()), "alg_layernorm_modulate_fp8")
     return q8, q8_scale
+
+
+def layernorm_modulate_mxfp4(x, q4, q4_scales, weight, bias, scale, shift, mod_bstride, batch, rows, D, seg_split, eps,
+                             x_bstride=None, x_off=0, scale_off=0, shift_off=0, q4_off=0, q4_scale_off=0):
+    """layernorm_modulate followed by quantize_mxfp4_rows, in one pass (bit-identical bytes and scales): q4 [batch * rows, D/2]
+    packed e2m1 bytes and q4_scales [batch * rows, D/32] E8M0 bytes (both uint8) are filled in place; x_off / scale_off /
+    shift_off are element offsets as in layernorm_modulate, q4_off / q4_scale_off byte offsets into the two outputs."""
+    _dev(x, "x")
+    if x.dtype != torch.bfloat16:
+        raise AlgHipError("layernorm_modulate_mxfp4 takes bf16 rows, got %s" % x.dtype)
+    _bytes_dev(q4, "q4"), _bytes_dev(q4_scales, "q4_scales")
+    if D <= 0 or D % 512 or D > 8192 or batch <= 0 or rows <= 0:
+        raise AlgHipError("layernorm_modulate_mxfp4: D = %d must be a multiple of 512 and <= 8192 (batch = %d, rows = %d)"
+                          % (D, batch, rows))
+    x_bstride = rows * D if x_bstride is None else x_bstride
+    if x_off + (batch - 1) * x_bstride + rows * D > x.numel() or q4_off + batch * rows * (D // 2) > q4.numel() or \
+            q4_scale_off + batch * rows * (D // 32) > q4_scales.numel():
+        raise AlgHipError("layernorm_modulate_mxfp4: %d x %d rows of D = %d do not fit the tensors" % (batch, rows, D))
+    _check(load_library().alg_layernorm_modulate_mxfp4(_p(x, x_off), _p(q4, q4_off), _p(q4_scales, q4_scale_off), _p(weight),
+                                                       _p(bias), _p(scale, scale_off), _p(shift, shift_off), mod_bstride, batch,
+                                                       rows, D, x_bstride, seg_split, float(eps), _stream()),
+           "alg_layernorm_modulate_mxfp4")
+    return q4, q4_scales
 
 
 def layernorm_modulate_seg_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstride, seg_stride, batch, rows, D, seg_split,

@@ -4,7 +4,11 @@
 // k-tiles of 256 elements = 128 bytes per row (schedule 6's staging width: a lane's 16-byte fragment is 32 e2m1 values = one
 // MX block = one operand of the K = 64 instruction).  Correctness first: one LDS buffer, the next k-tile waits in registers
 // while the current one is multiplied; tuning is left for later.
+//
+// alg_gemm_fp4_q4out is the same kernel with an MXFP4 output (Q4): the epilogue's bf16 values are quantised where they are, as
+// alg_quantize_mxfp4_rows would quantise the bf16 tensor, and only the e2m1 bytes + the E8M0 scales are stored.
 #include "common.h"
+#include "row_ops.h"
 
 namespace alg {
 namespace {
@@ -24,8 +28,10 @@ __device__ __forceinline__ void unpack_bf4(const uint2 v, float (&f)[4]) {
 // Operand lane map of the instruction with FP4 data (checked with exact integer data, tests/test_gpu_mxfp4.py): lane l holds
 // row l & 31, k = 32 (l >> 5) + j for j = 0..31 in the first four of its eight operand registers, element 2i in the low nibble
 // of byte i; the lane's scale operand (byte 0, opsel 0) is the E8M0 scale of exactly those 32 values.
-template <int ACT, bool RES>
-__global__ __launch_bounds__(256) void gemm_fp4_kernel(const alg_gemm_args p, const int m_tiles, const int n_tiles) {
+// Q4 (alg_gemm_fp4_q4out): C is [batch][M][N / 2] e2m1 bytes, out_scales [batch][M][N / 32] E8M0 bytes
+template <int ACT, bool RES, bool Q4>
+__global__ __launch_bounds__(256) void gemm_fp4_kernel(const alg_gemm_args p, const int m_tiles, const int n_tiles,
+                                                       uint8_t* __restrict__ out_scales, const int64_t out_scales_bs) {
   __shared__ __attribute__((aligned(16))) char lds[2][FT * FKB];   // A rows, B rows: row r chunk c at r * 128 + ((c ^ (r & 7)) * 16)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave & 1, wn = wave >> 1, l31 = lane & 31, h = lane >> 5;
@@ -120,6 +126,57 @@ __global__ __launch_bounds__(256) void gemm_fp4_kernel(const alg_gemm_args p, co
 
   // ---- epilogue: the arithmetic of the bf16 / e4m3 kernel's element-exact path (gemm_kernel.h), 64-bit offsets ----
   const bf16_t* bias = (const bf16_t*)p.bias;
+  if constexpr (Q4) {
+    // MXFP4 output (N % 32 == 0, no residual).  An MX block of an output row -- the 32 columns of one (mt, nt) -- lives in the lane
+    // pair (l, l + 32): lane half h holds columns 8 g + 4 h + i.  One half exchange gives both lanes the block's amax; a second
+    // one moves the halves' bytes so that the lower lane holds bytes 0-7 of the block's sixteen and the upper lane bytes 8-15:
+    // one 8-byte store per lane and block.  Every lane runs the exchanges; only the stores are guarded.
+    uint8_t* Cq = (uint8_t*)p.C + (int64_t)b * (p.strideC >> 1);
+    uint8_t* Sq = out_scales + (int64_t)b * out_scales_bs;
+    const int64_t ldc_b = p.ldc >> 1, ldsc = p.N >> 5;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt) {
+      const int row = m0 + fa[mt];
+#pragma unroll
+      for (int nt = 0; nt < 2; ++nt) {
+        const int nb = n0 + wn * 64 + nt * 32;            // the block's first column: wave-uniform
+        const int nbc = nb < p.N ? nb : p.N - 32;         // (a block past N reads the last block's bias and stores nothing)
+        float v[4][4];
+        float amax = 0.0f;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          float bv[4] = {0.f, 0.f, 0.f, 0.f};
+          if (bias) unpack_bf4(*(const uint2*)(bias + nbc + 8 * g + 4 * h), bv);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            float x = rbf(acc[mt][nt][4 * g + i] + bv[i]);   // nn.Linear returns a bf16 tensor
+            if (ACT != ALG_ACT_NONE) x = rbf(act_apply(x, ACT));
+            v[g][i] = x;
+            amax = fmaxf(amax, fabsf(x));
+          }
+        }
+        {
+          const unsigned am = __float_as_uint(amax);
+          const auto r = __builtin_amdgcn_permlane32_swap(am, am, false, false);   // r[0] | r[1]: own, the other half's
+          amax = fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+        }
+        const int e = mxfp4_scale_byte(amax);
+        // lo: this half's two bytes of column groups 0 and 1, hi: of groups 2 and 3
+        const unsigned lo = e2m1_pack(v[0], e) | (e2m1_pack(v[1], e) << 16), hi = e2m1_pack(v[2], e) | (e2m1_pack(v[3], e) << 16);
+        // the upper lanes' lo <-> the lower lanes' hi: a lower lane then holds groups 0, 1 of both halves, an upper lane groups 2, 3
+        const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
+        const unsigned h0 = r[0], h1 = r[1];   // the lane's two groups as half 0 and as half 1 hold them
+        uint2 o;
+        o.x = (h0 & 0xffffu) | (h1 << 16);
+        o.y = (h0 >> 16) | (h1 & 0xffff0000u);
+        if (row < p.M && nb < p.N) {
+          *(uint2*)(Cq + row * ldc_b + (nb >> 1) + 8 * h) = o;
+          if (h == 0) Sq[row * ldsc + (nb >> 5)] = (uint8_t)e;
+        }
+      }
+    }
+    return;
+  }
   const bf16_t* R = RES ? (const bf16_t*)p.R + (int64_t)b * p.strideR : nullptr;
   const bf16_t* gate = (RES && p.gate) ? (const bf16_t*)p.gate + (int64_t)b * p.strideGate : nullptr;
   const int64_t gate_seg = (p.flags & ALG_GEMM_GATE_SEG_STRIDE) ? p.gate_seg_stride : p.N;
@@ -182,37 +239,7 @@ __global__ __launch_bounds__(256) void gemm_fp4_kernel(const alg_gemm_args p, co
   }
 }
 
-// Eight bf16 values (one 16-byte load) of an MX block: four lanes share a block.
-__device__ __forceinline__ void mxfp4_quantize8(const uint4 v, uint8_t* __restrict__ q4, uint8_t* __restrict__ scale, int lane) {
-  const uint32_t u[4] = {v.x, v.y, v.z, v.w};
-  float f[8];
-  float amax = 0.0f;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = __uint_as_float(u[k] << 16);
-    f[2 * k + 1] = __uint_as_float(u[k] & 0xffff0000u);
-    amax = fmaxf(amax, fmaxf(fabsf(f[2 * k]), fabsf(f[2 * k + 1])));
-  }
-  amax = fmaxf(amax, __shfl_xor(amax, 1, 64));
-  amax = fmaxf(amax, __shfl_xor(amax, 2, 64));
-  // E8M0 byte: floor(log2(amax)) - 2 clamped to [-127, 127], + 127.  floor(log2) of a normal number is its exponent field - 127;
-  // a subnormal amax (field 0) lies below 2^-126 and clamps to byte 0 like field 1 and 2 do.  A zero block writes 127.
-  const int ef = (int)(__float_as_uint(amax) >> 23);
-  const int e = amax > 0.0f ? (ef > 2 ? ef - 2 : 0) : 127;
-  const float inv = __uint_as_float((uint32_t)(254 - e) << 23);   // 2^(127 - e): e <= 252, so a normal number
-  uint32_t out = 0;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const float a = fabsf(f[k]) * inv;   // exact (a power of two), or underflows far below the first tie point
-    // nearest of {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even code, saturating: one compare per boundary
-    const uint32_t code = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
-                          (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
-    out |= (code | ((__float_as_uint(f[k]) >> 28) & 8u)) << (4 * k);
-  }
-  *(uint32_t*)q4 = out;
-  if ((lane & 3) == 0) *scale = (uint8_t)e;
-}
-
+// (the block quantiser, mxfp4_quantize8: row_ops.h -- eight bf16 values per lane, four lanes share an MX block)
 __global__ __launch_bounds__(256) void quantize_mxfp4_rows_kernel(const bf16_t* __restrict__ x, int64_t x_rs, uint8_t* __restrict__ q,
                                                                   uint8_t* __restrict__ scales, int64_t rows, int K) {
   const int lane = threadIdx.x & 63;
@@ -227,71 +254,136 @@ __global__ __launch_bounds__(256) void quantize_mxfp4_rows_kernel(const bf16_t* 
 
 template <int ACT, bool RES>
 int launch_fp4(const alg_gemm_args* a, int m_tiles, int n_tiles, unsigned nwg, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_fp4_kernel<ACT, RES>), dim3(nwg), dim3(256), 0, s, *a, m_tiles, n_tiles);
+  hipLaunchKernelGGL((gemm_fp4_kernel<ACT, RES, false>), dim3(nwg), dim3(256), 0, s, *a, m_tiles, n_tiles, (uint8_t*)nullptr,
+                     (int64_t)0);
   return check_launch("alg_gemm_fp4");
+}
+template <int ACT>
+int launch_fp4_q4out(const alg_gemm_args* a, int m_tiles, int n_tiles, unsigned nwg, uint8_t* out_scales, int64_t out_scales_bs,
+                     hipStream_t s) {
+  hipLaunchKernelGGL((gemm_fp4_kernel<ACT, false, true>), dim3(nwg), dim3(256), 0, s, *a, m_tiles, n_tiles, out_scales, out_scales_bs);
+  return check_launch("alg_gemm_fp4_q4out");
 }
 }  // namespace
 }  // namespace alg
 
 using namespace alg;
 
-extern "C" int alg_gemm_fp4(const alg_gemm_args* a, void* stream) {
+// The refusals both entries share, each written once; `entry` is the name the messages carry.  q4out: C holds e2m1 bytes (the
+// output-side rules are alg_gemm_fp4_q4out's own, below).
+static int gemm_fp4_check(const alg_gemm_args* a, const char* entry, bool q4out) {
   if (!a || !a->A || !a->B || !a->C || !a->a_scale || !a->b_scale) {
-    set_error("alg_gemm_fp4: null argument (A, B, C, a_scale and b_scale are required)");
+    set_error("%s: null argument (A, B, C, a_scale and b_scale are required)", entry);
     return ALG_EINVAL;
   }
   if (a->M <= 0 || a->N <= 0 || a->K <= 0 || a->batch <= 0 || a->K % 256) {
-    set_error("alg_gemm_fp4: bad shape M=%d N=%d K=%d batch=%d (K %% 256 == 0)", a->M, a->N, a->K, a->batch);
+    set_error("%s: bad shape M=%d N=%d K=%d batch=%d (K %% 256 == 0)", entry, a->M, a->N, a->K, a->batch);
     return ALG_EINVAL;
   }
   if (a->flags & (ALG_GEMM_B_PACKED11 | ALG_GEMM_BIAS_PER_ROW | ALG_GEMM_PERMUTE_COLS)) {
-    set_error("alg_gemm_fp4: ALG_GEMM_B_PACKED11, ALG_GEMM_BIAS_PER_ROW and ALG_GEMM_PERMUTE_COLS are not built for MXFP4 operands (flags=%d)",
-              a->flags);
+    set_error("%s: ALG_GEMM_B_PACKED11, ALG_GEMM_BIAS_PER_ROW and ALG_GEMM_PERMUTE_COLS are not built for MXFP4 operands (flags=%d)",
+              entry, a->flags);
     return ALG_EINVAL;
   }
   if (a->conv_wp || a->conv_cin_log2 || a->conv_hpwp || a->conv_kw) {
-    set_error("alg_gemm_fp4: convolution addressing is not built for MXFP4 operands");
+    set_error("%s: convolution addressing is not built for MXFP4 operands", entry);
     return ALG_EINVAL;
   }
   if (a->lda % 32 || a->ldb % 32 || a->strideA % 32 || a->strideB % 32 || a->lda < a->K || a->ldb < a->K || a->strideA < 0 ||
       a->strideB < 0 || ((uintptr_t)a->A & 15) || ((uintptr_t)a->B & 15)) {
-    set_error("alg_gemm_fp4: A/B must be 16-byte aligned with lda/ldb >= K and lda/ldb/strides multiples of 32 elements (16 bytes)");
+    set_error("%s: A/B must be 16-byte aligned with lda/ldb >= K and lda/ldb/strides multiples of 32 elements (16 bytes)", entry);
     return ALG_EINVAL;
   }
   if (((uintptr_t)a->a_scale & 7) || ((uintptr_t)a->b_scale & 7) || (a->strideAScale & 7) || (a->strideBScale & 7) ||
       a->strideAScale < 0 || a->strideBScale < 0) {
-    set_error("alg_gemm_fp4: a_scale / b_scale (E8M0 bytes, [rows][K/32]) must be 8-byte aligned with batch strides multiples of 8 bytes");
+    set_error("%s: a_scale / b_scale (E8M0 bytes, [rows][K/32]) must be 8-byte aligned with batch strides multiples of 8 bytes", entry);
     return ALG_EINVAL;
   }
   if (a->act < ALG_ACT_NONE || a->act > ALG_ACT_SILU) {
-    set_error("alg_gemm_fp4: unknown activation %d", a->act);
+    set_error("%s: unknown activation %d", entry, a->act);
     return ALG_EINVAL;
   }
   if ((a->R && a->act != ALG_ACT_NONE) || (a->gate && !a->R)) {
-    set_error("alg_gemm_fp4: an activation cannot be combined with the residual epilogue, and a gate needs a residual");
+    set_error("%s: an activation cannot be combined with the residual epilogue, and a gate needs a residual", entry);
     return ALG_EINVAL;
   }
-  if ((a->N & 3) == 0) {   // 8-byte epilogue accesses
+  if (!q4out && (a->N & 3) == 0) {   // 8-byte epilogue accesses
     const bool bad = (a->ldc & 3) || (a->strideC & 3) || ((uintptr_t)a->C & 7) || (a->bias && ((uintptr_t)a->bias & 7)) ||
                      (a->R && ((a->ldr & 3) || (a->strideR & 3) || ((uintptr_t)a->R & 7))) ||
                      (a->gate && ((a->strideGate & 3) || ((a->flags & ALG_GEMM_GATE_SEG_STRIDE) && (a->gate_seg_stride & 3)) ||
                                   ((uintptr_t)a->gate & ((a->flags & ALG_GEMM_GATE_F32) ? 15 : 7))));
     if (bad) {
-      set_error("alg_gemm_fp4: C/bias/R/gate must be 8-byte aligned with ldc/ldr/strides multiples of 4 elements");
+      set_error("%s: C/bias/R/gate must be 8-byte aligned with ldc/ldr/strides multiples of 4 elements", entry);
       return ALG_EINVAL;
     }
   }
-  const int m_tiles = (a->M + FT - 1) / FT, n_tiles = (a->N + FT - 1) / FT;
-  const int64_t nwg = (int64_t)m_tiles * n_tiles * a->batch;
+  const int64_t nwg = (int64_t)((a->M + FT - 1) / FT) * ((a->N + FT - 1) / FT) * a->batch;
   if (nwg > 0x7fffffff) {
-    set_error("alg_gemm_fp4: grid too large");
+    set_error("%s: grid too large", entry);
     return ALG_ELIMIT;
   }
+  return ALG_OK;
+}
+
+extern "C" int alg_gemm_fp4(const alg_gemm_args* a, void* stream) {
+  if (const int rc = gemm_fp4_check(a, "alg_gemm_fp4", false)) return rc;
+  const int m_tiles = (a->M + FT - 1) / FT, n_tiles = (a->N + FT - 1) / FT;
+  const unsigned nwg = (unsigned)((int64_t)m_tiles * n_tiles * a->batch);
   hipStream_t s = (hipStream_t)stream;
-  if (a->R) return launch_fp4<ALG_ACT_NONE, true>(a, m_tiles, n_tiles, (unsigned)nwg, s);
-  if (a->act == ALG_ACT_GELU_TANH) return launch_fp4<ALG_ACT_GELU_TANH, false>(a, m_tiles, n_tiles, (unsigned)nwg, s);
-  if (a->act == ALG_ACT_SILU) return launch_fp4<ALG_ACT_SILU, false>(a, m_tiles, n_tiles, (unsigned)nwg, s);
-  return launch_fp4<ALG_ACT_NONE, false>(a, m_tiles, n_tiles, (unsigned)nwg, s);
+  if (a->R) return launch_fp4<ALG_ACT_NONE, true>(a, m_tiles, n_tiles, nwg, s);
+  if (a->act == ALG_ACT_GELU_TANH) return launch_fp4<ALG_ACT_GELU_TANH, false>(a, m_tiles, n_tiles, nwg, s);
+  if (a->act == ALG_ACT_SILU) return launch_fp4<ALG_ACT_SILU, false>(a, m_tiles, n_tiles, nwg, s);
+  return launch_fp4<ALG_ACT_NONE, false>(a, m_tiles, n_tiles, nwg, s);
+}
+
+// [p, p + the bytes batch items of `rows` rows at these strides span), for the overlap refusals
+static bool fp4_spans_overlap(const void* p, int64_t bstride, int64_t rstride, int64_t row_bytes, const void* q, int64_t q_bstride,
+                              int64_t q_rstride, int64_t q_row_bytes, int batch, int rows) {
+  const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+  const uintptr_t p1 = p0 + (uintptr_t)((batch - 1) * bstride + (rows - 1) * rstride + row_bytes);
+  const uintptr_t q1 = q0 + (uintptr_t)((batch - 1) * q_bstride + (rows - 1) * q_rstride + q_row_bytes);
+  return p0 < q1 && q0 < p1;
+}
+
+extern "C" int alg_gemm_fp4_q4out(const alg_gemm_args* a, void* out_scales, int64_t out_scales_bstride, void* stream) {
+  static const char* const entry = "alg_gemm_fp4_q4out";
+  if (const int rc = gemm_fp4_check(a, entry, true)) return rc;
+  if (a->N % 32) {
+    set_error("%s: N=%d must be a multiple of 32 (whole MX blocks along the output row)", entry, a->N);
+    return ALG_EINVAL;
+  }
+  if (a->R || a->gate) {
+    set_error("%s: the residual epilogue (R, gate) has no MXFP4 output", entry);
+    return ALG_EINVAL;
+  }
+  if (a->act != ALG_ACT_NONE && a->act != ALG_ACT_GELU_TANH) {
+    set_error("%s: activation %d is not built for the MXFP4 output (ALG_ACT_NONE, ALG_ACT_GELU_TANH)", entry, a->act);
+    return ALG_EINVAL;
+  }
+  if (a->ldc % 32 || a->strideC % 32 || a->ldc < a->N || a->strideC < 0 || ((uintptr_t)a->C & 15) ||
+      (a->bias && ((uintptr_t)a->bias & 7))) {
+    set_error("%s: C (e2m1 bytes) must be 16-byte aligned with ldc >= N and ldc / strideC multiples of 32 elements; bias 8-byte aligned",
+              entry);
+    return ALG_EINVAL;
+  }
+  if (!out_scales || ((uintptr_t)out_scales & 7) || (out_scales_bstride & 7) || out_scales_bstride < 0) {
+    set_error("%s: out_scales (E8M0 bytes, [batch][M][N/32]) must be given, 8-byte aligned, its batch stride a multiple of 8 bytes",
+              entry);
+    return ALG_EINVAL;
+  }
+  // workgroups read A and its scales while others store C and out_scales
+  if (fp4_spans_overlap(a->A, a->strideA >> 1, a->lda >> 1, a->K >> 1, a->C, a->strideC >> 1, a->ldc >> 1, a->N >> 1, a->batch, a->M) ||
+      fp4_spans_overlap(a->a_scale, a->strideAScale, a->K >> 5, a->K >> 5, out_scales, out_scales_bstride, a->N >> 5, a->N >> 5,
+                        a->batch, a->M)) {
+    set_error("%s: C overlaps A (or out_scales overlaps a_scale): the output needs buffers of its own", entry);
+    return ALG_EINVAL;
+  }
+  const int m_tiles = (a->M + FT - 1) / FT, n_tiles = (a->N + FT - 1) / FT;
+  const unsigned nwg = (unsigned)((int64_t)m_tiles * n_tiles * a->batch);
+  hipStream_t s = (hipStream_t)stream;
+  if (a->act == ALG_ACT_GELU_TANH)
+    return launch_fp4_q4out<ALG_ACT_GELU_TANH>(a, m_tiles, n_tiles, nwg, (uint8_t*)out_scales, out_scales_bstride, s);
+  return launch_fp4_q4out<ALG_ACT_NONE>(a, m_tiles, n_tiles, nwg, (uint8_t*)out_scales, out_scales_bstride, s);
 }
 
 extern "C" int alg_quantize_mxfp4_rows(const void* x, int64_t x_rstride, void* q, void* scales, int64_t rows, int K, void* stream) {

@@ -222,6 +222,36 @@ __global__ __launch_bounds__(256) void ln_mod_fp8_kernel(const bf16_t* __restric
   quantize_row_store<ITERS>(v, lane, q8 + row * D, q8_scale + row);
 }
 
+// ---- and in front of an MXFP4 GEMM (alg_layernorm_modulate_mxfp4) ----
+// ln_mod_fp8_kernel with the other quantiser.  The row sits in v as alg_quantize_mxfp4_rows' kernel reads the bf16 tensor: lane l
+// holds columns 512 i + 8 l .. + 7, so four consecutive lanes share an MX block and mxfp4_quantize8 (row_ops.h) is that kernel's
+// call on values that never left the registers.  q4 [total_rows][D / 2], q4_scales [total_rows][D / 32]; 4 bytes per lane per store.
+template <int ITERS>
+__global__ __launch_bounds__(256) void ln_mod_mxfp4_kernel(const bf16_t* __restrict__ x, uint8_t* __restrict__ q4,
+                                                           uint8_t* __restrict__ q4_scales, const bf16_t* __restrict__ w,
+                                                           const bf16_t* __restrict__ bs, const bf16_t* __restrict__ scale,
+                                                           const bf16_t* __restrict__ shift, int64_t mod_bs, int64_t x_bs,
+                                                           int64_t total_rows, int rows, int seg_split, int64_t seg_stride,
+                                                           float eps) {
+  constexpr int D = ITERS * 512;
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= total_rows) return;
+  const int bidx = (int)(row / rows);
+  const int r = (int)(row - (int64_t)bidx * rows);
+  const int seg = r >= seg_split ? 1 : 0;
+  const bf16_t* xr = x + (int64_t)bidx * x_bs + (int64_t)r * D;
+  float v[ITERS][8];
+  ln_mod_row<ITERS>(xr, w, bs, scale, shift, mod_bs, seg_stride, bidx, seg, lane, eps, v);
+  uint8_t* qr = q4 + row * (D / 2);
+  uint8_t* sr = q4_scales + row * (D / 32);
+#pragma unroll
+  for (int i = 0; i < ITERS; ++i) {
+    const int c = i * 512 + lane * 8;
+    mxfp4_quantize8(v[i], qr + (c >> 1), sr + (c >> 5), lane);
+  }
+}
+
 // In place per-head LayerNorm(64) + RoPE on qk [batch][S][2][heads][64]; 8 lanes per head vector.
 __global__ __launch_bounds__(256) void qk_norm_rope_kernel(bf16_t* __restrict__ qk, const bf16_t* __restrict__ wq,
                                                            const bf16_t* __restrict__ bq,
@@ -336,10 +366,13 @@ __global__ __launch_bounds__(256) void qk_norm_rope_token_kernel(bf16_t* __restr
 
 using namespace alg;
 
-// ---- LayerNorm + modulation with bf16 parameters: alg_layernorm_modulate, _seg (y) and _fp8, _seg_fp8 (q8 + q8_scale).
-// One operand struct; check, plan, launch (rownorm_host.h) ----
+// ---- LayerNorm + modulation with bf16 parameters: alg_layernorm_modulate, _seg (y), _fp8, _seg_fp8 (q8 + q8_scale) and _mxfp4
+// (q4 + q4_scales).  One operand struct; check, plan, launch (rownorm_host.h) ----
 struct LnModArgs {
   bool fp8;                  // the e4m3 twins: q8 + q8_scale instead of y
+  bool mxfp4;                // the MXFP4 twin: q4 + q4_scales instead of y
+  void* q4;
+  uint8_t* q4_scales;
   const void* x;
   void* y;
   void* q8;
@@ -362,7 +395,7 @@ static bool misaligned16(const void* p) { return ((uintptr_t)p & 15) != 0; }
 
 // `entry` is the name the messages carry: the _seg forms report as the entries they extend
 static int ln_mod_check(const LnModArgs& a, const char* entry) {
-  if (!a.x || (a.fp8 ? !a.q8 || !a.q8_scale : !a.y) || a.batch <= 0 || a.rows <= 0 || a.D <= 0 || a.seg_stride % 8) {
+  if (!a.x || (a.mxfp4 ? !a.q4 || !a.q4_scales : a.fp8 ? !a.q8 || !a.q8_scale : !a.y) || a.batch <= 0 || a.rows <= 0 || a.D <= 0 || a.seg_stride % 8) {
     set_error("%s: bad argument (batch=%d rows=%d D=%d)", entry, a.batch, a.rows, a.D);
     return ALG_EINVAL;
   }
@@ -376,15 +409,18 @@ static int ln_mod_check(const LnModArgs& a, const char* entry) {
   }
   const bool params_off = misaligned16(a.x) || misaligned16(a.weight) || misaligned16(a.bias) || misaligned16(a.scale) ||
                           misaligned16(a.shift) || a.mod_bstride % 8 || a.x_bstride % 8;
-  if (a.fp8 ? params_off || ((uintptr_t)a.q8 & 7) || ((uintptr_t)a.q8_scale & 3) : params_off || misaligned16(a.y) || a.y_bstride % 8) {
-    if (a.fp8) set_error("%s: x and the parameter rows must be 16-byte aligned, q8 8-byte aligned", entry);
+  if (a.mxfp4 ? params_off || ((uintptr_t)a.q4 & 3)
+      : a.fp8 ? params_off || ((uintptr_t)a.q8 & 7) || ((uintptr_t)a.q8_scale & 3)
+              : params_off || misaligned16(a.y) || a.y_bstride % 8) {
+    if (a.mxfp4) set_error("%s: x and the parameter rows must be 16-byte aligned, q4 4-byte aligned", entry);
+    else if (a.fp8) set_error("%s: x and the parameter rows must be 16-byte aligned, q8 8-byte aligned", entry);
     else set_error("%s: pointers must be 16-byte aligned", entry);
     return ALG_EINVAL;
   }
   const int64_t total = (int64_t)a.batch * a.rows;
   if (!row_blocks_fit((total + 3) / 4)) {
     const int rc = row_elimit(entry, "batch * rows", total);
-    return a.fp8 ? ALG_EINVAL : rc;   // the e4m3 entries have always refused this, with this code
+    return a.fp8 || a.mxfp4 ? ALG_EINVAL : rc;   // the e4m3 entries have always refused this, with this code; their MXFP4 twin follows
   }
   return ALG_OK;
 }
@@ -392,10 +428,10 @@ static int ln_mod_check(const LnModArgs& a, const char* entry) {
 // Which kernel, how many rows per wave, which grid.  MANY_ROWS -- many rows with all four parameter rows present (every AdaLN of
 // the CogVideoX / HunyuanVideo blocks), up to D = 3072, bf16 output: rpw so that the call is one resident round of waves
 // (CUs x 4 SIMDs x 2 waves of that kernel: 2048 on an MI355X), at least 8.  The e4m3 twins always take one row per wave
-// (ln_mod_fp8_kernel's comment has the measurement).
+// (ln_mod_fp8_kernel's comment has the measurement), and so does the MXFP4 twin, built on the same kernel.
 static RowPlan ln_mod_plan(const LnModArgs& a, int cus) {
   const int64_t total = (int64_t)a.batch * a.rows;
-  if (!a.fp8 && a.weight && a.bias && a.scale && a.D <= 3072 && total >= 4096) {
+  if (!a.fp8 && !a.mxfp4 && a.weight && a.bias && a.scale && a.D <= 3072 && total >= 4096) {
     const int64_t resident_waves = (int64_t)cus * 8;
     const int rpw = (int)std::max<int64_t>(8, (total + resident_waves - 1) / resident_waves);
     return {RowRoute::MANY_ROWS, rpw, (unsigned)((total + 4 * (int64_t)rpw - 1) / (4 * (int64_t)rpw))};
@@ -416,14 +452,19 @@ static int ln_mod_entry(const LnModArgs& a, const char* entry) {
       hipLaunchKernelGGL((ln_mod_rows_kernel<it.value>), grid, blk, 0, a.stream, x, (bf16_t*)a.y, w, bs, sc, sh, a.mod_bstride,
                          a.x_bstride, a.y_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps, pl.rpw);
     });
-  } else if (!a.fp8) {
+  } else if (!a.fp8 && !a.mxfp4) {
     dispatch_iters(a.D / 512, LnIters{}, [&](auto it) {
       hipLaunchKernelGGL(ln_mod_kernel<it.value>, grid, blk, 0, a.stream, x, (bf16_t*)a.y, w, bs, sc, sh, a.mod_bstride, a.x_bstride,
                          a.y_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps);
     });
-  } else {
+  } else if (a.fp8) {
     dispatch_iters(a.D / 512, LnIters{}, [&](auto it) {
       hipLaunchKernelGGL(ln_mod_fp8_kernel<it.value>, grid, blk, 0, a.stream, x, (uint8_t*)a.q8, a.q8_scale, w, bs, sc, sh,
+                         a.mod_bstride, a.x_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps);
+    });
+  } else {
+    dispatch_iters(a.D / 512, LnIters{}, [&](auto it) {
+      hipLaunchKernelGGL(ln_mod_mxfp4_kernel<it.value>, grid, blk, 0, a.stream, x, (uint8_t*)a.q4, a.q4_scales, w, bs, sc, sh,
                          a.mod_bstride, a.x_bstride, total, a.rows, a.seg_split, a.seg_stride, a.eps);
     });
   }
@@ -465,6 +506,16 @@ extern "C" int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_sca
                                           int D, int64_t x_bstride, int seg_split, float eps, void* stream) {
   return alg_layernorm_modulate_seg_fp8(x, q8, q8_scale, weight, bias, scale, shift, mod_bstride, D, batch, rows, D, x_bstride,
                                         seg_split, eps, stream);
+}
+
+extern "C" int alg_layernorm_modulate_mxfp4(const void* x, void* q4, void* q4_scales, const void* weight, const void* bias,
+                                            const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows,
+                                            int D, int64_t x_bstride, int seg_split, float eps, void* stream) {
+  LnModArgs a = {};
+  a.mxfp4 = true; a.x = x; a.q4 = q4; a.q4_scales = (uint8_t*)q4_scales; a.weight = weight; a.bias = bias; a.scale = scale;
+  a.shift = shift; a.mod_bstride = mod_bstride; a.seg_stride = D; a.batch = batch; a.rows = rows; a.D = D;
+  a.x_bstride = x_bstride; a.seg_split = seg_split; a.eps = eps; a.stream = (hipStream_t)stream;
+  return ln_mod_entry(a, "alg_layernorm_modulate_mxfp4");
 }
 
 extern "C" int alg_qk_norm_rope_scaled(void* qk, const void* wq, const void* bq, const void* wk, const void* bk,

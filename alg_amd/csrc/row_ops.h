@@ -1,7 +1,8 @@
 // Lane primitives of the memory-bound row kernels (norm.hip, wan.hip, hunyuan.hip, llama.hip, wan_vae.hip, vae.hip,
 // step_cache.hip, t5.hip; through qk_norm_rope.h the GEMM store loop) and the e4m3 row quantiser (gemm_p6_fp8.hip,
-// attention128_fp8.hip and every kernel that quantises a row it has just produced), each defined ONCE.  A lane holds eight
-// consecutive elements of its row: one 16-byte bf16 access, two for fp32, 8 bytes of e4m3.
+// attention128_fp8.hip and every kernel that quantises a row it has just produced), each defined ONCE; behind it the OCP MXFP4
+// block quantiser (gemm_fp4.hip: the row quantiser and the MXFP4 epilogue; norm.hip).  A lane holds eight consecutive elements
+// of its row: one 16-byte bf16 access, two for fp32, 8 bytes of e4m3, 4 of e2m1.
 #pragma once
 #include "common.h"
 
@@ -120,6 +121,51 @@ __device__ __forceinline__ void e4m3_row_store(const float (&v)[ITERS][8], float
   if (lane == 0) *scale_out = qs;
 #pragma unroll
   for (int i = 0; i < ITERS; ++i) *(uint2*)(qr + i * 512 + lane * 8) = e4m3x8(v[i], inv);
+}
+
+// ---- the OCP MXFP4 block quantiser (e2m1 elements, one E8M0 scale byte per 32 consecutive elements): what alg_quantize_mxfp4_rows
+// writes for a bf16 row, and therefore what every kernel that quantises values still in its registers writes (norm.hip's
+// ln_mod_mxfp4_kernel, gemm_fp4.hip's MXFP4 epilogue).  The callers differ only in which lanes share a block, i.e. in how the
+// block's amax is gathered; the scale byte, the compare chain and the nibble order are here ----
+// E8M0 byte: floor(log2(amax)) - 2 clamped to [-127, 127], + 127.  floor(log2) of a normal number is its exponent field - 127;
+// a subnormal amax (field 0) lies below 2^-126 and clamps to byte 0 like field 1 and 2 do.  A zero block writes 127.
+__device__ __forceinline__ int mxfp4_scale_byte(float amax) {
+  const int ef = (int)(__float_as_uint(amax) >> 23);
+  return amax > 0.0f ? (ef > 2 ? ef - 2 : 0) : 127;
+}
+__device__ __forceinline__ float mxfp4_inv(int e) {   // 2^(127 - e): e <= 252, so a normal number
+  return __uint_as_float((uint32_t)(254 - e) << 23);
+}
+// one element: the sign bit of f (kept on zeros) over the nearest of {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even code,
+// saturating: one compare per boundary
+__device__ __forceinline__ uint32_t e2m1_code(float f, float inv) {
+  const float a = fabsf(f) * inv;   // exact (a power of two), or underflows far below the first tie point
+  const uint32_t code = (uint32_t)(a > 0.25f) + (uint32_t)(a >= 0.75f) + (uint32_t)(a > 1.25f) + (uint32_t)(a >= 1.75f) +
+                        (uint32_t)(a > 2.5f) + (uint32_t)(a >= 3.5f) + (uint32_t)(a > 5.0f);
+  return code | ((__float_as_uint(f) >> 28) & 8u);
+}
+// N consecutive elements (values a bf16 tensor would hold) of a block whose scale byte is e: element k in nibble k
+template <int N>
+__device__ __forceinline__ uint32_t e2m1_pack(const float (&f)[N], int e) {
+  static_assert(N <= 8, "one 32-bit word holds eight e2m1 values");
+  const float inv = mxfp4_inv(e);
+  uint32_t out = 0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) out |= e2m1_code(f[k], inv) << (4 * k);
+  return out;
+}
+
+// A lane's eight consecutive elements where lane * 8 is the column (the row kernels' mapping): four lanes share an MX block.
+// q4 points at the lane's four bytes, scale at the block's byte.
+__device__ __forceinline__ void mxfp4_quantize8(const float (&f)[8], uint8_t* __restrict__ q4, uint8_t* __restrict__ scale, int lane) {
+  const int e = mxfp4_scale_byte(xor_max<4>(amax8(f, 0.0f)));
+  *(uint32_t*)q4 = e2m1_pack(f, e);
+  if ((lane & 3) == 0) *scale = (uint8_t)e;
+}
+__device__ __forceinline__ void mxfp4_quantize8(const uint4 v, uint8_t* __restrict__ q4, uint8_t* __restrict__ scale, int lane) {   // packed bf16
+  float f[8];
+  unpack8(v, f);
+  mxfp4_quantize8(f, q4, scale, lane);
 }
 
 // grid of a grid-stride elementwise kernel of 256 threads

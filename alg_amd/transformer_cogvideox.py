@@ -26,8 +26,12 @@ fp8 mode only (allocated on the first fp8 forward of a shape):
     q8s    [N, S4] float32  its per-token scales, S4 = S rounded up to a multiple of 4 (the V^T GEMM reads them as its B scales,
                             16 bytes at a time, per batch item)
 fp4 mode only (allocated on the first fp4 forward of a shape):
-    q4     [N*S, 2D] bytes  OCP MXFP4 copy of the current feed-forward GEMM input (rows of K/2 bytes, K = D or 4D, contiguous)
+    q4     [N*S, 2D] bytes  OCP MXFP4 copy of the current feed-forward GEMM input (rows of K/2 bytes, K = D or 4D, contiguous):
+                            with fuse_quant norm2 writes it (rows of D/2 bytes) and ff1 reads it
     q4s    [N*S, D/8] bytes its E8M0 block scales (rows of K/32 bytes)
+    q4h    [N*S, 2D] bytes  with fuse_quant: GELU(FF1) as ff1's epilogue writes it, MXFP4 (rows of 2D bytes), ff2's input -- a
+                            second buffer, since ff1 cannot write the one it reads (h is then not written at all)
+    q4hs   [N*S, D/8] bytes its E8M0 block scales
 """
 from __future__ import annotations
 
@@ -102,7 +106,8 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
 
         ``fp4=True`` (an extension, off by default): ff.net.0.proj and ff.net.2 of every block run with OCP MXFP4 weights and
         activations (W4A4, alg_gemm_fp4: e2m1 elements, one E8M0 scale per 32 along K) -- weights quantised once per output
-        channel, the norm2 output (written bf16 first) and the GELU output per token; everything else as ``fp8`` decides.
+        channel, the norm2 output and the GELU output per token, by the kernels that compute them (``fuse_quant``, as for e4m3;
+        off: each is written bf16 first and quantised by a pass of its own); everything else as ``fp8`` decides.
         Built this way the model keeps no bf16, packed or e4m3 copy of those two weights; ``model.fp4`` may be flipped on a
         model built without it exactly like ``fp8``."""
         cfg = self.config = config
@@ -123,7 +128,8 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         if self.fp4:
             self._check_fp4_shapes()
         # fp8: the modulated LayerNorms write the e4m3 tokens + row scales themselves (alg_layernorm_modulate_fp8; bit-identical
-        # to the norm into y followed by the quantiser pass, which is what False runs)
+        # to the norm into y followed by the quantiser pass, which is what False runs).  fp4: norm2 and ff1's epilogue write the
+        # MXFP4 operands of ff1 and ff2 themselves (alg_layernorm_modulate_mxfp4, alg_gemm_fp4_q4out; the same bits again)
         self.fuse_quant = True
         _lib.load_library()
         # True (default): the softmax scale * log2(e) rides in Q's last rounding and the attention takes log2-unit scores
@@ -404,6 +410,10 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             F4 = self.config.ff_inner_mult * self.config.inner_dim
             ws["q4"] = torch.empty(N * S, F4 // 2, dtype=torch.uint8, device=self.device)
             ws["q4s"] = torch.empty(N * S, F4 // 32, dtype=torch.uint8, device=self.device)
+        if self.fuse_quant and "q4h" not in ws:
+            F4 = self.config.ff_inner_mult * self.config.inner_dim
+            ws["q4h"] = torch.empty(N * S, F4 // 2, dtype=torch.uint8, device=self.device)
+            ws["q4hs"] = torch.empty(N * S, F4 // 32, dtype=torch.uint8, device=self.device)
         if self.layers and "wf14" not in self.layers[0]:
             if "wf1" not in self.layers[0]:
                 raise _lib.AlgHipError("this model was built with fp8=True and holds no bf16 copy of its feed-forward weights to "
@@ -414,12 +424,25 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         return ws["q4"], ws["q4s"]
 
     def _ff_fp4(self, L, ws, N, S, T, m2):
-        """The feed-forward half of a block with MXFP4 operands: norm2 into y (bf16), y and then the GELU output quantised per
-        token into q4 / q4s in front of the two alg_gemm_fp4 launches.  No fused norm + quantiser yet."""
+        """The feed-forward half of a block with MXFP4 operands.  fuse_quant (three launches): norm2 writes q4 / q4s itself, ff1's
+        epilogue writes GELU(FF1) as q4h / q4hs, ff2 reads those -- no bf16 y or h goes through memory.  Otherwise (five
+        launches, the same bits): norm2 into y (bf16), y and then the GELU output quantised per token into q4 / q4s in front
+        of the two alg_gemm_fp4 launches."""
         cfg, TM = self.config, self._timed
         D = cfg.inner_dim
         F4 = cfg.ff_inner_mult * D
         x, y, h, mod, q4, q4s = ws["x"], ws["y"], ws["h"], ws["mod"], ws["q4"], ws["q4s"]
+        if self.fuse_quant:
+            q4h, q4hs = ws["q4h"], ws["q4hs"]
+            TM("ln_mod", _lib.layernorm_modulate_mxfp4, x, q4, q4s, L["norm2_w"], L["norm2_b"], mod, mod, self.mod_cols, N, S, D,
+               T, cfg.norm_eps, scale_off=m2 + 2 * D, shift_off=m2)
+            TM("gemm_ff1", _lib.gemm_fp4, q4, L["wf14"][0], q4h, S, F4, D, D, D, F4, a_scale=q4s, b_scale=L["wf14"][1],
+               bias=L["bf1"], act=_lib.ACT_GELU_TANH, batch=N, strideA=S * D, strideAScale=S * (D // 32), strideC=S * F4,
+               q_out_scales=q4hs, strideOutScales=S * (F4 // 32))
+            TM("gemm_ff2", _lib.gemm_fp4, q4h, L["wf24"][0], x, S, D, F4, F4, F4, D, a_scale=q4hs, b_scale=L["wf24"][1],
+               bias=L["bf2"], R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D, strideGate=self.mod_cols, seg_split=T, batch=N,
+               strideA=S * F4, strideAScale=S * (F4 // 32), strideC=S * D, strideR=S * D)
+            return
         TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm2_w"], L["norm2_b"], mod, mod, self.mod_cols, N, S, D,
            T, cfg.norm_eps, scale_off=m2 + 2 * D, shift_off=m2)
         TM("quant4", _lib.quantize_mxfp4_rows, y, q4, q4s, N * S, D)

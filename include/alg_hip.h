@@ -291,6 +291,15 @@ int alg_gemm_fp4(const alg_gemm_args* args, void* stream);
  * before any launch. */
 int alg_quantize_mxfp4_rows(const void* x, int64_t x_rstride, void* q, void* scales, int64_t rows, int K, void* stream);
 
+/* alg_gemm_fp4 with an MXFP4 output, for a GEMM whose result is the next MXFP4 GEMM's A operand: instead of bf16, C receives
+ * [batch][M][N/2] packed e2m1 bytes (ldc / strideC count ELEMENTS, multiples of 32, ldc >= N; C 16-byte aligned) and out_scales
+ * the E8M0 bytes [batch][M][N/32] (rows contiguous, 8-byte aligned, out_scales_bstride in bytes, a multiple of 8) -- bit for
+ * bit what alg_gemm_fp4 into a bf16 C followed by alg_quantize_mxfp4_rows writes: the quantiser sees the bf16-rounded epilogue
+ * value act((A @ B^T) + bias), which never reaches memory.  N % 32 == 0; M arbitrary; ALG_ACT_NONE or ALG_ACT_GELU_TANH; no
+ * residual and no gate; C must not overlap A, nor out_scales a_scale (workgroups read A while others store).  Those and
+ * everything alg_gemm_fp4 refuses are ALG_EINVAL before any launch.  The pointer is a parameter: alg_gemm_args keeps its layout. */
+int alg_gemm_fp4_q4out(const alg_gemm_args* args, void* out_scales, int64_t out_scales_bstride, void* stream);
+
 /* The same quantiser on rows that sit inside a wider, batch-strided bf16 buffer, all batch items in ONE launch: row r of item b
  * starts at x + b * x_bstride + r * x_rstride (elements, both % 8 == 0; a column offset goes through the pointer); q is
  * [batch * rows][K] contiguous, scale [batch * rows].  Bit-identical to alg_quantize_fp8_rows on each item.  K = 3072, 12288 and
@@ -797,6 +806,13 @@ int alg_layernorm_modulate_fp8(const void* x, void* q8, float* q8_scale, const v
 int alg_layernorm_modulate_seg_fp8(const void* x, void* q8, float* q8_scale, const void* weight, const void* bias,
                                    const void* scale, const void* shift, int64_t mod_bstride, int64_t seg_stride, int batch,
                                    int rows, int D, int64_t x_bstride, int seg_split, float eps, void* stream);
+/* alg_layernorm_modulate in front of an MXFP4 GEMM: the arguments and arithmetic of alg_layernorm_modulate_fp8, but it writes
+ * q4 [batch * rows][D / 2] packed e2m1 bytes and q4_scales [batch * rows][D / 32] E8M0 bytes (both contiguous) -- bit for bit
+ * what alg_quantize_mxfp4_rows makes of the bf16 y, without the bf16 row going through memory.  x 16-byte aligned, q4 4-byte
+ * aligned.  D % 512 == 0, D <= 8192; anything else is ALG_EINVAL before any launch. */
+int alg_layernorm_modulate_mxfp4(const void* x, void* q4, void* q4_scales, const void* weight, const void* bias,
+                                 const void* scale, const void* shift, int64_t mod_bstride, int batch, int rows, int D,
+                                 int64_t x_bstride, int seg_split, float eps, void* stream);
 
 /* In place on qk: [batch][S][2][heads][64] bf16 (q then k per token):
  * per-head LayerNorm(64) with (wq,bq) / (wk,bk), then RoPE (cos/sin fp32 [S - text_len][64], interleaved-pair
