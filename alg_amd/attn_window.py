@@ -56,10 +56,13 @@ Only the policy is an approximation; its visual quality on a trained checkpoint 
 """
 import math
 import time
+from collections import namedtuple
 from types import SimpleNamespace
 
 import numpy as np
 import torch
+
+from . import _lib
 
 MAX_SEGMENTS = 12  # alg_flash_attn_d128_ranges_prefix: segments per block of a KvSegments
 Q_BLOCK = 256      # queries per workgroup of attention128_q64.hip and of attention.hip
@@ -755,6 +758,102 @@ def _prefixed_ranges(F, hw, W, sink, prefix, rows):
     return _table(per_block, Skv, Sq)
 
 
+class SelfAttnOperands(namedtuple("SelfAttnOperands", "head_dim q k vt o batch heads Sq Skv q_bs q_rs k_bs k_rs vt_bs vt_rs o_bs o_rs scale "
+                                  "q_off k_off vt_off o_off q_prescaled", defaults=(0, 0, 0, 0, False))):
+    """What every _lib.flash_attn_d{64,128}* wrapper takes for one self-attention launch group (a block's whole batch in Wan and
+    CogVideoX, one sample in HunyuanVideo): strides and offsets in elements.  The d = 64 wrappers have no Skv, no K strides and no
+    vt_off / o_off, and a d = 64 record asserts what that assumes; q_prescaled (d = 64 only) is the dense wrapper's flag -- Q
+    carries scale * log2(e), the only form the ranged entries have."""
+    __slots__ = ()
+
+    def __new__(cls, *a, **k):
+        self = super().__new__(cls, *a, **k)
+        assert self.head_dim == 128 and not self.q_prescaled or self.head_dim == 64 and (
+            self.Sq == self.Skv and (self.k_bs, self.k_rs) == (self.q_bs, self.q_rs) and self.vt_off == 0 and self.o_off == 0), self
+        return self
+
+    def args(self):
+        """(positionals, offsets): the 17 positionals of a d = 128 wrapper up to `scale`, or the 13 of a d = 64 wrapper (its dense
+        one takes `scale` behind them); the table, the order and lse= follow."""
+        if self.head_dim == 64:
+            return ((self.q, self.k, self.vt, self.o, self.batch, self.heads, self.Sq, self.q_bs, self.q_rs, self.vt_bs, self.vt_rs,
+                     self.o_bs, self.o_rs), dict(q_off=self.q_off, k_off=self.k_off))
+        return ((self.q, self.k, self.vt, self.o, self.batch, self.heads, self.Sq, self.Skv, self.q_bs, self.q_rs, self.k_bs, self.k_rs,
+                 self.vt_bs, self.vt_rs, self.o_bs, self.o_rs, self.scale),
+                dict(q_off=self.q_off, k_off=self.k_off, vt_off=self.vt_off, o_off=self.o_off))
+
+
+def launch_self_attention(timed, name, ops, table, order=None):
+    """One self-attention launch of `ops` under the profile key `name`: with `order` (a LaunchOrder) the _order entry, with a
+    KvRangesHeads the per-head entry, with a KvRanges the shared-table entry, with None the dense one.  timed(name, fn, *a, **kw)
+    makes the call (a model's _timed, or a pass-through)."""
+    a, offs = ops.args()
+    entry = "flash_attn_d%d" % ops.head_dim       # (the wrappers are looked up in _lib at call time)
+    if order is not None:
+        return timed(name, getattr(_lib, entry + "_ranges_order"), *a, table, order, **offs)
+    if isinstance(table, KvRangesHeads):
+        return timed(name, getattr(_lib, entry + "_ranges_heads"), *a, table, **offs)
+    if table is not None:
+        return timed(name, getattr(_lib, entry + "_ranges"), *a, table, **offs)
+    if ops.head_dim == 64:
+        return timed(name, _lib.flash_attn_d64, *a, ops.scale, **offs, q_prescaled=ops.q_prescaled)
+    return timed(name, _lib.flash_attn_d128, *a, **offs)
+
+
+def calibrate_self_attention(timed, name, ops, cal, layer, samples, sample0, rows, full, base):
+    """The self-attention of `ops` on the calibration forward (HeadWindowHost): the dense output into ops.o under `name`, the
+    measurement under "attn_calib".  `cal`: the buffers of _head_window_mode, laid out [layer][sample][head]; `ops` holds the
+    samples sample0 .. sample0 + ops.batch - 1 of `samples`; rows = (row0, n): the latent-query rows the recall is taken over.
+
+    cal.widths set: ONE alg_flash_attn_d128_ranges_prefix launch over `base` (the frame_profile_segments table), then
+    alg_attn_prefix_mass.  Otherwise the per-head entry with `full` (the one full range; writes lse_full), the same with `base` (the
+    window table) into the scratch cal.o [samples][Sq][heads * head_dim] for lse_part, and alg_attn_lse_recall."""
+    a, offs = ops.args()
+    heads, Sq, slot = ops.heads, ops.Sq, layer * samples + sample0
+    if cal.widths is not None:
+        p_off = sample0 * heads * cal.segments * Sq
+        timed(name, _lib.flash_attn_d128_ranges_prefix, *a, base, cal.prefix, **offs, prefix_off=p_off)
+        return timed("attn_calib", _lib.attn_prefix_mass, cal.prefix, cal.mass, ops.batch * heads, cal.segments, Sq, row0=rows[0],
+                     rows=rows[1], prefix_off=p_off, out_off=slot * heads * cal.segments)
+    entry, lse_off, row = "flash_attn_d%d_ranges_heads" % ops.head_dim, sample0 * heads * Sq, heads * ops.head_dim
+    timed(name, getattr(_lib, entry), *a, full, lse=cal.lse_full, **offs, lse_off=lse_off)
+    a, offs = SelfAttnOperands(*ops._replace(o=cal.o, o_bs=Sq * row, o_rs=row, o_off=sample0 * Sq * row)).args()
+    timed("attn_calib", getattr(_lib, entry), *a, base, lse=cal.lse_part, **offs, lse_off=lse_off)
+    return timed("attn_calib", _lib.attn_lse_recall, cal.lse_part, cal.lse_full, cal.recall, ops.batch * heads, Sq, row0=rows[0],
+                 rows=rows[1], part_off=lse_off, full_off=lse_off, out_off=slot * heads)
+
+
+class SelfAttnPlan:
+    """How one forward's self-attention launches (HeadWindowHost._self_attn_begin): per launch group g the shared frame-window
+    table shared[g] (None: the dense launch), and with attn_window_recall > 0 the mode -- None (off), "dense" (not calibrated yet),
+    "tables" or "calibrating" -- with `cal` (the calibration buffers), bases[g] (what the per-head tables are built from: shared[g],
+    or with attn_window_widths the {width: table} dict), and on the calibration forward full[g] (the one-full-range table) and
+    measure[g] (what the measuring launch runs over: shared[g], or the profile table)."""
+
+    def __init__(self, host, shared, batch):
+        self.host, self.shared, self.batch = host, list(shared), int(batch)
+        self.mode = self.cal = self.full = self.measure = None
+        self.bases = self.shared
+
+    def order(self, table):
+        """The balanced LaunchOrder of a per-head table (attn_window_balance), else None."""
+        return self.host._layer_order(table, self.batch) if isinstance(table, KvRangesHeads) else None
+
+    def layer(self, layer, g=0):
+        """(table, order) group g of layer `layer` launches with, outside the calibration forward."""
+        if self.mode is None:
+            return self.shared[g], None
+        if self.mode != "tables":      # dense until calibrated
+            return None, None
+        table = self.host._layer_table(self.bases[g], layer)
+        return table, self.order(table)
+
+    def finish(self, band_table=None):
+        """End of the forward: on the calibration forward the decisions and the per-head tables (_head_window_finish)."""
+        if self.cal is not None:
+            self.host._head_window_finish(self.cal, self.bases, batch=self.batch, band_table=band_table)
+
+
 class HeadWindowHost:
     """What a DiT with `attn_window` needs for per-head windows chosen by recall (mixed into WanTransformer3DModel,
     HunyuanVideoTransformer3DModel and CogVideoXTransformer3DModel).
@@ -804,9 +903,16 @@ class HeadWindowHost:
     CogVideoX: the recall is taken over the latent-query rows [T, S) of the joint sequence (T prompt tokens first), and its dense
     entry may plan a split-KV tail, which the ranged entry never does: the calibration forward's attention output is the dense
     entry's SINGLE-LAUNCH form bit for bit (what ALG_ATTN_SPLIT_TAIL=0 gives) and differs from a planned tail by that option's
-    documented <= 1 bf16 step, in that one forward of the video."""
+    documented <= 1 bf16 step, in that one forward of the video.
+
+    THE LAUNCHES live in this module, once for the three models.  A forward asks _self_attn_begin for its SelfAttnPlan (the shared
+    tables from _window_table, the mode, the calibration buffers, the width bases, the profile and full tables), a block describes
+    its operands as a SelfAttnOperands record (HunyuanVideo: one per sample) and hands it to launch_self_attention with the
+    (table, order) plan.layer resolves -- or, on the calibration forward, to calibrate_self_attention -- and plan.finish ends the
+    forward.  The models keep what is theirs: the e4m3 attention in front, their refusals, and Wan's band around the shared call."""
 
     def _head_window_init(self):
+        self._attn_ranges = {}           # shape + (window, sink) -> KvRanges | None; ("profile", ...) -> KvSegments (built once each)
         self.attn_window_recall = 0.0
         self.attn_window_stats = []
         self._attn_calibrate = False     # set around one forward by call_transformer(calibrate=True)
@@ -824,6 +930,66 @@ class HeadWindowHost:
     @property
     def attn_window_calibrated(self):
         return self._attn_decided is not None
+
+    def _timed(self, name, fn, *a, **k):
+        """fn(*a, **k), bracketed by a HIP event pair under `name` when the model's `profile` is a dict (bench / tests)."""
+        if self.profile is None:
+            return fn(*a, **k)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        r = fn(*a, **k)
+        e1.record()
+        self.profile.setdefault(name, []).append((e0, e1))
+        return r
+
+    def _window_sink(self, window=None):
+        window, sink = int(self.attn_window if window is None else window), int(self.attn_sink_frames)
+        if window < 0 or sink < 0:
+            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
+        return window, sink
+
+    def _window_table(self, frames, hw, extra=(), window=None, **layout):
+        """The frame_window_ranges table of a video shape -- device-resident, built once per (frames, hw, *extra, window, sink): before
+        any capture that replays it -- or None where the window is the dense attention.  window: attn_window, or one of
+        attn_window_widths; extra, layout: what else the model's token layout depends on, and frame_window_ranges' keywords for it
+        (CogVideoX prefix=T; HunyuanVideo tail=, rows=)."""
+        window, sink = self._window_sink(window)
+        key = (frames, hw) + tuple(extra) + (window, sink)
+        if key not in self._attn_ranges:
+            r = frame_window_ranges(frames, hw, window, sink_frames=sink, **layout)
+            if r is not None:
+                r.on(self.device)   # uploaded here, once
+            self._attn_ranges[key] = r
+        return self._attn_ranges[key]
+
+    def _profile_table(self, frames, hw, widths, extra=(), **layout):
+        """The frame_profile_segments table of the same shape for attn_window_widths (device-resident, built once)."""
+        _, sink = self._window_sink()
+        key = ("profile", frames, hw) + tuple(extra) + (widths, sink)
+        if key not in self._attn_ranges:
+            self._attn_ranges[key] = frame_profile_segments(frames, hw, widths, sink_frames=sink, **layout)
+            self._attn_ranges[key].on(self.device)
+        return self._attn_ranges[key]
+
+    def _self_attn_begin(self, shared, key, layers, samples, heads, rows, o_shape, batch, table_of=None, profile_of=None, band=0):
+        """The SelfAttnPlan of one forward.  shared: the attn_window table of every launch group (one; HunyuanVideo: one per sample,
+        launched with batch 1), None where the window is off or dense -- then nothing else happens.  key .. o_shape, band: what
+        _head_window_mode takes.  table_of(g, width), profile_of(g, widths): the model's cached tables of group g, asked for only
+        with attn_window_widths."""
+        plan = SelfAttnPlan(self, shared, batch)
+        if plan.shared[0] is None:
+            return plan
+        mode = self._head_window_mode(key, layers, samples, heads, rows, o_shape, band=band)
+        if mode not in (None, "dense", "tables"):
+            plan.cal, mode = mode, "calibrating"
+        plan.mode = mode
+        widths = self._head_window_widths() if mode is not None else None
+        if widths is not None:   # per group the tables of every candidate width, one profile table for the calibration
+            plan.bases = [self._head_width_bases(widths, lambda w, g=g: table_of(g, w)) for g in range(len(plan.shared))]
+        if plan.cal is not None:
+            plan.full = [self._head_full(t.Sq, t.Skv) for t in plan.shared]
+            plan.measure = plan.shared if widths is None else [profile_of(g, widths) for g in range(len(plan.shared))]
+        return plan
 
     def _head_window_widths(self):
         """attn_window_widths validated: None (off) or the tuple of candidate widths."""
@@ -1031,7 +1197,6 @@ class HeadWindowHost:
             return None
         k = (id(table), int(batch), policy)
         if k not in self._attn_orders:
-            from . import _lib
             if _lib._capturing():   # refused before anything is uploaded
                 raise _lib.AlgHipError("attn_window_balance: no launch order for batch %d and policy %r has been built yet, and "
                                        "building one uploads a table, which cannot be captured into a graph -- set the flag "
@@ -1057,7 +1222,6 @@ def call_transformer(transformer, dense, *args, forward=None, calibrate=False, *
     fn = transformer if forward is None else forward
     if (calibrate and getattr(transformer, "attn_window", 0) and getattr(transformer, "attn_window_recall", 0.0) > 0.0
             and not transformer.attn_window_calibrated):
-        from . import _lib
         if _lib._capturing():   # refused before anything is launched
             raise _lib.AlgHipError("attn window: the calibration forward (attn_window_recall > 0, heads not decided yet) cannot be "
                                    "captured into a graph -- the windowed heads are decided on the host from recalls the GPU has "

@@ -43,7 +43,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .attn_window import HeadWindowHost, KvRangesHeads, frame_window_ranges
+from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
 from .step_cache import StepCacheHost
 
 
@@ -160,7 +160,6 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         # 0: today's launches, nothing allocated
         self.attn_window = 0
         self.attn_sink_frames = 1
-        self._attn_ranges = {}    # (frames, hw, T, window, sink) -> KvRanges, or None where the window covers the whole video
         # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall reaches it keep the window
         # (attn_window.HeadWindowHost: attn_window_stats, reset_attn_window_heads).  0.0: the shared window, nothing allocated
         self._head_window_init()      # (attn_window_widths stays None: the property below refuses anything else)
@@ -327,17 +326,6 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             raise ValueError("positional embedding covers %d tokens, the sequence has %d" % (hit.shape[0], S))
         return hit
 
-    def _timed(self, name, fn, *args, **kwargs):
-        """Launch ``fn``; when profiling is on, bracket it with HIP events on the launch stream."""
-        if self.profile is None:
-            return fn(*args, **kwargs)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        out = fn(*args, **kwargs)
-        e1.record()
-        self.profile.setdefault(name, []).append((e0, e1))
-        return out
-
     # ------------------------------------------------------------------------------------------------
     @classmethod
     def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False, fp8=False, fp4=False):
@@ -453,7 +441,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
            R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D, strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * F4,
            strideAScale=S * (F4 // 32), strideC=S * D, strideR=S * D)
 
-    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr=None, cal=None, fp4=False):
+    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, plan, li, fp4=False):
         """One transformer block with e4m3 operands on its five linears: the launch order of the bf16 block, each GEMM input
         quantised per token into q8 / q8s first (by the LayerNorm itself where a norm produces it)."""
         cfg, G, TM = self.config, _lib.gemm, self._timed
@@ -493,7 +481,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
            bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
         TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
            cfg.qk_norm_eps, q_scale=q_scale)
-        self._attention(ws, kvr, N, S, scale, prescale, cal)
+        self._attention(ws, plan, li, N, S, T, scale, prescale)
         quant(att, D)
         lin("gemm_out", L["wo8"], x, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
@@ -517,52 +505,24 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
                              % (value,))
 
     def _window_ranges(self, frames, hw, T):
-        """The frame-window table of this sequence shape -- T prompt tokens, then `frames` latent frames of hw tokens -- device-
-        resident, built once per (frames, hw, T, window, sink): before any capture that replays it.  None: the window covers the
-        video, the launches are the dense ones."""
-        window, sink = int(self.attn_window), int(self.attn_sink_frames)
-        if window < 0 or sink < 0:
-            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
+        """The frame-window table of this sequence shape -- T prompt tokens, then `frames` latent frames of hw tokens
+        (HeadWindowHost._window_table: cached per (frames, hw, T, window, sink)).  None: the window covers the video, the launches
+        are the dense ones."""
         if not self.attn_prescale:
             raise ValueError("attn_window needs attn_prescale = True: alg_flash_attn_d64_ranges has one softmax form (pre-scaled Q)")
-        key = (frames, hw, T, window, sink)
-        if key not in self._attn_ranges:
-            r = frame_window_ranges(frames, hw, window, sink_frames=sink, prefix=T)
-            if r is not None:
-                r.on(self.device)
-            self._attn_ranges[key] = r
-        return self._attn_ranges[key]
+        return self._window_table(frames, hw, (T,), prefix=T)
 
-    def _attention(self, ws, kvr, N, S, scale, prescale, cal=None):
-        """softmax(q k^T * scale) v of the joint sequence from qk / vt into att: the dense launch, (kvr: the frame-window table) the
-        ranged one, or (kvr: a per-head table, attn_window_recall > 0) alg_flash_attn_d64_ranges_heads.
-
-        cal = (buffers, layer, window table, prompt tokens): the calibration forward of HeadWindowHost.  att is written by the
-        per-head entry with the one full range -- the dense entry's single-launch form, bit for bit -- which also writes lse_full; a
-        second launch with the window table writes lse_part (its output goes to a scratch buffer), and alg_attn_lse_recall reduces
-        the two over the latent-query rows [T, S) into row `layer` of the recall buffer."""
-        cfg = self.config
-        D, Hn = cfg.inner_dim, cfg.num_attention_heads
-        qk, vt, att, S_pad = ws["qk"], ws["vt"], ws["att"], ws["S_pad"]
-        if cal is not None:
-            c, layer, base, T = cal
-            A = (N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D)
-            self._timed("attn", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, att, *A, self._head_full(S, S), lse=c.lse_full, k_off=D)
-            self._timed("attn_calib", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, c.o, *A, base, lse=c.lse_part, k_off=D)
-            return self._timed("attn_calib", _lib.attn_lse_recall, c.lse_part, c.lse_full, c.recall, N * Hn, S, row0=T, rows=S - T,
-                               out_off=layer * N * Hn)
-        order = self._layer_order(kvr, N) if isinstance(kvr, KvRangesHeads) else None      # attn_window_balance
-        if order is not None:
-            return self._timed("attn", _lib.flash_attn_d64_ranges_order, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad,
-                               S_pad, S * D, D, kvr, order, k_off=D)
-        if isinstance(kvr, KvRangesHeads):
-            return self._timed("attn", _lib.flash_attn_d64_ranges_heads, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad,
-                               S_pad, S * D, D, kvr, k_off=D)
-        if kvr is not None:
-            return self._timed("attn", _lib.flash_attn_d64_ranges, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad,
-                               S * D, D, kvr, k_off=D)
-        return self._timed("attn", _lib.flash_attn_d64, qk, qk, vt, att, N, Hn, S, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D,
-                           scale, k_off=D, q_prescaled=prescale)
+    def _attention(self, ws, plan, li, N, S, T, scale, prescale):
+        """softmax(q k^T * scale) v of the joint sequence from qk / vt into att, as `plan` says for layer li: the dense launch, the
+        frame-window table's, a per-head table's -- or, on the calibration forward, the dense output (the per-head entry with the
+        one full range: the dense entry's single-launch form, bit for bit) and the window's recall over the latent-query rows
+        [T, S)."""
+        D, Hn, S_pad = self.config.inner_dim, self.config.num_attention_heads, ws["S_pad"]
+        ops = SelfAttnOperands(64, ws["qk"], ws["qk"], ws["vt"], ws["att"], N, Hn, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad,
+                               S_pad, S * D, D, scale, k_off=D, q_prescaled=prescale)
+        if plan.cal is not None:
+            return calibrate_self_attention(self._timed, "attn", ops, plan.cal, li, N, 0, (T, S - T), plan.full[0], plan.measure[0])
+        return launch_self_attention(self._timed, "attn", ops, *plan.layer(li))
 
     def _rope(self, image_rotary_emb):
         if image_rotary_emb is None:
@@ -676,23 +636,16 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         wo_k, wf1_k, wf2_k = ("pwo", "pwf1", "pwf2") if packed else ("wo", "wf1", "wf2")
         kvr = self._window_ranges(Fr // p_t, (Hh // p) * (Ww // p), T) if self.attn_window else None   # None: the dense launch
         sc = self._step_cache_begin(x, cache_keys, cache_force, T, P)   # None: off, nothing below differs from the plain forward
-        # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
-        hwm = None
-        if kvr is not None:
-            hwm = self._head_window_mode((Fr // p_t, (Hh // p) * (Ww // p), T, int(self.attn_window), int(self.attn_sink_frames)),
-                                         len(self.layers), N, Hn, S, (N, S, D))
-        calib = hwm if hwm not in (None, "dense", "tables") else None
-        kvr0, cal = kvr, None
+        # this forward's attention launches: the shared window, or per-head tables chosen by recall (attn_window.SelfAttnPlan)
+        plan = self._self_attn_begin([kvr], (Fr // p_t, (Hh // p) * (Ww // p), T, int(self.attn_window), int(self.attn_sink_frames)),
+                                     len(self.layers), N, Hn, S, (N, S, D), batch=N)
         for li, L in enumerate(self.layers):
             if li == 1 and sc is not None and TM("step_cache", sc.after_block0, x):
                 break                 # hit: x = x1 + the cached tail, straight to the head
             m1 = li * 12 * D          # norm1: shift @+0, scale @+2D, gate @+4D (each [2][D])
             m2 = m1 + 6 * D           # norm2
-            if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
-                kvr = None if hwm == "dense" or calib is not None else self._layer_table(kvr0, li)
-                cal = (calib, li, kvr0, T) if calib is not None else None
             if fp8:
-                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, kvr, cal, fp4)
+                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, plan, li, fp4)
                 continue
             TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
                T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
@@ -711,7 +664,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
                     TM("gemm_vt", G, *vt_call[0], **vt_call[1])
                 TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
                                    cfg.qk_norm_eps, q_scale=q_scale)
-            self._attention(ws, kvr, N, S, scale, prescale, cal)
+            self._attention(ws, plan, li, N, S, T, scale, prescale)
             TM("gemm_out", G, att, L[wo_k], x, S, D, D, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
               strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * D, strideC=S * D, strideR=S * D)
             if fp4:
@@ -729,8 +682,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
                 TM("step_cache", sc.after_block0, x)
             TM("step_cache", sc.end, x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
 
-        if calib is not None:
-            self._head_window_finish(calib, [kvr0])
+        plan.finish()
 
         # 4. norm_final over the joint sequence, AdaLayerNorm on the video tokens, proj_out, unpatchify
         _lib.layernorm_modulate(x, y, self.norm_final_w, self.norm_final_b, None, None, 0, N, S, D, T, cfg.norm_eps)

@@ -36,7 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import HeadWindowHost, KvRangesHeads, frame_profile_segments, frame_window_ranges
+from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
 from .transformer_wan import k_scale_bound
 
 BF = torch.bfloat16
@@ -180,7 +180,6 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
         # stay per sample (alg_flash_attn_d128_ranges).  0: today's launches, nothing allocated
         self.attn_window = 0
         self.attn_sink_frames = 1
-        self._attn_ranges = {}    # (F, hw, valid, J, window, sink) -> KvRanges, or None where the window covers the whole video
         # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall (over the latent queries,
         # minimum over the samples) reaches it keep the window (attn_window.HeadWindowHost).  0.0: the shared window, nothing allocated
         self._head_window_init()
@@ -325,17 +324,6 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
     def to(self, *a, **k):
         return self
 
-    def _timed(self, name, fn, *a, **k):
-        """the launch, bracketed by a HIP event pair under `name` when `profile` is a dict (bench / tests)"""
-        if self.profile is None:
-            return fn(*a, **k)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a, **k)
-        e1.record()
-        self.profile.setdefault(name, []).append((e0, e1))
-        return r
-
     def rope_tables(self, F_, H, W):
         key = (F_, H, W)
         hit = self._rope_cache.get(key)
@@ -409,33 +397,44 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
             for L in self.single:
                 self._quantize_block(L, self.FP8_SINGLE, drop_bf16=False)
 
-    def _profile_segments(self, frames, hw, valid, J, widths):
-        """The frame_profile_segments table of one sample of this video shape for attn_window_widths (device-resident, built once)."""
-        key = ("profile", frames, hw, valid, J, widths, int(self.attn_sink_frames))
-        if key not in self._attn_ranges:
-            S = frames * hw
-            self._attn_ranges[key] = frame_profile_segments(frames, hw, widths, sink_frames=int(self.attn_sink_frames),
-                                                            tail=(S, S + valid), rows=J)
-            self._attn_ranges[key].on(self.device)
-        return self._attn_ranges[key]
-
     def _window_ranges(self, frames, hw, valid, J, window=None):
-        """The frame-window table of one sample of this video shape (device-resident, built once per key: before any capture that
-        replays it), or None where the window is the dense attention.  Keys: frames * hw latent tokens, then `valid` prompt keys.
+        """The frame-window table of one sample of this video shape (HeadWindowHost._window_table: cached per (F, hw, valid, J,
+        window, sink)), or None where the window is the dense attention.  Keys: frames * hw latent tokens, then `valid` prompt keys.
         window: attn_window, or one of attn_window_widths."""
-        window, sink = int(self.attn_window if window is None else window), int(self.attn_sink_frames)
-        if window < 0 or sink < 0:
-            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
         if self.fp8_attention:
             raise ValueError("attn_window does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges")
-        key = (frames, hw, valid, J, window, sink)
-        if key not in self._attn_ranges:
-            S = frames * hw
-            r = frame_window_ranges(frames, hw, window, sink_frames=sink, tail=(S, S + valid), rows=J)
-            if r is not None:
-                r.on(self.device)   # uploaded here, once
-            self._attn_ranges[key] = r
-        return self._attn_ranges[key]
+        S = frames * hw
+        return self._window_table(frames, hw, (valid, J), window=window, tail=(S, S + valid), rows=J)
+
+    def _joint_attention(self, ws, plan, bi, valid, S, scale):
+        """The joint attention of block bi (its index in dual + single order) from ws.qk / ws.vt into the front of ws.am's rows:
+        one launch per sample over its S latent and valid[b] prompt keys -- the e4m3 kernel (fp8_attention), or what `plan` says."""
+        cfg, T = self.config, self._timed
+        D, heads, N, J, AM = cfg.dim, cfg.num_attention_heads, len(valid), ws.J, ws.am.shape[2]
+        f8, prof = self.fp8_attention, self.profile
+        if f8:   # V^T of the joint sequence (latent and prompt columns) per row, in the fp8 kernel's key order
+            T("vt_quant", _lib.quantize_fp8_vt, ws.vt, ws.vt8, ws.vt8s, N, D, J, D * ws.J_pad, ws.J_pad, D * ws.J_pad, ws.J_pad)
+        if prof is not None:   # one event pair around the samples' launches
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        direct = lambda name, fn, *a, **k: fn(*a, **k)
+        for b in range(N):
+            if f8:
+                _lib.flash_attn_d128_fp8(ws.a8, ws.a8s, ws.a8, ws.k8s, ws.vt8, ws.vt8s, ws.am, 1, heads, J, S + valid[b],
+                                         J * 2 * D, 2 * D, J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * AM, AM, scale,
+                                         q_off=b * J * 2 * D, qs_off=b * J * heads, k_off=b * J * 2 * D + D,
+                                         ks_off=(bi * N + b) * heads, vt_off=b * D * ws.J_pad, vts_off=b * D, o_off=b * J * AM)
+                continue
+            ops = SelfAttnOperands(128, ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D,
+                                   D * ws.J_pad, ws.J_pad, J * AM, AM, scale, q_off=b * J * 2 * D, k_off=b * J * 2 * D + D,
+                                   vt_off=b * D * ws.J_pad, o_off=b * J * AM)
+            if plan.cal is not None:   # the calibration forward: the recall over the latent queries only
+                calibrate_self_attention(direct, "attn_self", ops, plan.cal, bi, N, b, (0, S), plan.full[b], plan.measure[b])
+            else:
+                launch_self_attention(direct, "attn_self", ops, *plan.layer(bi, b))
+        if prof is not None:
+            e1.record()
+            prof.setdefault("attn_self", []).append((e0, e1))
 
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask, pooled_projections,
                  guidance=None, attention_kwargs=None, return_dict=True):
@@ -543,82 +542,13 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
         f8 = self.fp8_attention
         H8 = _lib.headnorm_rope_fp8
         kvr = [self._window_ranges(F_, first, valid[b], J) for b in range(N)] if self.attn_window else [None] * N   # None: dense
-
-        # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
-        hwm = None
-        if kvr[0] is not None:
-            hwm = self._head_window_mode((F_, first, int(self.attn_window), int(self.attn_sink_frames)),
-                                         len(self.dual) + len(self.single), N, heads, J, (N, J, D))
-        cal = hwm if hwm not in (None, "dense", "tables") else None
-        kvr0 = kvr
-        widths = self._head_window_widths() if hwm is not None else None
-        if widths is not None:   # attn_window_widths: per sample the tables of every candidate width
-            kvr0 = [self._head_width_bases(widths, lambda w_, b=b: self._window_ranges(F_, first, valid[b], J, window=w_))
-                    for b in range(N)]
-
-        def attention(bi=0):
-            """bi: index of the block in dual + single order (its K scales, fp8_attention)."""
-            prof = self.profile
-            if f8:   # V^T of the joint sequence (latent and prompt columns) per row, in the fp8 kernel's key order
-                T("vt_quant", _lib.quantize_fp8_vt, ws.vt, ws.vt8, ws.vt8s, N, D, J, D * ws.J_pad, ws.J_pad, D * ws.J_pad, ws.J_pad)
-            if prof is not None:
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-            for b in range(N):
-                if f8:
-                    _lib.flash_attn_d128_fp8(ws.a8, ws.a8s, ws.a8, ws.k8s, ws.vt8, ws.vt8s, ws.am, 1, heads, J, S + valid[b],
-                                             J * 2 * D, 2 * D, J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale,
-                                             q_off=b * J * 2 * D, qs_off=b * J * heads, k_off=b * J * 2 * D + D,
-                                             ks_off=(bi * N + b) * heads, vt_off=b * D * ws.J_pad, vts_off=b * D,
-                                             o_off=b * J * (D + M))
-                    continue
-                kv_b = kvr[b]
-                if hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
-                    kv_b = None if hwm == "dense" or cal is not None else self._layer_table(kvr0[b], bi)
-                if cal is not None and widths is not None:   # ... in one pass: all keys in rings, a prefix LSE behind every ring
-                    _lib.flash_attn_d128_ranges_prefix(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
-                                                       J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale,
-                                                       self._profile_segments(F_, first, valid[b], J, widths), cal.prefix,
-                                                       q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
-                                                       o_off=b * J * (D + M), prefix_off=b * heads * cal.segments * J)
-                    _lib.attn_prefix_mass(cal.prefix, cal.mass, heads, cal.segments, J, row0=0, rows=S,          # latent queries only
-                                          prefix_off=b * heads * cal.segments * J, out_off=(bi * N + b) * heads * cal.segments)
-                    continue
-                if cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
-                    A = (1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad)
-                    offs = dict(q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad, lse_off=b * heads * J)
-                    _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, ws.am, *A, J * (D + M), D + M, scale,
-                                                      self._head_full(J, S + valid[b]), lse=cal.lse_full, o_off=b * J * (D + M), **offs)
-                    _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, cal.o, *A, J * D, D, scale, kvr[b], lse=cal.lse_part,
-                                                      o_off=b * J * D, **offs)
-                    _lib.attn_lse_recall(cal.lse_part, cal.lse_full, cal.recall, heads, J, row0=0, rows=S,      # latent queries only
-                                         part_off=b * heads * J, full_off=b * heads * J, out_off=(bi * N + b) * heads)
-                    continue
-                order = self._layer_order(kv_b, 1) if isinstance(kv_b, KvRangesHeads) else None      # attn_window_balance
-                if order is not None:
-                    _lib.flash_attn_d128_ranges_order(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
-                                                      J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
-                                                      order, q_off=b * J * 2 * D, k_off=b * J * 2 * D + D,
-                                                      vt_off=b * D * ws.J_pad, o_off=b * J * (D + M))
-                    continue
-                if isinstance(kv_b, KvRangesHeads):
-                    _lib.flash_attn_d128_ranges_heads(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D,
-                                                      J * 2 * D, 2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
-                                                      q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
-                                                      o_off=b * J * (D + M))
-                    continue
-                if kv_b is not None:
-                    _lib.flash_attn_d128_ranges(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D,
-                                                2 * D, D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, kv_b,
-                                                q_off=b * J * 2 * D, k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad,
-                                                o_off=b * J * (D + M))
-                    continue
-                _lib.flash_attn_d128(ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D,
-                                     D * ws.J_pad, ws.J_pad, J * (D + M), D + M, scale, q_off=b * J * 2 * D,
-                                     k_off=b * J * 2 * D + D, vt_off=b * D * ws.J_pad, o_off=b * J * (D + M))
-            if prof is not None:
-                e1.record()
-                prof.setdefault("attn_self", []).append((e0, e1))
+        # this forward's joint-attention launches, one group per sample: the shared window, or per-head tables chosen by recall
+        plan = self._self_attn_begin(kvr, (F_, first, int(self.attn_window), int(self.attn_sink_frames)),
+                                     len(self.dual) + len(self.single), N, heads, J, (N, J, D), batch=1,
+                                     table_of=lambda b, w_: self._window_ranges(F_, first, valid[b], J, window=w_),
+                                     profile_of=lambda b, ws_: self._profile_table(F_, first, ws_, (valid[b], J),
+                                                                                   tail=(S, S + valid[b]), rows=J))
+        attention = lambda bi: self._joint_attention(ws, plan, bi, valid, S, scale)
 
         def ada(lin_, rows_in, out, n_out, two):
             """AdaLN linear on silu(emb): `two` -> both embeddings of every sample ([N][2][n_out]), else temb only."""
@@ -776,8 +706,7 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                   strideGate=smod_bs, gate_seg_stride=sseg, seg_split=split, batch=N, strideA=J * AM, strideC=J * D,
                   strideR=J * D)
 
-        if cal is not None:
-            self._head_window_finish(cal, kvr0, batch=1)   # (one launch per sample)
+        plan.finish()
 
         # ---- output head: AdaLayerNormContinuous (scale | shift), projection, unpatchify ----
         G(ws.semb1, w.ada_out[0], ws.mod_out, N, 2 * D, D, D, D, 2 * D, bias=w.ada_out[1])

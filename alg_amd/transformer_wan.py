@@ -31,7 +31,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
-from .attn_window import HeadWindowHost, KvRangesHeads, frame_profile_segments, frame_window_ranges, position_band_ranges
+from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention, position_band_ranges
 from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
@@ -184,7 +184,6 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         # own, as ONE alg_flash_attn_d128_ranges launch for the whole batch.  0: today's launches, nothing allocated
         self.attn_window = 0
         self.attn_sink_frames = 1
-        self._attn_ranges = {}    # (F, hw, window, sink) -> KvRanges, or None where the window covers the whole video
         # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall reaches it keep the window
         # (attn_window.HeadWindowHost: attn_window_stats, reset_attn_window_heads).  0.0: the shared window, nothing allocated
         self._head_window_init()
@@ -303,16 +302,6 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         return self
 
     # ---- helpers -----------------------------------------------------------------------------------------------------
-    def _timed(self, name, fn, *a, **k):
-        if self.profile is None:
-            return fn(*a, **k)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        r = fn(*a, **k)
-        e1.record()
-        self.profile.setdefault(name, []).append((e0, e1))
-        return r
-
     def rope_tables(self, F_, H, W):
         """WanRotaryPosEmbed as (cos, sin) fp32 [S, 64]: axis split (44, 42, 42) of the 128-wide head, float64 angles."""
         key = (F_, H, W)
@@ -386,20 +375,11 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         return ws
 
     def _window_ranges(self, frames, hw, window=None):
-        """The frame-window table of this video shape (device-resident, built once per (F, hw, window, sink): before any capture
-        that replays it), or None where the window is the dense attention.  window: attn_window, or one of attn_window_widths."""
-        window, sink = int(self.attn_window if window is None else window), int(self.attn_sink_frames)
-        if window < 0 or sink < 0:
-            raise ValueError("attn_window and attn_sink_frames must be >= 0 (got %d, %d)" % (window, sink))
+        """The frame-window table of this video shape (HeadWindowHost._window_table: cached per (F, hw, window, sink)), or None
+        where the window is the dense attention.  window: attn_window, or one of attn_window_widths."""
         if self.fp8_attention:
             raise ValueError("attn_window does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges")
-        key = (frames, hw, window, sink)
-        if key not in self._attn_ranges:
-            r = frame_window_ranges(frames, hw, window, sink_frames=sink)
-            if r is not None:
-                r.on(self.device)   # uploaded here, once
-            self._attn_ranges[key] = r
-        return self._attn_ranges[key]
+        return self._window_table(frames, hw, window=window)
 
     def _band_ranges(self, frames, hw, band):
         """The position_band_ranges table of this video shape (device-resident, built once), or None where the band is the dense
@@ -438,13 +418,38 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         else:
             T("attn_band", _lib.flash_attn_d128_ranges, *A)
 
-    def _profile_segments(self, frames, hw, widths):
-        """The frame_profile_segments table of this video shape for attn_window_widths (device-resident, built once)."""
-        key = ("profile", frames, hw, widths, int(self.attn_sink_frames))
-        if key not in self._attn_ranges:
-            self._attn_ranges[key] = frame_profile_segments(frames, hw, widths, sink_frames=int(self.attn_sink_frames))
-            self._attn_ranges[key].on(self.device)
-        return self._attn_ranges[key]
+    def _self_attention(self, T, ws, plan, li, band_t, N, F_, S, scale):
+        """Block li's self-attention from ws.qk / ws.vt into ws.att: the launch (or calibration) of `plan`, and around it, with
+        attn_band (band_t: the band table), the band heads' launch on position-major operands."""
+        D, heads, S_pad = self.config.dim, self.config.num_attention_heads, ws.S_pad
+        ops = SelfAttnOperands(128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad,
+                               S * D, D, scale, k_off=D)
+        cal = plan.cal
+        if cal is not None:   # the calibration forward: the dense output, the window's recall
+            calibrate_self_attention(T, "attn_self", ops, cal, li, N, 0, (0, S), plan.full[0], plan.measure[0])
+            if band_t is not None:   # the third candidate: every head on position-major operands, for its LSE only
+                all_heads = self._band_plan(plan.shared[0], ("band",) * heads)[1]
+                self._band_attention(T, ws, self._band_scratch(N, S, D, S_pad), all_heads, band_t, N, F_, S, S_pad, scale,
+                                     lse=cal.lse_band)
+                # (rows p F + f -> f hw + p: a torch transpose of the fp32 LSE, once per layer per video)
+                cal.lse_band_rows.view(N, heads, F_, S // F_).copy_(cal.lse_band.view(N, heads, S // F_, F_).transpose(-1, -2))
+                T("attn_calib", _lib.attn_lse_recall, cal.lse_band_rows, cal.lse_full, cal.recall_band, N * heads, S,
+                  out_off=li * N * heads)
+            return
+        band_heads = None
+        if band_t is not None and plan.mode == "tables":   # the main launch's table without the band heads
+            table, band_heads = self._layer_band_plan(plan.bases[0], li)
+            order = plan.order(table)
+        else:
+            table, order = plan.layer(li)
+        if band_heads is None or band_heads.n_sel < heads:   # (every head chose the band: no main launch)
+            launch_self_attention(T, "attn_self", ops, table, order)
+        if band_heads is not None:   # behind the main launch, which wrote zeros to these heads' slices of ws.att
+            bs = self._band_scratch(N, S, D, S_pad)
+            self._band_attention(T, ws, bs, band_heads, band_t, N, F_, S, S_pad, scale)
+            Dc = band_heads.n_sel * 128
+            T("attn_layout", _lib.attn_rows_position_major, bs.o, ws.att, band_heads, 128, N, F_, S // F_, S * Dc, Dc, S * D, D,
+              inverse=True)
 
     # ---- forward -----------------------------------------------------------------------------------------------------
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
@@ -531,23 +536,15 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         packed = None
         sc = self._step_cache_begin(ws.x, cache_keys, cache_force, 0, S)   # None: off, nothing below differs from the plain forward
         kvr = self._window_ranges(F_, S // F_) if self.attn_window else None    # None: the dense launch
-        # per-head windows chosen by recall: None (off), "dense" (not calibrated yet), "tables", or this forward calibrates (buffers)
-        hwm = None
         # attn_band validated (needs the recall policy, excludes the widths); 0: off -- also on a forward the sampler runs with the
         # window switched off (call_transformer: the dense early steps)
         band = self._head_window_band() if self.attn_window else 0
         band_t = self._band_ranges(F_, S // F_, band) if band and kvr is not None else None    # None: off, or the band is dense
-        if kvr is not None:
-            hwm = self._head_window_mode((F_, S // F_, int(self.attn_window), int(self.attn_sink_frames)), len(self.blocks), N,
-                                         heads, S, (N, S, D), band=band if band_t is not None else 0)
-        cal = hwm if hwm not in (None, "dense", "tables") else None
-        full = self._head_full(S, S) if cal is not None else None
-        if band_t is not None and cal is not None:
-            all_heads = self._band_plan(kvr, ("band",) * heads)[1]
-        kvr0 = kvr
-        widths = self._head_window_widths() if hwm is not None else None
-        if widths is not None:   # attn_window_widths: the tables of every candidate width, one profile table for the calibration
-            kvr0 = self._head_width_bases(widths, lambda w_: self._window_ranges(F_, S // F_, window=w_))
+        # this forward's self-attention launches: the shared window, or per-head tables chosen by recall (attn_window.SelfAttnPlan)
+        plan = self._self_attn_begin([kvr], (F_, S // F_, int(self.attn_window), int(self.attn_sink_frames)), len(self.blocks), N,
+                                     heads, S, (N, S, D), batch=N, band=band if band_t is not None else 0,
+                                     table_of=lambda g, w_: self._window_ranges(F_, S // F_, window=w_),
+                                     profile_of=lambda g, ws_: self._profile_table(F_, S // F_, ws_))
         for li, L in enumerate(self.blocks):
             if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
                 break                 # hit: x = x1 + the cached tail, straight to the head
@@ -577,51 +574,7 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             else:
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
                 T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
-                band_heads = None
-                if hwm is not None and band_t is not None:   # ... with attn_band: the main launch's table and the band heads
-                    kvr, band_heads = (None, None) if hwm == "dense" or cal is not None else self._layer_band_plan(kvr0, li)
-                elif hwm is not None:   # attn_window_recall > 0: dense until calibrated, then this layer's own table
-                    kvr = None if hwm == "dense" or cal is not None else self._layer_table(kvr0, li)
-                order = self._layer_order(kvr, N) if isinstance(kvr, KvRangesHeads) else None      # attn_window_balance
-                if cal is not None and widths is not None:   # ... in one pass: all keys in rings, a prefix LSE behind every ring
-                    A = (N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale)
-                    T("attn_self", _lib.flash_attn_d128_ranges_prefix, ws.qk, ws.qk, ws.vt, ws.att, *A,
-                      self._profile_segments(F_, S // F_, widths), cal.prefix, k_off=D)
-                    T("attn_calib", _lib.attn_prefix_mass, cal.prefix, cal.mass, N * heads, cal.segments, S,
-                      out_off=li * N * heads * cal.segments)
-                elif cal is not None:   # the calibration forward: the dense output + lse_full, the windowed launch for lse_part only
-                    A = (N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale)
-                    T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, *A, full, lse=cal.lse_full, k_off=D)
-                    T("attn_calib", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, cal.o, *A, kvr0, lse=cal.lse_part, k_off=D)
-                    T("attn_calib", _lib.attn_lse_recall, cal.lse_part, cal.lse_full, cal.recall, N * heads, S,
-                      out_off=li * N * heads)
-                    if band_t is not None:   # the third candidate: every head on position-major operands, for its LSE only
-                        self._band_attention(T, ws, self._band_scratch(N, S, D, S_pad), all_heads, band_t, N, F_, S, S_pad, scale,
-                                             lse=cal.lse_band)
-                        # (rows p F + f -> f hw + p: a torch transpose of the fp32 LSE, once per layer per video)
-                        cal.lse_band_rows.view(N, heads, F_, S // F_).copy_(cal.lse_band.view(N, heads, S // F_, F_).transpose(-1, -2))
-                        T("attn_calib", _lib.attn_lse_recall, cal.lse_band_rows, cal.lse_full, cal.recall_band, N * heads, S,
-                          out_off=li * N * heads)
-                elif band_heads is not None and band_heads.n_sel == heads:   # every head chose the band: no main launch
-                    pass
-                elif order is not None:
-                    T("attn_self", _lib.flash_attn_d128_ranges_order, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
-                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, order, k_off=D)
-                elif isinstance(kvr, KvRangesHeads):
-                    T("attn_self", _lib.flash_attn_d128_ranges_heads, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
-                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, k_off=D)
-                elif kvr is not None:
-                    T("attn_self", _lib.flash_attn_d128_ranges, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
-                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, kvr, k_off=D)
-                else:
-                    T("attn_self", _lib.flash_attn_d128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D,
-                      S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D)
-                if band_heads is not None:   # behind the main launch, which wrote zeros to these heads' slices of ws.att
-                    bs = self._band_scratch(N, S, D, S_pad)
-                    self._band_attention(T, ws, bs, band_heads, band_t, N, F_, S, S_pad, scale)
-                    Dc = band_heads.n_sel * 128
-                    T("attn_layout", _lib.attn_rows_position_major, bs.o, ws.att, band_heads, 128, N, F_, S // F_, S * Dc, Dc, S * D, D,
-                      inverse=True)
+                self._self_attention(T, ws, plan, li, band_t, N, F_, S, scale)
             lin("gemm_out", ws.att, L.wo, ws.x, S, D, D, D, D, bias=L.bo, R=ws.x, ldr=D, gate=ws.mod,
                 gate_off=m0 + 2 * D, strideGate=mod_bs, batch=N, strideA=S * D, strideC=S * D, strideR=S * D,
                 seg_split=1 << 30, flags=_lib.GEMM_GATE_F32)
@@ -667,8 +620,7 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                 T("step_cache", sc.after_block0, ws.x)
             T("step_cache", sc.end, ws.x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
 
-        if cal is not None:
-            self._head_window_finish(cal, [kvr0], band_table=band_t)
+        plan.finish(band_table=band_t)
 
         # ---- output head ----
         _lib.layernorm_mod_f32(ws.x, ws.y, None, None, ws.mod_out, ws.mod_out, 2 * D, N, S, D, cfg.eps, scale_off=D,
