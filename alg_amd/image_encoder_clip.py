@@ -206,7 +206,7 @@ class CLIPVisionModel:
         n = torch.empty(T, D, device=dev, dtype=bf)
         att = torch.empty(T, D, device=dev, dtype=bf)
         if self.flash:
-            L_pad = (L + 127) // 128 * 128
+            L_pad = (L + 127) // 128 * 128     # V^T pitch.  The attention takes ceil(L / 64) * 64; 128 is kept
             qk = torch.empty(T, 2 * D, device=dev, dtype=bf)
             vt = torch.zeros(B, D, L_pad, device=dev, dtype=bf)     # V^T written by a GEMM with swapped operands
         else:

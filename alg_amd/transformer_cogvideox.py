@@ -357,7 +357,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         cfg, dev = self.config, self.device
         D = cfg.inner_dim
         bf = dict(device=dev, dtype=torch.bfloat16)
-        S_pad = (S + 127) // 128 * 128  # V^T rows: S rounded up to the widest KV stage of the attention variants
+        S_pad = (S + 127) // 128 * 128  # V^T pitch.  The attention takes ceil(S / 64) * 64 (tests/test_gpu_attn_operands.py); 128 is kept
         ws = dict(
             S_pad=S_pad,
             x=torch.empty(N, S, D, **bf),

@@ -121,7 +121,7 @@ def run_attention(device, q, k, v, scale):
     """q,k,v [B, S, H, 64] bf16 (CPU) -> o [B, S, H, 64] via the kernel's strided layouts."""
     Bn, S, H, _ = q.shape
     D = H * 64
-    S_pad = (S + 127) // 128 * 128  # the 128-kv-per-stage variants read one 64-row tile further
+    S_pad = (S + 127) // 128 * 128  # (the kernels take ceil(S / 64) * 64 as well: tests/test_gpu_attn_operands.py)
     qk = torch.cat([q.reshape(Bn, S, D), k.reshape(Bn, S, D)], dim=-1).contiguous().to(device)
     vt = torch.zeros(Bn, D, S_pad, dtype=BF)
     perm = torch.tensor([swap23(n) for n in range(S)])
