@@ -79,12 +79,13 @@ static int gemm_check(const alg_gemm_args* a, bool fp8) {
     set_error("alg_gemm_bf16: gate needs a residual");
     return ALG_EINVAL;
   }
-  // 8-byte epilogue accesses need 8-byte aligned quads whenever N is a multiple of 4
+  // 8-byte epilogue accesses need 8-byte aligned quads whenever N is a multiple of 4 (the second gate segment is read with 8- and
+  // 16-byte loads at gate + gate_seg_stride + n: the segment stride counts as a pitch)
   if ((a->N & 3) == 0) {
     const bool bad = (a->ldc & 3) || (a->strideC & 3) || ((uintptr_t)a->C & 7) ||
                      (a->bias && !(a->flags & ALG_GEMM_BIAS_PER_ROW) && ((uintptr_t)a->bias & 7)) ||
                      (a->R && ((a->ldr & 3) || (a->strideR & 3) || ((uintptr_t)a->R & 7))) ||
-                     (a->gate && ((a->strideGate & 3) ||
+                     (a->gate && ((a->strideGate & 3) || ((a->flags & ALG_GEMM_GATE_SEG_STRIDE) && (a->gate_seg_stride & 3)) ||
                                   ((uintptr_t)a->gate & ((a->flags & ALG_GEMM_GATE_F32) ? 15 : 7))));
     if (bad) {
       set_error("alg_gemm_bf16: C/bias/R/gate must be 8-byte aligned with ldc/ldr/strides multiples of 4 elements");

@@ -224,7 +224,13 @@ typedef struct alg_gemm_args {
 } alg_gemm_args;
 
 /* C = R + gate * act(A @ B^T + bias)   (bias optional; either act or the residual(+gate) form).  K % 64 == 0, lda/ldb % 8 == 0,
- * A and B 16-byte aligned.  M and N are arbitrary (edge tiles clamp loads and guard stores). */
+ * A and B 16-byte aligned.  M and N are arbitrary (edge tiles clamp loads and guard stores).
+ * C, R, gate and a column bias: with N % 4 == 0 the epilogue moves whole quads, so C, R, a bf16 gate and the column bias are 8-byte
+ * aligned, a float32 gate (ALG_GEMM_GATE_F32) 16-byte aligned, and every pitch -- ldc, ldr, strideC, strideR, strideGate, and
+ * gate_seg_stride under ALG_GEMM_GATE_SEG_STRIDE -- is a multiple of 4 elements (0 included); a call that breaks this is ALG_EINVAL
+ * before any launch and writes no C.  With N % 4 != 0 every access is a single element: nothing beyond the element size is
+ * required.  (16-byte aligned C / R / gate with pitches in multiples of 8, N % 8 == 0 and perm_col0 % 16 == 0 is the fast path;
+ * the result does not depend on which store loop a call takes: tests/test_gpu_gemm_operands.py.) */
 int alg_gemm_bf16(const alg_gemm_args* args, void* stream);
 
 /* Packs an nn.Linear weight W [N][K] (bf16, row pitch ldb elements) for GEMM schedule 11 (ALG_GEMM_B_PACKED11): per (256-row tile of W,

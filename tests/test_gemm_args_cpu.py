@@ -95,6 +95,7 @@ def call(lib, entry, *a):
 
 
 PACKED11, PER_ROW, PERMUTE, GATE_F32 = _lib.GEMM_B_PACKED11, _lib.GEMM_BIAS_PER_ROW, _lib.GEMM_PERMUTE_COLS, _lib.GEMM_GATE_F32
+SEG_STRIDE = _lib.GEMM_GATE_SEG_STRIDE
 # the tall call of tests/test_gpu_gemm_packed_entries.py (TALL): two slabs at ldc = 16384
 TALL = dict(M=140_000, N=512, K=128, ldc=16384, strideC=0)
 
@@ -120,6 +121,12 @@ REFUSALS = [
     ("ldc % 4", "alg_gemm_bf16", (g(ldc=522),), EINVAL, ALIGN_C),
     ("column bias misaligned", "alg_gemm_bf16", (g(bias=BIAS + 4),), EINVAL, ALIGN_C),
     ("fp32 gate 8-byte aligned", "alg_gemm_bf16", (g(R=R, gate=GATE + 8, flags=GATE_F32),), EINVAL, ALIGN_C),
+    # the second gate segment is read with 8- and 16-byte loads at gate + gate_seg_stride + n: the segment stride is a pitch
+    ("gate_seg_stride % 4", "alg_gemm_bf16", (g(R=R, gate=GATE, flags=SEG_STRIDE, gate_seg_stride=522),), EINVAL, ALIGN_C),
+    ("gate_seg_stride odd, fp32 gate, fp8", "alg_gemm_fp8", (f8(R=R, gate=GATE, flags=SEG_STRIDE | GATE_F32, gate_seg_stride=521),),
+     EINVAL, ALIGN_C),
+    ("gate_seg_stride % 4, packed", "alg_gemm_bf16", (g(R=R, gate=GATE, flags=SEG_STRIDE | PACKED11, gate_seg_stride=6),), EINVAL,
+     ALIGN_C),
     ("conv kw = 5", "alg_gemm_bf16", (conv_args(conv_kw=5),), EINVAL, CONV % (6, 576, 64, 8, 64)),
     ("conv + fp8", "alg_gemm_fp8", (conv_args(K=1152, lda=128, ldb=1152, a_scale=SA, b_scale=SB),), EINVAL,
      CONV % (6, 1152, 128, 8, 64)),
@@ -186,6 +193,11 @@ ROUTES = [
     ("A panel past 32 bits", None, "alg_gemm_bf16", (g(lda=1 << 23),), "alg_gemm_bf16", PP),
     ("residual + gate", None, "alg_gemm_bf16", (g(R=R, gate=GATE),), "alg_gemm_bf16", ASM),
     ("gelu", None, "alg_gemm_bf16", (g(act=_lib.ACT_GELU_TANH),), "alg_gemm_bf16", ASM),
+    ("gate_seg_stride = 0", None, "alg_gemm_bf16", (g(R=R, gate=GATE, flags=SEG_STRIDE, gate_seg_stride=0),), "alg_gemm_bf16", ASM),
+    ("gate_seg_stride = N + 4", None, "alg_gemm_bf16", (g(R=R, gate=GATE, flags=SEG_STRIDE, gate_seg_stride=524),), "alg_gemm_bf16", ASM),
+    ("gate_seg_stride unused without the flag", None, "alg_gemm_bf16", (g(R=R, gate=GATE, gate_seg_stride=522),), "alg_gemm_bf16", ASM),
+    ("gate_seg_stride odd, N % 4 != 0", None, "alg_gemm_bf16", (g(N=250, ldc=250, ldr=250, strideC=75000, strideR=75000, R=R, gate=GATE,
+                                                                 flags=SEG_STRIDE, gate_seg_stride=251),), "alg_gemm_bf16", ASM),
     ("packed", None, "alg_gemm_bf16", (g(flags=PACKED11),), "alg_gemm_bf16", ASM),
     ("tall: first slab", None, "alg_gemm_bf16", (g(**TALL),), "alg_gemm_bf16", ASM),
     ("fp8 K = 128", None, "alg_gemm_fp8", (f8(),), "alg_gemm_bf16", PP),
