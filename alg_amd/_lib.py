@@ -39,6 +39,7 @@ EXPORTS = (
     "alg_flash_attn_d128_ranges_prefix", "alg_attn_prefix_mass",
     "alg_gemm_fp4", "alg_quantize_mxfp4_rows", "alg_gemm_fp4_q4out", "alg_layernorm_modulate_mxfp4",
     "alg_attn_rows_position_major", "alg_attn_vt_position_major",
+    "alg_lora_merge",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
@@ -124,6 +125,8 @@ def load_library():
                                 c_void_p]
     lib.alg_step_cache_workspace_bytes.argtypes = [c_int, c_int]
     lib.alg_step_cache_probe.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3
+    lib.alg_lora_merge.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
+                                   c_void_p]
     lib.alg_concat_cast.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_int] + [c_int64] * 7 + [
         c_void_p, c_int, c_void_p]
     lib.alg_flash_attn_d128.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 8 + [c_float, c_void_p]
@@ -484,6 +487,38 @@ def lincomb(terms, out_dtype, out=None):
     dts = (c_int * n)(*[_dt(t) for t in xs])
     _check(lib.alg_lincomb(arr, cf, dts, n, _ptr(out), ALG_F32 if out_dtype == torch.float32 else ALG_BF16,
                            out.numel(), _stream()), "alg_lincomb")
+    return out
+
+
+def lora_merge(w, a, b, scale, out=None):
+    """out = bf16(w + (scale * b) @ a) on the device (include/alg_hip.h: alg_lora_merge): w [N, K] bf16 or fp32 with unit column
+    stride (its row stride is the leading dimension), a [R, K], b [N, R] and scale [R] contiguous fp32.  out: a bf16 [N, K]
+    tensor with unit column stride; None allocates one; a bf16 w may be passed as out (in place).  Returns out."""
+    lib = load_library()
+    for name, t in (("w", w), ("a", a), ("b", b), ("scale", scale)):
+        _dev(t, "lora_merge: " + name)
+    if w.dim() != 2 or a.dim() != 2 or b.dim() != 2 or scale.dim() != 1:
+        raise AlgHipError("lora_merge: w, a and b must be 2-D, scale 1-D")
+    N, K = w.shape
+    R = a.shape[0]
+    if tuple(a.shape) != (R, K) or tuple(b.shape) != (N, R) or tuple(scale.shape) != (R,):
+        raise AlgHipError("lora_merge: shapes w %s, a %s, b %s, scale %s do not fit [N, K], [R, K], [N, R], [R]"
+                          % (tuple(w.shape), tuple(a.shape), tuple(b.shape), tuple(scale.shape)))
+    for name, t in (("a", a), ("b", b), ("scale", scale)):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise AlgHipError("lora_merge: %s must be a contiguous float32 tensor (adapters are never rounded)" % name)
+    if out is None:
+        out = torch.empty(N, K, dtype=torch.bfloat16, device=w.device)
+    _dev(out, "lora_merge: out")
+    if out.dtype != torch.bfloat16 or tuple(out.shape) != (N, K):
+        raise AlgHipError("lora_merge: out must be a bfloat16 tensor of shape %s" % ((N, K),))
+    for name, t in (("w", w), ("out", out)):
+        if K > 1 and t.stride(1) != 1:
+            raise AlgHipError("lora_merge: %s must have unit column stride" % name)
+    ldw = w.stride(0) if N > 1 else max(w.stride(0), K)
+    ldo = out.stride(0) if N > 1 else max(out.stride(0), K)
+    _check(lib.alg_lora_merge(_ptr(w), _dt(w), ldw, _ptr(a), _ptr(b), _ptr(scale), _ptr(out), ldo, N, K, R, _stream()),
+           "alg_lora_merge")
     return out
 
 

@@ -132,7 +132,7 @@ class CogVideoXImageToVideoPipeline:
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, cache_dir=None, transformer=None,
                         scheduler=None, vae=None, text_encoder=None, tokenizer=None, device="cuda", fp8=False,
                         fp4=False, step_cache=0.0, attn_window=0, attn_window_recall=0.0, attn_window_balance=False, attn_window_widths=None,
-                        **_):
+                        lora=None, **_):
         """Local-disk loader of a diffusers-format CogVideoX-I2V directory (`run.py:38-52`; no hub download here):
         `transformer/`, `vae/`, `text_encoder/` (T5), `tokenizer/`, `scheduler/` -- each read if its sub-directory
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
@@ -145,7 +145,9 @@ class CogVideoXImageToVideoPipeline:
         `attn_window` > 0 (ValueError otherwise); `attn_window_balance` (True = "units", "lanes", "units"; needs
         attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
         order (attn_window.balanced_order), bit-identical output.  `attn_window_widths` (the per-head window WIDTH of the
-        head_dim 128 models) is refused: ValueError."""
+        head_dim 128 models) is refused: ValueError.  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
+        transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
+        like `fp8` it has no effect on a transformer instance passed in."""
         import os
 
         from .attn_window import _balance_policy
@@ -167,7 +169,7 @@ class CogVideoXImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = CogVideoXTransformer3DModel.from_pretrained(model_path, torch_dtype=torch_dtype,
-                                                                      device=device, fp8=fp8, fp4=fp4)
+                                                                      device=device, fp8=fp8, fp4=fp4, lora=lora)
         if step_cache:
             transformer.step_cache = float(step_cache)
         if attn_window:

@@ -121,7 +121,7 @@ class HunyuanVideoImageToVideoPipeline:
     def from_pretrained(cls, model_path, torch_dtype=torch.bfloat16, transformer=None, scheduler=None, vae=None,
                         text_encoder=None, tokenizer=None, text_encoder_2=None, tokenizer_2=None, image_processor=None,
                         device="cuda", fp8_attention=False, fp8=False, attn_window=0, attn_window_recall=0.0,
-                        attn_window_balance=False, attn_window_widths=None, **_):
+                        attn_window_balance=False, attn_window_widths=None, lora=None, **_):
         """Local-disk loader of a diffusers-format HunyuanVideo-I2V directory (`run.py:68-90`): `transformer/`,
         `text_encoder/` (Llava-Llama-3) + `tokenizer/` + `image_processor/`, `text_encoder_2/` (CLIP-L text tower) +
         `tokenizer_2/`, `vae/`, `scheduler/`.  `fp8=True` loads the transformer with e4m3 block linears
@@ -132,7 +132,9 @@ class HunyuanVideoImageToVideoPipeline:
         attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
         order (attn_window.balanced_order), bit-identical output; `attn_window_widths`
         (a strictly ascending tuple of positive ints ending in attn_window, or "1,2,4"; needs attn_window_recall > 0, ValueError
-        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration."""
+        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration.  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
+        transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
+        like `fp8` it has no effect on a transformer instance passed in."""
         import os
 
         from .attn_window import _balance_policy
@@ -158,7 +160,7 @@ class HunyuanVideoImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = HunyuanVideoTransformer3DModel.from_pretrained(model_path, device=device, fp8_attention=fp8_attention,
-                                                                         fp8=fp8)
+                                                                         fp8=fp8, lora=lora)
         if attn_window:
             transformer.attn_window = int(attn_window)
         if attn_window_recall:

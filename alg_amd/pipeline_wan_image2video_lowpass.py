@@ -118,7 +118,10 @@ class WanImageToVideoPipeline:
         otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration;
         `attn_band` (an int, positions on each side; needs attn_window > 0 and attn_window_recall > 0, not with
         attn_window_widths or fp8_attention, ValueError otherwise) adds the position-major band as a third candidate per head
-        (transformer.attn_band)."""
+        (transformer.attn_band).  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
+        transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
+        like `fp8` it has no effect on a transformer instance passed in.  (`lora` is taken from the trailing keywords: the
+        named keywords end with attn_band.)"""
         import os
 
         from .attn_window import _balance_policy
@@ -154,7 +157,8 @@ class WanImageToVideoPipeline:
 
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
-            transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention)
+            transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention,
+                                                                lora=_.get("lora"))
         if attn_band:
             transformer.attn_band = int(attn_band)
         if step_cache:

@@ -90,6 +90,9 @@ def _bf(t, device):
 
 class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
     dtype = torch.bfloat16
+    # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
+    # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
+    lora_report = ()
 
     # the block linears that fp8 mode quantises, per output channel: Q|K, V, attention out, feed-forward in / out
     FP8_WEIGHTS = ("wqk", "wv", "wo", "wf1", "wf2")
@@ -328,22 +331,36 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
 
     # ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False, fp8=False, fp4=False):
+    def from_synthetic(cls, config=None, seed=1234, std=0.02, device="cuda", randomize_affine=False, fp8=False, fp4=False,
+                       lora=None):
         """Seeded synthetic weights at the configured shapes, generated on the device tensor by tensor (the
-        real checkpoint cannot be downloaded here).  Matrices N(0, std^2), biases 0, norm gains 1."""
+        real checkpoint cannot be downloaded here).  Matrices N(0, std^2), biases 0, norm gains 1.  `lora` (a path,
+        (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is merged into the state dict
+        before the model is built from it."""
+        from .lora import merge_into
         from .weights import synthetic_state_dict
 
         config = config or CogVideoXTransformerConfig()
-        return cls(config, synthetic_state_dict(config, seed=seed, std=std, device=device,
-                                                 randomize_affine=randomize_affine), device=device, fp8=fp8, fp4=fp4)
+        sd = synthetic_state_dict(config, seed=seed, std=std, device=device, randomize_affine=randomize_affine)
+        report = merge_into(sd, lora, device)
+        model = cls(config, sd, device=device, fp8=fp8, fp4=fp4)
+        model.lora_report = report
+        return model
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", fp8=False, fp4=False, **_):
-        """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk."""
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", fp8=False, fp4=False,
+                        lora=None, **_):
+        """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk.  `lora` (as in
+        from_synthetic) is merged into the state dict before the model is built from it; in a multi-rank run every rank reads
+        the adapter file and merges for itself behind the weight broadcast (alg_lora_merge gives every rank the same bits)."""
+        from .lora import merge_into
         from .weights import load_diffusers_transformer
 
         config, sd = load_diffusers_transformer(path, subfolder)
-        return cls(config, sd, device=device, fp8=fp8, fp4=fp4)
+        report = merge_into(sd, lora, device)
+        model = cls(config, sd, device=device, fp8=fp8, fp4=fp4)
+        model.lora_report = report
+        return model
 
     def to(self, *args, **kwargs):
         return self

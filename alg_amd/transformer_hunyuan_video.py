@@ -150,6 +150,9 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
 
 class HunyuanVideoTransformer3DModel(HeadWindowHost):
     dtype = BF
+    # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
+    # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
+    lora_report = ()
 
     # the block linears that fp8 mode quantises, per output channel (attribute names of a block's weights): dual blocks, latent
     # stream: to_q | to_k, to_v, to_out.0, ff.net.0.proj, ff.net.2; single blocks: to_q | to_k, to_v, proj_mlp, proj_out
@@ -300,13 +303,22 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                 setattr(L, nm, (None, held[1]) if isinstance(held, tuple) else None)
 
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8_attention=False, fp8=False):
+    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8_attention=False, fp8=False, lora=None):
+        """`lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is merged into
+        the state dict before the model is built from it."""
+        from .lora import merge_into
         config = config or HunyuanVideoTransformerConfig()
-        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8_attention=fp8_attention,
-                   fp8=fp8)
+        sd = synthetic_state_dict(config, seed=seed, device=device)
+        report = merge_into(sd, lora, device)
+        model = cls(config, sd, device=device, fp8_attention=fp8_attention, fp8=fp8)
+        model.lora_report = report
+        return model
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8_attention=False, fp8=False, **_):
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8_attention=False, fp8=False,
+                        lora=None, **_):
+        """Load a diffusers-format checkpoint directory from local disk.  `lora` (as in from_synthetic) is merged into the state
+        dict before the model is built from it; in a multi-rank run every rank merges for itself behind the weight broadcast."""
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -318,8 +330,12 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
         cfg = HunyuanVideoTransformerConfig(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in raw.items()
                                                if k in fields})
         from .weights import read_shards
+        from .lora import merge_into
         sd = read_shards(root)
-        return cls(cfg, sd, device=device, fp8_attention=fp8_attention, fp8=fp8)
+        report = merge_into(sd, lora, device)
+        model = cls(cfg, sd, device=device, fp8_attention=fp8_attention, fp8=fp8)
+        model.lora_report = report
+        return model
 
     def to(self, *a, **k):
         return self

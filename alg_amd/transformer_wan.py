@@ -155,6 +155,9 @@ def k_scale_bound(norm_weight, norm_dim, heads, rope):
 
 class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
     dtype = BF
+    # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
+    # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
+    lora_report = ()
 
     def __init__(self, config: WanTransformerConfig, weights: dict, device="cuda", fp8=False, fp8_attention=False):
         """``fp8=True`` (BASELINE config 5): the seven large linears of every block run on the fp8 MFMA -- weights are
@@ -277,14 +280,23 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
 
     # ---- construction ------------------------------------------------------------------------------------------------
     @classmethod
-    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8=False, fp8_attention=False):
+    def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8=False, fp8_attention=False, lora=None):
+        """`lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is merged into
+        the state dict before the model is built from it."""
+        from .lora import merge_into
         config = config or WanTransformerConfig()
-        return cls(config, synthetic_state_dict(config, seed=seed, device=device), device=device, fp8=fp8,
-                   fp8_attention=fp8_attention)
+        sd = synthetic_state_dict(config, seed=seed, device=device)
+        report = merge_into(sd, lora, device)
+        model = cls(config, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
+        model.lora_report = report
+        return model
 
     @classmethod
-    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8=False, fp8_attention=False, **_):
-        """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk."""
+    def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8=False, fp8_attention=False,
+                        lora=None, **_):
+        """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk.  `lora` (as in
+        from_synthetic) is merged into the state dict before the model is built from it; in a multi-rank run every rank merges
+        for itself behind the weight broadcast."""
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -295,8 +307,12 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         fields = WanTransformerConfig.__dataclass_fields__
         cfg = WanTransformerConfig(**{k: (tuple(v) if k == "patch_size" else v) for k, v in raw.items() if k in fields})
         from .weights import read_shards
+        from .lora import merge_into
         sd = read_shards(root)
-        return cls(cfg, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
+        report = merge_into(sd, lora, device)
+        model = cls(cfg, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
+        model.lora_report = report
+        return model
 
     def to(self, *args, **kwargs):
         return self

@@ -159,6 +159,28 @@ int64_t alg_step_cache_workspace_bytes(int rows, int D);
 int alg_step_cache_probe(void* keep, const void* x1, void* r, int rows, int D, int tok0, int tok_rows, void* workspace,
                          double* sums, void* stream);
 
+/* LoRA merge at load time (an extension; the reference pipelines inherit diffusers' LoRA loader mixins; alg_amd/lora.py merges
+ * the adapters into the state dict BEFORE a transformer is built from it, so no forward path knows about them):
+ *   t[n, r]   = double(scale[r]) * double(B[n, r])                exact
+ *   acc[n, k] = fma(t[n, r], double(A[r, k]), acc)                r = 0 .. R-1 ascending, from acc = 0, in double
+ *   out[n, k] = bf16_rne(double(W[n, k]) + acc[n, k])             ONE rounding, from the double sum straight to bf16
+ * (double, not fp32: where W and the delta cancel, an fp32 chain is several bf16 steps away from the float64 merge; this is
+ * within one step everywhere, and it runs once per model load)
+ * W: [N][K] of w_dtype (ALG_BF16 or ALG_F32: an fp32 checkpoint is not rounded to bf16 before the delta is added), leading
+ * dimension ldw; A: [R][K] fp32 and B: [N][R] fp32, both contiguous; scale: [R] fp32, one entry per rank column (several adapters
+ * are concatenated along R by the caller, each column carrying its user_scale * alpha / r; B is never pre-scaled); out: bf16
+ * [N][K], leading dimension ldo.  out may be W itself when W is bf16 and ldw == ldo; any other overlap of the two is refused.
+ * 1 <= R <= 512; K % 8 == 0; N and R need no alignment (N == 0: nothing is launched); ldw, ldo >= K and multiples of 16
+ * bytes; W, A and out 16-byte aligned.  Bytes between K and a leading dimension are neither read nor written.
+ * The chain of one output element is a function of its own operands alone (vector fp64 FMA, no MFMA, no atomics): the result
+ * does not depend on the tile, the grid or where a row lies in the matrix -- a slice merged alone has the bits of the full
+ * merge, and every rank of a multi-GPU run produces the same weights.
+ * Check, plan, launch: the shape refusals come first (a validate-only call may pass null pointers), then null or misaligned
+ * pointers and the aliasing rule, all ALG_EINVAL before anything is launched; more workgroups (64 x 128 outputs each) than one
+ * launch covers is ALG_ELIMIT. */
+int alg_lora_merge(const void* W, int w_dtype, int64_t ldw, const float* A, const float* B, const float* scale, void* out,
+                   int64_t ldo, int N, int K, int R, void* stream);
+
 /* wan:877-889, hy:1146-1160, 1230  CFG batch assembly in one launch (replaces cat([latents]*n) + cat(dim) + .to()):
  *   out[i, o, a, r] = a < A0 ? src0[i][o*s0_ostride + a*R + r] : src1[i][o*s1_ostride + (a1_off + a - A0)*R + r]
  * for i < n (<= 16), o < O, a < A0 + A1, r < R, cast to out_dtype.  src0 / src1 are HOST arrays of n device pointers
