@@ -40,10 +40,11 @@ EXPORTS = (
     "alg_gemm_fp4", "alg_quantize_mxfp4_rows", "alg_gemm_fp4_q4out", "alg_layernorm_modulate_mxfp4",
     "alg_attn_rows_position_major", "alg_attn_vt_position_major",
     "alg_lora_merge",
+    "alg_attn_drift", "alg_attn_drift_workspace_bytes",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
-            "alg_step_cache_workspace_bytes")
+            "alg_step_cache_workspace_bytes", "alg_attn_drift_workspace_bytes")
 
 
 class AlgHipError(RuntimeError):
@@ -125,6 +126,8 @@ def load_library():
                                 c_void_p]
     lib.alg_step_cache_workspace_bytes.argtypes = [c_int, c_int]
     lib.alg_step_cache_probe.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3
+    lib.alg_attn_drift_workspace_bytes.argtypes = [c_int, c_int]
+    lib.alg_attn_drift.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
     lib.alg_lora_merge.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                    c_void_p]
     lib.alg_concat_cast.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_int] + [c_int64] * 7 + [
@@ -520,6 +523,36 @@ def lora_merge(w, a, b, scale, out=None):
     _check(lib.alg_lora_merge(_ptr(w), _dt(w), ldw, _ptr(a), _ptr(b), _ptr(scale), _ptr(out), ldo, N, K, R, _stream()),
            "alg_lora_merge")
     return out
+
+
+ATTN_DRIFT_THREADS, ATTN_DRIFT_MAX_BLOCKS = 256, 512     # attn_reuse.hip's AD_THREADS, AD_MAX_BLOCKS: one pass of the capped grid
+
+
+def attn_drift_workspace_bytes(rows, cols):
+    """Bytes of workspace alg_attn_drift needs for [rows, cols] operands (one pair of doubles per block of its capped grid)."""
+    n = load_library().alg_attn_drift_workspace_bytes(int(rows), int(cols))
+    _check(0 if n >= 0 else int(n), "alg_attn_drift_workspace_bytes")
+    return int(n)
+
+
+def attn_drift(a, b, workspace, out):
+    """out[0] = sum |a - b|, out[1] = sum |b| (include/alg_hip.h: alg_attn_drift).  a, b: device bf16 [rows, cols] tensors or views
+    with unit column stride (the row strides are theirs); workspace: at least attn_drift_workspace_bytes(rows, cols) bytes; out: 2
+    device float64 elements (a contiguous view is fine)."""
+    lib = load_library()
+    for name, t in (("a", a), ("b", b)):
+        _dev(t, "attn_drift: " + name)
+        if t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape != a.shape or (t.shape[1] > 1 and t.stride(1) != 1):
+            raise AlgHipError("attn_drift: a and b must be bfloat16 [rows, cols] tensors of one shape with unit column stride")
+    rows, cols = a.shape
+    _dev(workspace, "attn_drift: workspace")
+    _dev(out, "attn_drift: out")
+    if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous():
+        raise AlgHipError("attn_drift: out must be a contiguous device float64 tensor of 2 elements")
+    if workspace.numel() * workspace.element_size() < attn_drift_workspace_bytes(rows, cols):
+        raise AlgHipError("attn_drift: the workspace is smaller than attn_drift_workspace_bytes(rows, cols)")
+    _check(lib.alg_attn_drift(_ptr(a), _ptr(b), rows, cols, a.stride(0) if rows > 1 else cols, b.stride(0) if rows > 1 else cols,
+                              _ptr(workspace), _ptr(out), _stream()), "alg_attn_drift")
 
 
 def step_cache_workspace_bytes(rows, D):

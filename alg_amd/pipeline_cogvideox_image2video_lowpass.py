@@ -29,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import _lib, attn_window, lp_utils, step_cache
+from . import _lib, attn_reuse, attn_window, lp_utils, step_cache
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler
 from .transformer_cogvideox import CogVideoXTransformer3DModel
 
@@ -147,11 +147,15 @@ class CogVideoXImageToVideoPipeline:
         order (attn_window.balanced_order), bit-identical output.  `attn_window_widths` (the per-head window WIDTH of the
         head_dim 128 models) is refused: ValueError.  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
         transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
-        like `fp8` it has no effect on a transformer instance passed in."""
+        like `fp8` it has no effect on a transformer instance passed in.  `attn_reuse` (an int, 0 = off, N >= 2; 1 is a ValueError), `attn_reuse_t_lo` = 100 and
+        `attn_reuse_t_hi` = 800 (lo >= hi is a ValueError) switch the transformer's attention reuse across steps on
+        (alg_amd/attn_reuse.py; off by default); like `fp8` they go to the transformer loader and have no effect on a transformer
+        instance passed in.  (They are taken from the trailing keywords: the order of the named ones is pinned.)"""
         import os
 
         from .attn_window import _balance_policy
 
+        reuse_kw = attn_reuse.switches_from(_)
         if attn_window_widths is not None:
             raise ValueError("attn_window_widths=%r: the per-head window width (one-pass calibration) is not built for head_dim 64"
                              % (attn_window_widths,))
@@ -169,7 +173,8 @@ class CogVideoXImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = CogVideoXTransformer3DModel.from_pretrained(model_path, torch_dtype=torch_dtype,
-                                                                      device=device, fp8=fp8, fp4=fp4, lora=lora)
+                                                                      device=device, fp8=fp8, fp4=fp4, lora=lora,
+                                                                      **reuse_kw)
         if step_cache:
             transformer.step_cache = float(step_cache)
         if attn_window:
@@ -586,6 +591,9 @@ class CogVideoXImageToVideoPipeline:
                 raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
                                        "passes and leave the single-GPU result; run one of the two")
             self.transformer.reset_step_cache()
+        # the transformer's opt-in attention reuse (alg_amd/attn_reuse.py): a new video starts from an empty cache, every forward names
+        # the roles of its passes and its timestep, the first and the last step are always computed
+        use_reuse = attn_reuse.begin_video(self.transformer, cfg_split)
         # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
         use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
         if use_recall:
@@ -655,6 +663,10 @@ class CogVideoXImageToVideoPipeline:
                 noise_pred = cfg_split.merge(local, n_pass, B)
             else:
                 cache_kw = dict(cache_keys=step_cache.pass_keys(n_pass, B), cache_force=i == len(timesteps) - 1) if use_cache else {}
+                if use_reuse:
+                    self.transformer.attn_reuse_advance()
+                    cache_kw = dict(cache_keys=attn_reuse.step_keys(n_pass, B, int(t)),
+                                    cache_force=i == len(timesteps) - 1 or not self.transformer.attn_reuse_stats)
                 noise_pred = dit(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb, **cache_kw)
             gs = guidance_scale
             if do_cfg and not use_low_pass_guidance and use_dynamic_cfg:  # cog:1105-1108

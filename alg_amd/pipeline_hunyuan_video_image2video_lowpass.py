@@ -29,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from . import _lib, attn_window, lp_utils
+from . import _lib, attn_reuse, attn_window, lp_utils
 from .pipeline_cogvideox_image2video_lowpass import retrieve_timesteps
 from .schedulers import FlowMatchEulerDiscreteScheduler
 
@@ -134,8 +134,13 @@ class HunyuanVideoImageToVideoPipeline:
         (a strictly ascending tuple of positive ints ending in attn_window, or "1,2,4"; needs attn_window_recall > 0, ValueError
         otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration.  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
         transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
-        like `fp8` it has no effect on a transformer instance passed in."""
+        like `fp8` it has no effect on a transformer instance passed in.  `attn_reuse` (an int, 0 = off, N >= 2; 1 is a ValueError), `attn_reuse_t_lo` = 100 and
+        `attn_reuse_t_hi` = 800 (lo >= hi is a ValueError) switch the transformer's attention reuse across steps on
+        (alg_amd/attn_reuse.py; off by default); like `fp8` they go to the transformer loader and have no effect on a transformer
+        instance passed in.  (They are taken from the trailing keywords: the order of the named ones is pinned.)"""
         import os
+
+        reuse_kw = attn_reuse.switches_from(_)
 
         from .attn_window import _balance_policy
         _balance_policy(attn_window_balance)
@@ -160,7 +165,7 @@ class HunyuanVideoImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = HunyuanVideoTransformer3DModel.from_pretrained(model_path, device=device, fp8_attention=fp8_attention,
-                                                                         fp8=fp8, lora=lora)
+                                                                         fp8=fp8, lora=lora, **reuse_kw)
         if attn_window:
             transformer.attn_window = int(attn_window)
         if attn_window_recall:
@@ -581,6 +586,9 @@ class HunyuanVideoImageToVideoPipeline:
         use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
         if use_recall:
             self.transformer.reset_attn_window_heads()
+        # the transformer's opt-in attention reuse (alg_amd/attn_reuse.py): a new video starts from an empty cache, every forward names
+        # the roles of its passes and its timestep, the first and the last step are always computed
+        use_reuse = attn_reuse.begin_video(self.transformer)
         for i, t in enumerate(timesteps):
             if self._interrupt:
                 continue
@@ -608,12 +616,17 @@ class HunyuanVideoImageToVideoPipeline:
                 mask = cat(negative_prompt_attention_mask, prompt_attention_mask)
             n = latent_model_input.shape[0]
             timestep = t.expand(n).to(device=device, dtype=tdtype)  # hy:1230 (the timestep itself is cast to bf16)
+            cache_kw = {}
+            if use_reuse:
+                self.transformer.attn_reuse_advance()
+                cache_kw = dict(cache_keys=attn_reuse.step_keys(len(groups), latents.shape[0], float(t)),
+                                cache_force=i == len(timesteps) - 1 or not self.transformer.attn_reuse_stats)
             # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
             noise_pred = attn_window.call_transformer(
                 self.transformer, i < attn_window_dense_steps, hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
                 encoder_attention_mask=mask, pooled_projections=pooled, guidance=guidance,
                 attention_kwargs=attention_kwargs, return_dict=False,
-                calibrate=use_recall and i == attn_window.calibration_step(attn_window_dense_steps))[0]
+                calibrate=use_recall and i == attn_window.calibration_step(attn_window_dense_steps), **cache_kw)[0]
             # hy:1254-1261 keys the combine on shape[0] (3 -> three chunks, 2 -> two chunks, anything else: none)
             if noise_pred.shape[0] in (2, 3):
                 noise_pred = _lib.cfg_combine(noise_pred.contiguous(), noise_pred.shape[0], true_cfg_scale)

@@ -31,7 +31,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, attn_window, lp_utils, step_cache
+from . import _lib, attn_reuse, attn_window, lp_utils, step_cache
 from .schedulers import UniPCMultistepScheduler
 
 
@@ -121,8 +121,13 @@ class WanImageToVideoPipeline:
         (transformer.attn_band).  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
         transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
         like `fp8` it has no effect on a transformer instance passed in.  (`lora` is taken from the trailing keywords: the
-        named keywords end with attn_band.)"""
+        named keywords end with attn_band.)  `attn_reuse` (an int, 0 = off, N >= 2; 1 is a ValueError), `attn_reuse_t_lo` = 100 and
+        `attn_reuse_t_hi` = 800 (lo >= hi is a ValueError) switch the transformer's attention reuse across steps on
+        (alg_amd/attn_reuse.py; off by default); like `fp8` they go to the transformer loader and have no effect on a transformer
+        instance passed in.  (They are taken from the trailing keywords: the order of the named ones is pinned.)"""
         import os
+
+        reuse_kw = attn_reuse.switches_from(_)
 
         from .attn_window import _balance_policy
         _balance_policy(attn_window_balance)
@@ -158,7 +163,7 @@ class WanImageToVideoPipeline:
         has = lambda sub: os.path.isdir(os.path.join(model_path, sub))
         if transformer is None:
             transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention,
-                                                                lora=_.get("lora"))
+                                                                lora=_.get("lora"), **reuse_kw)
         if attn_band:
             transformer.attn_band = int(attn_band)
         if step_cache:
@@ -521,6 +526,9 @@ class WanImageToVideoPipeline:
                 raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
                                        "passes and leave the single-GPU result; run one of the two")
             self.transformer.reset_step_cache()
+        # the transformer's opt-in attention reuse (alg_amd/attn_reuse.py): a new video starts from an empty cache, every forward names
+        # the roles of its passes and its timestep, the first and the last step are always computed
+        use_reuse = attn_reuse.begin_video(self.transformer, cfg_split)
         # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
         use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
         if use_recall:
@@ -583,6 +591,10 @@ class WanImageToVideoPipeline:
             else:
                 cache_kw = dict(cache_keys=step_cache.pass_keys(len(groups), latents.shape[0]),
                                 cache_force=i == len(timesteps) - 1) if use_cache else {}
+                if use_reuse:
+                    self.transformer.attn_reuse_advance()
+                    cache_kw = dict(cache_keys=attn_reuse.step_keys(len(groups), latents.shape[0], float(t)),
+                                    cache_force=i == len(timesteps) - 1 or not self.transformer.attn_reuse_stats)
                 noise_pred = dit(
                     hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
                     encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False, **cache_kw)[0]

@@ -43,6 +43,7 @@ from typing import Optional
 import torch
 
 from . import _lib
+from .attn_reuse import AttnReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
 from .step_cache import StepCacheHost
 
@@ -88,7 +89,7 @@ def _bf(t, device):
     return t.to(device=device, dtype=torch.bfloat16).contiguous()
 
 
-class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
+class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
     dtype = torch.bfloat16
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -157,6 +158,11 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         # residual they produced on the last computed forward.  0.0: every forward is the plain one, launch for launch.
         self.step_cache = 0.0
         self.step_cache_max_consecutive = 0   # at most this many skipped forwards in a row (0: no cap)
+        # N >= 2 (opt-in, an extension: alg_amd/attn_reuse.py): a forward that is handed `cache_keys` with the step's timestep
+        # (attn_reuse.step_keys) computes every block's self-attention on every N-th step while attn_reuse_t_lo < t < attn_reuse_t_hi
+        # and reads it back from a per-key cache on the steps between, skipping norm1, Q|K, V^T, qk_norm_rope and the attention.
+        # 0: every forward is the plain one, launch for launch, nothing allocated.  attn_reuse_drift: the diagnostic (AttnReuseHost)
+        self.attn_reuse = 0
         # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): in the joint attention of every block a
         # block of latent queries attends to the prompt keys, to the conditioning frames (attn_sink_frames) and to the latent frames
         # within attn_window of its own; prompt queries see everything.  ONE alg_flash_attn_d64_ranges launch for the whole batch.
@@ -352,14 +358,18 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
                         lora=None, **_):
         """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk.  `lora` (as in
         from_synthetic) is merged into the state dict before the model is built from it; in a multi-rank run every rank reads
-        the adapter file and merges for itself behind the weight broadcast (alg_lora_merge gives every rank the same bits)."""
+        the adapter file and merges for itself behind the weight broadcast (alg_lora_merge gives every rank the same bits).  `attn_reuse`, `attn_reuse_t_lo` and `attn_reuse_t_hi` (taken from the trailing keywords; alg_amd/attn_reuse.py) set the
+        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors."""
+        from .attn_reuse import apply_switches, switches_from
         from .lora import merge_into
         from .weights import load_diffusers_transformer
 
+        reuse = switches_from(_)
         config, sd = load_diffusers_transformer(path, subfolder)
         report = merge_into(sd, lora, device)
         model = cls(config, sd, device=device, fp8=fp8, fp4=fp4)
         model.lora_report = report
+        apply_switches(model, reuse)
         return model
 
     def to(self, *args, **kwargs):
@@ -458,7 +468,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
            R=x, ldr=D, gate=mod, gate_off=m2 + 4 * D, strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * F4,
            strideAScale=S * (F4 // 32), strideC=S * D, strideR=S * D)
 
-    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, plan, li, fp4=False):
+    def _block_fp8(self, L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, plan, li, fp4=False, ar=None):
         """One transformer block with e4m3 operands on its five linears: the launch order of the bf16 block, each GEMM input
         quantised per token into q8 / q8s first (by the LayerNorm itself where a norm produces it)."""
         cfg, G, TM = self.config, _lib.gemm, self._timed
@@ -491,14 +501,19 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             TM(name, G, q8, wt[0], C, S, N_, K_, K_, K_, ldc, a_scale=q8s, b_scale=wt[1], batch=N, strideA=S * K_,
                strideAScale=SS, strideC=S * ldc, **kw)
 
-        ln_mod(L["norm1_w"], L["norm1_b"], m1)
-        lin("gemm_qk", L["wqk8"], qk, 2 * D, D, 2 * D, bias=L["bqk"])
-        # V^T: the weight is the A operand, the (already quantised) tokens are B
-        TM("gemm_vt", G, L["wv8"][0], q8, vt, D, S, D, D, D, S_pad, a_scale=L["wv8"][1], b_scale=q8s, strideBScale=SS,
-           bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
-        TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
-           cfg.qk_norm_eps, q_scale=q_scale)
-        self._attention(ws, plan, li, N, S, T, scale, prescale)
+        if ar is not None and ar.reuse:   # attn_reuse: the cached attention output stands in for everything up to it
+            TM("attn_reuse", ar.load, li, att)
+        else:
+            ln_mod(L["norm1_w"], L["norm1_b"], m1)
+            lin("gemm_qk", L["wqk8"], qk, 2 * D, D, 2 * D, bias=L["bqk"])
+            # V^T: the weight is the A operand, the (already quantised) tokens are B
+            TM("gemm_vt", G, L["wv8"][0], q8, vt, D, S, D, D, D, S_pad, a_scale=L["wv8"][1], b_scale=q8s, strideBScale=SS,
+               bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+            TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
+               cfg.qk_norm_eps, q_scale=q_scale)
+            self._attention(ws, plan, li, N, S, T, scale, prescale)
+            if ar is not None:
+                TM("attn_reuse", ar.store, li, att)
         quant(att, D)
         lin("gemm_out", L["wo8"], x, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
             strideGate=self.mod_cols, seg_split=T, strideR=S * D)
@@ -563,7 +578,9 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         encoder_hidden_states [N, T, text_dim]; timestep [N].  Returns noise prediction [N, F, C_out, H, W] bf16.
 
         cache_keys (one hashable per sample, naming the role of its pass) arms the step cache when `step_cache` > 0;
-        cache_force computes this forward whatever the probe says (the last step of a schedule).
+        cache_force computes this forward whatever the probe says (the last step of a schedule).  With `attn_reuse` >= 2 the same
+        keys, as an attn_reuse.StepKeys that carries the step's timestep, name the samples' attention-cache entries, and
+        cache_force computes (and rewrites them) whatever the schedule says.
         """
         cfg = self.config
         N = len(conds)
@@ -652,6 +669,8 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
         packed = self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         wo_k, wf1_k, wf2_k = ("pwo", "pwf1", "pwf2") if packed else ("wo", "wf1", "wf2")
         kvr = self._window_ranges(Fr // p_t, (Hh // p) * (Ww // p), T) if self.attn_window else None   # None: the dense launch
+        # attention reuse (alg_amd/attn_reuse.py): None -- off, nothing below differs from the plain forward; refused next to a step cache
+        ar = self._attn_reuse_begin(cache_keys, cache_force, N, len(self.layers), S, D)
         sc = self._step_cache_begin(x, cache_keys, cache_force, T, P)   # None: off, nothing below differs from the plain forward
         # this forward's attention launches: the shared window, or per-head tables chosen by recall (attn_window.SelfAttnPlan)
         plan = self._self_attn_begin([kvr], (Fr // p_t, (Hh // p) * (Ww // p), T, int(self.attn_window), int(self.attn_sink_frames)),
@@ -662,26 +681,31 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             m1 = li * 12 * D          # norm1: shift @+0, scale @+2D, gate @+4D (each [2][D])
             m2 = m1 + 6 * D           # norm2
             if fp8:
-                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, plan, li, fp4)
+                self._block_fp8(L, ws, q8, q8s, N, S, T, m1, m2, cos, sin, scale, q_scale, prescale, plan, li, fp4, ar)
                 continue
-            TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
-               T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
-            qk_call = ((y, L["wqk"], qk, S, 2 * D, D, D, D, 2 * D), dict(bias=L["bqk"], batch=N, strideA=S * D, strideC=S * 2 * D))
-            vt_call = ((L["wv"], y, vt, D, S, D, D, D, S_pad), dict(bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad,
-                                                                   flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS))
-            # the softmax scale * log2(e) rides in Q's last rounding (attn_prescale = False: scaled per score in the attention)
-            if self.pair_qkv and self.fuse_qk_norm:   # ... and QK LayerNorm + rope in the Q|K store loop: qk is written once
-                TM("gemm_qkv", _lib.gemm_pair_qk, qk_call, vt_call, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin,
-                               Hn, T, cfg.qk_norm_eps, q_scale=q_scale)
+            if ar is not None and ar.reuse:   # attn_reuse: the cached attention output stands in for everything up to it
+                TM("attn_reuse", ar.load, li, att)
             else:
-                if self.pair_qkv:   # both projections read y: ONE persistent launch, the two partial last rounds become one
-                    TM("gemm_qkv", _lib.gemm_pair, qk_call, vt_call)
+                TM("ln_mod", _lib.layernorm_modulate, x, y, L["norm1_w"], L["norm1_b"], mod, mod, self.mod_cols, N, S, D,
+                   T, cfg.norm_eps, scale_off=m1 + 2 * D, shift_off=m1)
+                qk_call = ((y, L["wqk"], qk, S, 2 * D, D, D, D, 2 * D), dict(bias=L["bqk"], batch=N, strideA=S * D, strideC=S * 2 * D))
+                vt_call = ((L["wv"], y, vt, D, S, D, D, D, S_pad), dict(bias=L["bv"], batch=N, strideB=S * D, strideC=D * S_pad,
+                                                                       flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS))
+                # the softmax scale * log2(e) rides in Q's last rounding (attn_prescale = False: scaled per score in the attention)
+                if self.pair_qkv and self.fuse_qk_norm:   # ... and QK LayerNorm + rope in the Q|K store loop: qk is written once
+                    TM("gemm_qkv", _lib.gemm_pair_qk, qk_call, vt_call, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin,
+                                   Hn, T, cfg.qk_norm_eps, q_scale=q_scale)
                 else:
-                    TM("gemm_qk", G, *qk_call[0], **qk_call[1])
-                    TM("gemm_vt", G, *vt_call[0], **vt_call[1])
-                TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
-                                   cfg.qk_norm_eps, q_scale=q_scale)
-            self._attention(ws, plan, li, N, S, T, scale, prescale)
+                    if self.pair_qkv:   # both projections read y: ONE persistent launch, the two partial last rounds become one
+                        TM("gemm_qkv", _lib.gemm_pair, qk_call, vt_call)
+                    else:
+                        TM("gemm_qk", G, *qk_call[0], **qk_call[1])
+                        TM("gemm_vt", G, *vt_call[0], **vt_call[1])
+                    TM("qk_norm_rope", _lib.qk_norm_rope_, qk, L["norm_q_w"], L["norm_q_b"], L["norm_k_w"], L["norm_k_b"], cos, sin, N, S, Hn, T,
+                                       cfg.qk_norm_eps, q_scale=q_scale)
+                self._attention(ws, plan, li, N, S, T, scale, prescale)
+                if ar is not None:
+                    TM("attn_reuse", ar.store, li, att)
             TM("gemm_out", G, att, L[wo_k], x, S, D, D, D, D, D, bias=L["bo"], R=x, ldr=D, gate=mod, gate_off=m1 + 4 * D,
               strideGate=self.mod_cols, seg_split=T, batch=N, strideA=S * D, strideC=S * D, strideR=S * D)
             if fp4:
@@ -700,6 +724,8 @@ class CogVideoXTransformer3DModel(StepCacheHost, HeadWindowHost):
             TM("step_cache", sc.end, x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
 
         plan.finish()
+        if ar is not None:
+            ar.finish()
 
         # 4. norm_final over the joint sequence, AdaLayerNorm on the video tokens, proj_out, unpatchify
         _lib.layernorm_modulate(x, y, self.norm_final_w, self.norm_final_b, None, None, 0, N, S, D, T, cfg.norm_eps)

@@ -36,6 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .attn_reuse import AttnReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
 from .transformer_wan import k_scale_bound
 
@@ -148,7 +149,7 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
     return sd
 
 
-class HunyuanVideoTransformer3DModel(HeadWindowHost):
+class HunyuanVideoTransformer3DModel(AttnReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -186,6 +187,13 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
         # attn_window_recall > 0 (opt-in, with attn_window > 0): only the heads whose measured recall (over the latent queries,
         # minimum over the samples) reaches it keep the window (attn_window.HeadWindowHost).  0.0: the shared window, nothing allocated
         self._head_window_init()
+        # N >= 2 (opt-in, an extension: alg_amd/attn_reuse.py): a forward that is handed `cache_keys` with the step's timestep
+        # (attn_reuse.step_keys) computes every block's joint attention on every N-th step while attn_reuse_t_lo < t < attn_reuse_t_hi
+        # and reads its latent and prompt rows back from a per-key cache on the steps between.  Skipped then -- dual blocks: both
+        # streams' norm1, the four Q|K / V projections, the four head norms, the attention; single blocks: Q|K, V^T, the head norms
+        # and the attention (the norm and proj_mlp stay: the MLP half needs them).  0: every forward is the plain one, launch for
+        # launch, nothing allocated.  attn_reuse_drift: the diagnostic (AttnReuseHost)
+        self.attn_reuse = 0
         self.fp8 = bool(fp8)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
@@ -318,7 +326,10 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
     def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8_attention=False, fp8=False,
                         lora=None, **_):
         """Load a diffusers-format checkpoint directory from local disk.  `lora` (as in from_synthetic) is merged into the state
-        dict before the model is built from it; in a multi-rank run every rank merges for itself behind the weight broadcast."""
+        dict before the model is built from it; in a multi-rank run every rank merges for itself behind the weight broadcast.  `attn_reuse`, `attn_reuse_t_lo` and `attn_reuse_t_hi` (taken from the trailing keywords; alg_amd/attn_reuse.py) set the
+        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors."""
+        from .attn_reuse import apply_switches, switches_from
+        reuse = switches_from(_)
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -335,6 +346,7 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
         report = merge_into(sd, lora, device)
         model = cls(cfg, sd, device=device, fp8_attention=fp8_attention, fp8=fp8)
         model.lora_report = report
+        apply_switches(model, reuse)
         return model
 
     def to(self, *a, **k):
@@ -453,7 +465,10 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
             prof.setdefault("attn_self", []).append((e0, e1))
 
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_attention_mask, pooled_projections,
-                 guidance=None, attention_kwargs=None, return_dict=True):
+                 guidance=None, attention_kwargs=None, return_dict=True, cache_keys=None, cache_force=False):
+        """cache_keys (one hashable per sample, naming the role of its pass, as an attn_reuse.StepKeys that carries the step's
+        timestep) names the samples' attention-cache entries when `attn_reuse` >= 2; cache_force computes this forward (and
+        rewrites them) whatever the schedule says (the first and the last step of a schedule, a calibration forward)."""
         cfg, w, G, T = self.config, self.w, _lib.gemm, self._timed
         if hidden_states.device.type != "cuda":
             raise _lib.AlgHipError("HunyuanVideoTransformer3DModel needs device tensors; there is no CPU fallback")
@@ -565,6 +580,11 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                                      profile_of=lambda b, ws_: self._profile_table(F_, first, ws_, (valid[b], J),
                                                                                    tail=(S, S + valid[b]), rows=J))
         attention = lambda bi: self._joint_attention(ws, plan, bi, valid, S, scale)
+        # attention reuse (alg_amd/attn_reuse.py): None -- off, nothing below differs from the plain forward.  An entry holds the J
+        # joint rows (latents, then prompt) of every block; att_rows: their place in the front columns of ws.am, per sample
+        ar = self._attn_reuse_begin(cache_keys, cache_force, N, len(self.dual) + len(self.single), J, D)
+        reuse = ar is not None and ar.reuse
+        att_rows = [ws.am[n, :, :D] for n in range(N)] if ar is not None else None
 
         def ada(lin_, rows_in, out, n_out, two):
             """AdaLN linear on silu(emb): `two` -> both embeddings of every sample ([N][2][n_out]), else temb only."""
@@ -611,43 +631,48 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
             mv = ws.mod
             ada(Lw.ada_c, ws.semb1, ws.modc, 6 * D, False)
             # shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp at +0, +D, ... of every 6D vector
-            if fp8:
-                norm8(S, mv, mod_bs, seg, D, 0)
+            if reuse:   # attn_reuse: the cached joint rows stand in for both streams' norm1, projections, head norms and the attention
+                T("attn_reuse", ar.load, bi, att_rows)
             else:
-                T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, mv, mv, mod_bs, seg, N, S, D, split, 1e-6,
-                  x_bstride=J * D, y_bstride=J * D, scale_off=D, shift_off=0)
-            _lib.layernorm_modulate_seg(ws.x, ws.y, None, None, ws.modc, ws.modc, 6 * D, 0, N, L, D, 0, 1e-6,
-                                        x_bstride=J * D, y_bstride=J * D, x_off=S * D, y_off=S * D, scale_off=D, shift_off=0)
-            if fp8:
-                lin8("gemm_qk", Lw.wqk8, ws.qk, S, 2 * D, D, 2 * D, bias=Lw.bqk, strideC=J * 2 * D)
-            else:
-                T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, S, 2 * D, D, D, D, 2 * D, bias=Lw.bqk, batch=N, strideA=J * D, strideC=J * 2 * D)
-            G(ws.y, Lw.wqk_c, ws.qk, L, 2 * D, D, D, D, 2 * D, bias=Lw.bqk_c, batch=N, strideA=J * D, strideC=J * 2 * D,
-              a_off=S * D, c_off=S * 2 * D)
-            if fp8:
-                vt8(Lw.v8, Lw.v[1], S)
-            else:
-                T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, S, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
-                  strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
-            G(Lw.v_c[0], ws.y, ws.vt, D, L, D, D, D, ws.J_pad, bias=Lw.v_c[1], batch=N, strideB=J * D,
-              strideC=D * ws.J_pad, b_off=S * D, perm_col0=S, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
-            # latent rows: norm_q / norm_k + rope; prompt rows: norm_added_q / norm_added_k, no rope
-            if f8:   # the same four norms, writing e4m3 Q | K (and the Q scales) instead of updating ws.qk
-                qkb, sb, hs = J * 2 * D, J * heads, bi * N * heads
-                T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, qkb, N, S, heads, S, 1e-6, ws.a8, 2 * D, qkb, scale=ws.a8s,
-                  scale_bstride=sb)
-                T("headnorm_rope", H8, ws.qk, Lw.nk, cos, sin, 2 * D, qkb, N, S, heads, S, 1e-6, ws.a8, 2 * D, qkb, head_scale=ws.k8s,
-                  hs_off=hs, x_off=D, q8_off=D)
-                H8(ws.qk, Lw.nq_c, None, None, 2 * D, qkb, N, L, heads, 0, 1e-6, ws.a8, 2 * D, qkb, scale=ws.a8s, scale_bstride=sb,
-                   x_off=S * 2 * D, q8_off=S * 2 * D, scale_off=S * heads)
-                H8(ws.qk, Lw.nk_c, None, None, 2 * D, qkb, N, L, heads, 0, 1e-6, ws.a8, 2 * D, qkb, head_scale=ws.k8s, hs_off=hs,
-                   x_off=S * 2 * D + D, q8_off=S * 2 * D + D)
-            else:
-                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6)
-                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6, x_off=D)
-                _lib.headnorm_rope_(ws.qk, Lw.nq_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D)
-                _lib.headnorm_rope_(ws.qk, Lw.nk_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D + D)
-            attention(bi)
+                if fp8:
+                    norm8(S, mv, mod_bs, seg, D, 0)
+                else:
+                    T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, mv, mv, mod_bs, seg, N, S, D, split, 1e-6,
+                      x_bstride=J * D, y_bstride=J * D, scale_off=D, shift_off=0)
+                _lib.layernorm_modulate_seg(ws.x, ws.y, None, None, ws.modc, ws.modc, 6 * D, 0, N, L, D, 0, 1e-6,
+                                            x_bstride=J * D, y_bstride=J * D, x_off=S * D, y_off=S * D, scale_off=D, shift_off=0)
+                if fp8:
+                    lin8("gemm_qk", Lw.wqk8, ws.qk, S, 2 * D, D, 2 * D, bias=Lw.bqk, strideC=J * 2 * D)
+                else:
+                    T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, S, 2 * D, D, D, D, 2 * D, bias=Lw.bqk, batch=N, strideA=J * D, strideC=J * 2 * D)
+                G(ws.y, Lw.wqk_c, ws.qk, L, 2 * D, D, D, D, 2 * D, bias=Lw.bqk_c, batch=N, strideA=J * D, strideC=J * 2 * D,
+                  a_off=S * D, c_off=S * 2 * D)
+                if fp8:
+                    vt8(Lw.v8, Lw.v[1], S)
+                else:
+                    T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, S, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
+                      strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+                G(Lw.v_c[0], ws.y, ws.vt, D, L, D, D, D, ws.J_pad, bias=Lw.v_c[1], batch=N, strideB=J * D,
+                  strideC=D * ws.J_pad, b_off=S * D, perm_col0=S, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+                # latent rows: norm_q / norm_k + rope; prompt rows: norm_added_q / norm_added_k, no rope
+                if f8:   # the same four norms, writing e4m3 Q | K (and the Q scales) instead of updating ws.qk
+                    qkb, sb, hs = J * 2 * D, J * heads, bi * N * heads
+                    T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, qkb, N, S, heads, S, 1e-6, ws.a8, 2 * D, qkb, scale=ws.a8s,
+                      scale_bstride=sb)
+                    T("headnorm_rope", H8, ws.qk, Lw.nk, cos, sin, 2 * D, qkb, N, S, heads, S, 1e-6, ws.a8, 2 * D, qkb, head_scale=ws.k8s,
+                      hs_off=hs, x_off=D, q8_off=D)
+                    H8(ws.qk, Lw.nq_c, None, None, 2 * D, qkb, N, L, heads, 0, 1e-6, ws.a8, 2 * D, qkb, scale=ws.a8s, scale_bstride=sb,
+                       x_off=S * 2 * D, q8_off=S * 2 * D, scale_off=S * heads)
+                    H8(ws.qk, Lw.nk_c, None, None, 2 * D, qkb, N, L, heads, 0, 1e-6, ws.a8, 2 * D, qkb, head_scale=ws.k8s, hs_off=hs,
+                       x_off=S * 2 * D + D, q8_off=S * 2 * D + D)
+                else:
+                    T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6)
+                    T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, S, heads, S, 1e-6, x_off=D)
+                    _lib.headnorm_rope_(ws.qk, Lw.nq_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D)
+                    _lib.headnorm_rope_(ws.qk, Lw.nk_c, None, None, 2 * D, J * 2 * D, N, L, heads, 0, 1e-6, x_off=S * 2 * D + D)
+                attention(bi)
+                if ar is not None:
+                    T("attn_reuse", ar.store, bi, att_rows)
             if fp8:
                 quant8(S, D, 0)
                 lin8("gemm_out", Lw.o8, ws.x, S, D, D, D, bias=Lw.o[1], R=ws.x, ldr=D, gate=mv, gate_off=2 * D, strideGate=mod_bs,
@@ -695,24 +720,31 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
             if fp8:   # one norm over the joint rows feeds proj_mlp, Q|K and V^T
                 norm8(J, ws.mod, smod_bs, sseg, D, 0)
                 lin8("gemm_ff1", Lw.mlp8, ws.am, J, M, D, AM, bias=Lw.mlp[1], act=_lib.ACT_GELU_TANH, strideC=J * AM, c_off=D)
-                lin8("gemm_qk", Lw.wqk8, ws.qk, J, 2 * D, D, 2 * D, bias=Lw.bqk, strideC=J * 2 * D)
-                vt8(Lw.v8, Lw.v[1], J)
+                if not reuse:
+                    lin8("gemm_qk", Lw.wqk8, ws.qk, J, 2 * D, D, 2 * D, bias=Lw.bqk, strideC=J * 2 * D)
+                    vt8(Lw.v8, Lw.v[1], J)
             else:
                 T("ln_mod", _lib.layernorm_modulate_seg, ws.x, ws.y, None, None, ws.mod, ws.mod, smod_bs, sseg, N, J, D, split, 1e-6,
                   scale_off=D, shift_off=0)
                 T("gemm_ff1", G, ws.y, PK(Lw, Lw.mlp[0]), ws.am, N * J, M, D, D, D, AM, bias=Lw.mlp[1], act=_lib.ACT_GELU_TANH, c_off=D)
-                T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, N * J, 2 * D, D, D, D, 2 * D, bias=Lw.bqk)
-                T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, J, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
-                  strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
-            if f8:
-                T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
-                  scale=ws.a8s, scale_bstride=J * heads)
-                T("headnorm_rope", H8, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
-                  head_scale=ws.k8s, hs_off=bi * N * heads, x_off=D, q8_off=D)
+                if not reuse:
+                    T("gemm_qk", G, ws.y, PK(Lw, Lw.wqk), ws.qk, N * J, 2 * D, D, D, D, 2 * D, bias=Lw.bqk)
+                    T("gemm_vt", G, Lw.v[0], ws.y, ws.vt, D, J, D, D, D, ws.J_pad, bias=Lw.v[1], batch=N, strideB=J * D,
+                      strideC=D * ws.J_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+            if reuse:   # attn_reuse: the cached attention columns go in front of gelu(mlp) in the [attention | gelu(mlp)] buffer
+                T("attn_reuse", ar.load, bi, att_rows)
             else:
-                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6)
-                T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, x_off=D)
-            attention(bi)
+                if f8:
+                    T("headnorm_rope", H8, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
+                      scale=ws.a8s, scale_bstride=J * heads)
+                    T("headnorm_rope", H8, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, ws.a8, 2 * D, J * 2 * D,
+                      head_scale=ws.k8s, hs_off=bi * N * heads, x_off=D, q8_off=D)
+                else:
+                    T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nq, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6)
+                    T("headnorm_rope", _lib.headnorm_rope_, ws.qk, Lw.nk, cos, sin, 2 * D, J * 2 * D, N, J, heads, S, 1e-6, x_off=D)
+                attention(bi)
+                if ar is not None:
+                    T("attn_reuse", ar.store, bi, att_rows)
             if fp8:   # the whole [attention | gelu(mlp)] row, ONE scale per token
                 quant8(J, AM, 0)
                 lin8("gemm_out_mlp", Lw.out8, ws.x, J, D, AM, D, bias=Lw.out[1], R=ws.x, ldr=D, gate=ws.mod, gate_off=2 * D,
@@ -723,6 +755,8 @@ class HunyuanVideoTransformer3DModel(HeadWindowHost):
                   strideR=J * D)
 
         plan.finish()
+        if ar is not None:
+            ar.finish()
 
         # ---- output head: AdaLayerNormContinuous (scale | shift), projection, unpatchify ----
         G(ws.semb1, w.ada_out[0], ws.mod_out, N, 2 * D, D, D, D, 2 * D, bias=w.ada_out[1])

@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention, position_band_ranges
+from .attn_reuse import AttnReuseHost
 from .step_cache import StepCacheHost
 
 BF = torch.bfloat16
@@ -153,7 +154,7 @@ def k_scale_bound(norm_weight, norm_dim, heads, rope):
     return (w * (1.02 * math.sqrt(norm_dim * (2.0 if rope else 1.0)) / 448.0)).contiguous()
 
 
-class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
+class WanTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -182,6 +183,12 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         # on the last computed forward.  0.0: every forward is the plain one, launch for launch.
         self.step_cache = 0.0
         self.step_cache_max_consecutive = 0   # at most this many skipped forwards in a row (0: no cap)
+        # N >= 2 (opt-in, an extension: alg_amd/attn_reuse.py): a forward that is handed `cache_keys` with the step's timestep
+        # (attn_reuse.step_keys) computes every block's SELF-attention on every N-th step while attn_reuse_t_lo < t < attn_reuse_t_hi
+        # and reads it back from a per-key cache on the steps between, skipping the first ln_mod, Q|K / V^T, both rms_rope and attn1 in
+        # whatever form it runs; the cross-attention and the feed-forward run as ever.  0: every forward is the plain one, launch
+        # for launch, nothing allocated.  attn_reuse_drift: the diagnostic (AttnReuseHost)
+        self.attn_reuse = 0
         # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): the self-attention of every block
         # attends to the conditioning frames (attn_sink_frames) and to the latent frames within attn_window of the query block's
         # own, as ONE alg_flash_attn_d128_ranges launch for the whole batch.  0: today's launches, nothing allocated
@@ -296,7 +303,10 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                         lora=None, **_):
         """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk.  `lora` (as in
         from_synthetic) is merged into the state dict before the model is built from it; in a multi-rank run every rank merges
-        for itself behind the weight broadcast."""
+        for itself behind the weight broadcast.  `attn_reuse`, `attn_reuse_t_lo` and `attn_reuse_t_hi` (taken from the trailing keywords; alg_amd/attn_reuse.py) set the
+        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors."""
+        from .attn_reuse import apply_switches, switches_from
+        reuse = switches_from(_)
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -312,6 +322,7 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
         report = merge_into(sd, lora, device)
         model = cls(cfg, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
         model.lora_report = report
+        apply_switches(model, reuse)
         return model
 
     def to(self, *args, **kwargs):
@@ -471,7 +482,9 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
     def __call__(self, hidden_states, timestep, encoder_hidden_states, encoder_hidden_states_image=None,
                  attention_kwargs=None, return_dict=True, cache_keys=None, cache_force=False):
         """cache_keys (one hashable per sample, naming the role of its pass) arms the step cache when `step_cache` > 0;
-        cache_force computes this forward whatever the probe says (the last step of a schedule)."""
+        cache_force computes this forward whatever the probe says (the last step of a schedule).  With `attn_reuse` >= 2 the same
+        keys, as an attn_reuse.StepKeys that carries the step's timestep, name the samples' attention-cache entries, and
+        cache_force computes (and rewrites them) whatever the schedule says."""
         cfg, w, G, T = self.config, self.w, _lib.gemm, self._timed
         if hidden_states.device.type != "cuda":
             raise _lib.AlgHipError("WanTransformer3DModel needs device tensors; there is no CPU fallback")
@@ -550,6 +563,8 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
 
         use_packed = not self.fp8 and self.packed_weights and os.environ.get("ALG_GEMM_PIPE", "10") == "10"
         packed = None
+        # attention reuse (alg_amd/attn_reuse.py): None -- off, nothing below differs from the plain forward; refused next to a step cache
+        ar = self._attn_reuse_begin(cache_keys, cache_force, N, len(self.blocks), S, D)
         sc = self._step_cache_begin(ws.x, cache_keys, cache_force, 0, S)   # None: off, nothing below differs from the plain forward
         kvr = self._window_ranges(F_, S // F_) if self.attn_window else None    # None: the dense launch
         # attn_band validated (needs the recall policy, excludes the widths); 0: off -- also on a forward the sampler runs with the
@@ -568,29 +583,34 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
                 packed = {id(getattr(L, name)): pw for name, pw in L.packed.items()}
             m0 = li * N * 6 * D  # element offset of this block's [N, 6, D] modulation: shift, scale, gate, c_shift, c_scale, c_gate
             # ---- self-attention ----
-            ln_mod(None, None, ws.mod, ws.mod, mod_bs, scale_off=m0 + D, shift_off=m0)
-            vt_kw = dict(bias=L.bv, batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
-            if self.fp8:
-                lin("gemm_qk", ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, 2 * D, requant=not fuse_q, bias=L.bqk)
-                # V^T: the weight is the A operand, the (already quantised) tokens are B
-                T("gemm_vt", G, L.wv[0], ws.q8, ws.vt, D, S, D, D, D, S_pad, a_scale=L.wv[1], b_scale=ws.q8s, strideBScale=S, **vt_kw)
-            elif self.pair_qkv:   # both projections read y: one persistent launch (alg_gemm_bf16_pair), bit-identical
-                T("gemm_qkv", _lib.gemm_pair, ((ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, D, 2 * D), dict(bias=L.bqk)),
-                  ((L.wv, ws.y, ws.vt, D, S, D, D, D, S_pad), vt_kw))
+            if ar is not None and ar.reuse:   # attn_reuse: the cached attention output stands in for everything up to it
+                T("attn_reuse", ar.load, li, ws.att)
             else:
-                lin("gemm_qk", ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, 2 * D, bias=L.bqk)
-                T("gemm_vt", G, L.wv, ws.y, ws.vt, D, S, D, D, D, S_pad, **vt_kw)
-            if self.fp8_attention:   # e4m3 Q | K straight out of the norm, V^T per row, attention on the fp8 MFMA
-                T("rms_rope", _lib.rmsnorm_rope_fp8, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps, ws.a8, 2 * D, scale=ws.a8s)
-                T("rms_rope", _lib.rmsnorm_rope_fp8, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, ws.a8, 2 * D,
-                  head_scale=ws.k8s, hs_off=li * N * heads, x_off=D, q8_off=D)
-                T("vt_quant", _lib.quantize_fp8_vt, ws.vt, ws.vt8, ws.vt8s, N, D, S, D * S_pad, S_pad, D * S_pad, S_pad)
-                T("attn_self", _lib.flash_attn_d128_fp8, ws.a8, ws.a8s, ws.a8, ws.k8s, ws.vt8, ws.vt8s, ws.att, N, heads, S, S,
-                  S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D, ks_off=li * N * heads)
-            else:
-                T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
-                T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
-                self._self_attention(T, ws, plan, li, band_t, N, F_, S, scale)
+                ln_mod(None, None, ws.mod, ws.mod, mod_bs, scale_off=m0 + D, shift_off=m0)
+                vt_kw = dict(bias=L.bv, batch=N, strideB=S * D, strideC=D * S_pad, flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)
+                if self.fp8:
+                    lin("gemm_qk", ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, 2 * D, requant=not fuse_q, bias=L.bqk)
+                    # V^T: the weight is the A operand, the (already quantised) tokens are B
+                    T("gemm_vt", G, L.wv[0], ws.q8, ws.vt, D, S, D, D, D, S_pad, a_scale=L.wv[1], b_scale=ws.q8s, strideBScale=S, **vt_kw)
+                elif self.pair_qkv:   # both projections read y: one persistent launch (alg_gemm_bf16_pair), bit-identical
+                    T("gemm_qkv", _lib.gemm_pair, ((ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, D, 2 * D), dict(bias=L.bqk)),
+                      ((L.wv, ws.y, ws.vt, D, S, D, D, D, S_pad), vt_kw))
+                else:
+                    lin("gemm_qk", ws.y, L.wqk, ws.qk, N * S, 2 * D, D, D, 2 * D, bias=L.bqk)
+                    T("gemm_vt", G, L.wv, ws.y, ws.vt, D, S, D, D, D, S_pad, **vt_kw)
+                if self.fp8_attention:   # e4m3 Q | K straight out of the norm, V^T per row, attention on the fp8 MFMA
+                    T("rms_rope", _lib.rmsnorm_rope_fp8, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps, ws.a8, 2 * D, scale=ws.a8s)
+                    T("rms_rope", _lib.rmsnorm_rope_fp8, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, ws.a8, 2 * D,
+                      head_scale=ws.k8s, hs_off=li * N * heads, x_off=D, q8_off=D)
+                    T("vt_quant", _lib.quantize_fp8_vt, ws.vt, ws.vt8, ws.vt8s, N, D, S, D * S_pad, S_pad, D * S_pad, S_pad)
+                    T("attn_self", _lib.flash_attn_d128_fp8, ws.a8, ws.a8s, ws.a8, ws.k8s, ws.vt8, ws.vt8s, ws.att, N, heads, S, S,
+                      S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad, S * D, D, scale, k_off=D, ks_off=li * N * heads)
+                else:
+                    T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nq, cos, sin, 2 * D, N, S, D, cfg.eps)
+                    T("rms_rope", _lib.rmsnorm_rope_, ws.qk, L.nk, cos, sin, 2 * D, N, S, D, cfg.eps, x_off=D)
+                    self._self_attention(T, ws, plan, li, band_t, N, F_, S, scale)
+                if ar is not None:
+                    T("attn_reuse", ar.store, li, ws.att)
             lin("gemm_out", ws.att, L.wo, ws.x, S, D, D, D, D, bias=L.bo, R=ws.x, ldr=D, gate=ws.mod,
                 gate_off=m0 + 2 * D, strideGate=mod_bs, batch=N, strideA=S * D, strideC=S * D, strideR=S * D,
                 seg_split=1 << 30, flags=_lib.GEMM_GATE_F32)
@@ -637,6 +657,8 @@ class WanTransformer3DModel(StepCacheHost, HeadWindowHost):
             T("step_cache", sc.end, ws.x)   # computed forward: tail <- x - x1 (a no-op behind a hit)
 
         plan.finish(band_table=band_t)
+        if ar is not None:
+            ar.finish()
 
         # ---- output head ----
         _lib.layernorm_mod_f32(ws.x, ws.y, None, None, ws.mod_out, ws.mod_out, 2 * D, N, S, D, cfg.eps, scale_off=D,

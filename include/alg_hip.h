@@ -159,6 +159,18 @@ int64_t alg_step_cache_workspace_bytes(int rows, int D);
 int alg_step_cache_probe(void* keep, const void* x1, void* r, int rows, int D, int tok0, int tok_rows, void* workspace,
                          double* sums, void* stream);
 
+/* Attention-reuse drift (an extension: alg_amd/attn_reuse.py) -- how far a layer's attention output moved from its cached copy.
+ * a (new), b (cached): bf16 [rows][cols], row strides in ELEMENTS (multiples of 8, at least cols), cols % 8 == 0, 16-byte aligned.
+ *   out[0] = sum |float(a) - float(b)|,  out[1] = sum |float(b)|
+ * DEVICE doubles, deterministic (no atomics: eight fp32 terms per 16-byte vector, everything above in double in a fixed order
+ * that depends on (rows, cols) alone: a capped grid with a grid-stride loop, one partial pair per block into `work`, a second
+ * launch of one block sums them).  A NaN in a reaches out[0] only.  work: alg_attn_drift_workspace_bytes(rows, cols) bytes,
+ * 8-byte aligned.  rows == 0 writes zeros (a and b are not read then and may be null).  Bytes between cols and a row stride are
+ * not read.  Every refusal is ALG_EINVAL before anything is launched. */
+int64_t alg_attn_drift_workspace_bytes(int rows, int cols);
+int alg_attn_drift(const void* a, const void* b, int rows, int cols, int64_t a_rstride, int64_t b_rstride, void* work, double* out,
+                   void* stream);
+
 /* LoRA merge at load time (an extension; the reference pipelines inherit diffusers' LoRA loader mixins; alg_amd/lora.py merges
  * the adapters into the state dict BEFORE a transformer is built from it, so no forward path knows about them):
  *   t[n, r]   = double(scale[r]) * double(B[n, r])                exact
