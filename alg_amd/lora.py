@@ -213,3 +213,12 @@ def merge_into(state_dict, specs, device="cuda"):
             w = w.contiguous()
         state_dict[it.key] = _lib.lora_merge(w, it.a.to(dev), it.b.to(dev), it.scale.to(dev))
     return report
+
+
+def build(cls, config, state_dict, lora, device, **ctor_kw):
+    """cls(config, state_dict, device=device, **ctor_kw) with the adapters of `lora` merged into `state_dict` first (merge_into,
+    in place); the report is the model's `lora_report`."""
+    report = merge_into(state_dict, lora, device)
+    model = cls(config, state_dict, device=device, **ctor_kw)
+    model.lora_report = report
+    return model

@@ -21,7 +21,6 @@ they are absent the caller passes ``prompt_embeds`` / ``negative_prompt_embeds``
 """
 from __future__ import annotations
 
-import functools
 import inspect
 import math
 from dataclasses import dataclass
@@ -29,7 +28,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import _lib, attn_reuse, attn_window, lp_utils, step_cache
+from . import _lib, attn_reuse, lp_utils, sampler_ext
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler
 from .transformer_cogvideox import CogVideoXTransformer3DModel
 
@@ -138,33 +137,18 @@ class CogVideoXImageToVideoPipeline:
         exists and no instance was passed in.  Without a text encoder the call needs `prompt_embeds`, without a VAE
         `image_latents` and `output_type="latent"`.  `fp8=True` loads the transformer with e4m3 block linears
         (CogVideoXTransformer3DModel(..., fp8=True)); `fp4=True` with MXFP4 feed-forward
-        linears (CogVideoXTransformer3DModel(..., fp4=True)); neither has an effect on a transformer instance passed in.  `step_cache` > 0
-        switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default), `attn_window` > 0
-        its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by default);
-        `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost) and needs
-        `attn_window` > 0 (ValueError otherwise); `attn_window_balance` (True = "units", "lanes", "units"; needs
-        attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
-        order (attn_window.balanced_order), bit-identical output.  `attn_window_widths` (the per-head window WIDTH of the
-        head_dim 128 models) is refused: ValueError.  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
-        transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
-        like `fp8` it has no effect on a transformer instance passed in.  `attn_reuse` (an int, 0 = off, N >= 2; 1 is a ValueError), `attn_reuse_t_lo` = 100 and
-        `attn_reuse_t_hi` = 800 (lo >= hi is a ValueError) switch the transformer's attention reuse across steps on
-        (alg_amd/attn_reuse.py; off by default); like `fp8` they go to the transformer loader and have no effect on a transformer
-        instance passed in.  (They are taken from the trailing keywords: the order of the named ones is pinned.)"""
+        linears (CogVideoXTransformer3DModel(..., fp4=True)); neither has an effect on a transformer instance passed in.
+        `step_cache` (a threshold), `attn_window` (latent frames on each side), `attn_window_recall` (needs attn_window > 0 here)
+        and `attn_window_balance` set the transformer's attributes of these names, also on an instance passed in; all are off by
+        default, `attn_window_widths` (head_dim 128 only) is refused, and sampler_ext.window_switches raises ValueError for what
+        does not compose before anything is loaded.  `lora` (alg_amd/lora.py) and, from the trailing keywords (the order of the
+        named ones is pinned), `attn_reuse`, `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) go to the transformer
+        loader: like `fp8` they have no effect on a transformer instance passed in."""
         import os
 
-        from .attn_window import _balance_policy
-
         reuse_kw = attn_reuse.switches_from(_)
-        if attn_window_widths is not None:
-            raise ValueError("attn_window_widths=%r: the per-head window width (one-pass calibration) is not built for head_dim 64"
-                             % (attn_window_widths,))
-        if attn_window_recall and not int(attn_window) > 0:
-            raise ValueError("attn_window_recall=%r needs attn_window > 0: the recall is that of a frame window" % (attn_window_recall,))
-        _balance_policy(attn_window_balance)
-        if attn_window_balance and not attn_window_recall:
-            raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
-                             "windowed heads" % (attn_window_balance,))
+        switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths,
+                                               step_cache=step_cache, widths_built=False, recall_needs_window=True)
 
         from .autoencoder_kl_cogvideox import AutoencoderKLCogVideoX
         from .text_encoder_t5 import T5EncoderModel
@@ -175,14 +159,7 @@ class CogVideoXImageToVideoPipeline:
             transformer = CogVideoXTransformer3DModel.from_pretrained(model_path, torch_dtype=torch_dtype,
                                                                       device=device, fp8=fp8, fp4=fp4, lora=lora,
                                                                       **reuse_kw)
-        if step_cache:
-            transformer.step_cache = float(step_cache)
-        if attn_window:
-            transformer.attn_window = int(attn_window)
-        if attn_window_recall:
-            transformer.attn_window_recall = float(attn_window_recall)
-        if attn_window_balance:
-            transformer.attn_window_balance = attn_window_balance
+        sampler_ext.apply_switches(transformer, switches)
         if vae is None and has("vae"):
             vae = AutoencoderKLCogVideoX.from_pretrained(model_path, device=device)
         if text_encoder is None and has("text_encoder"):
@@ -583,24 +560,9 @@ class CogVideoXImageToVideoPipeline:
         old_pred_original_sample = None  # cog:998
 
         B = latents.shape[0]
-        # the transformer's opt-in step cache (alg_amd/step_cache.py): a new video starts from an empty cache, every forward names
-        # the roles of its passes, the last step is always computed.  Transformers without the switch are called as ever.
-        use_cache = step_cache.active(self.transformer)
-        if use_cache:
-            if cfg_split is not None:
-                raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
-                                       "passes and leave the single-GPU result; run one of the two")
-            self.transformer.reset_step_cache()
-        # the transformer's opt-in attention reuse (alg_amd/attn_reuse.py): a new video starts from an empty cache, every forward names
-        # the roles of its passes and its timestep, the first and the last step are always computed
-        use_reuse = attn_reuse.begin_video(self.transformer, cfg_split)
-        # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
-        use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
-        if use_recall:
-            if cfg_split is not None:
-                raise _lib.AlgHipError("attn_window_recall > 0 with cfg_split: the two ranks of a CFG pair would decide the windowed "
-                                       "heads on different passes; run one of the two")
-            self.transformer.reset_attn_window_heads()
+        # the transformer's opt-in extensions (alg_amd/sampler_ext.py): refusals and resets here, one callable per step below
+        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps, cfg_split,
+                                            forward=self.transformer.forward_assembled, host_timestep=int)
         # every timestep of the schedule on the device ONCE: a step takes a view of it (no host tensor + H2D copy per step)
         ts_dev = torch.as_tensor([int(t_) for t_ in timesteps], dtype=torch.float32).to(device)
         for i, t in enumerate(timesteps):
@@ -650,10 +612,7 @@ class CogVideoXImageToVideoPipeline:
             conds = [g[b:b + 1] for g in cond_groups for b in range(B)]
             lat_in = latents if B == 1 else torch.cat([latents] * n_pass, dim=0)
             ts = ts_dev[i:i + 1].expand(n_pass * B)
-            # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
-            dit = functools.partial(attn_window.call_transformer, self.transformer, i < attn_window_dense_steps,
-                                    forward=self.transformer.forward_assembled,
-                                    calibrate=bool(use_recall) and i == attn_window.calibration_step(attn_window_dense_steps))
+            dit = ext.step(i, t, n_pass, B)
             if cfg_split is not None and n_pass > 1:
                 # alg_amd.parallel.CFGPairSplit: this rank evaluates its share of the CFG passes, one all-gather merges
                 # the predictions; combine + step below run identically on both ranks of the pair
@@ -662,12 +621,7 @@ class CogVideoXImageToVideoPipeline:
                 local = dit(lat_l, [conds[r] for r in rows], embeds[rows].contiguous(), ts[:len(rows)], image_rotary_emb, ofs=ofs_emb)
                 noise_pred = cfg_split.merge(local, n_pass, B)
             else:
-                cache_kw = dict(cache_keys=step_cache.pass_keys(n_pass, B), cache_force=i == len(timesteps) - 1) if use_cache else {}
-                if use_reuse:
-                    self.transformer.attn_reuse_advance()
-                    cache_kw = dict(cache_keys=attn_reuse.step_keys(n_pass, B, int(t)),
-                                    cache_force=i == len(timesteps) - 1 or not self.transformer.attn_reuse_stats)
-                noise_pred = dit(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb, **cache_kw)
+                noise_pred = dit(lat_in, conds, embeds, ts, image_rotary_emb, ofs=ofs_emb)
             gs = guidance_scale
             if do_cfg and not use_low_pass_guidance and use_dynamic_cfg:  # cog:1105-1108
                 gs = 1 + guidance_scale * (

@@ -29,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from . import _lib, attn_reuse, attn_window, lp_utils
+from . import _lib, attn_reuse, lp_utils, sampler_ext
 from .pipeline_cogvideox_image2video_lowpass import retrieve_timesteps
 from .schedulers import FlowMatchEulerDiscreteScheduler
 
@@ -126,36 +126,16 @@ class HunyuanVideoImageToVideoPipeline:
         `text_encoder/` (Llava-Llama-3) + `tokenizer/` + `image_processor/`, `text_encoder_2/` (CLIP-L text tower) +
         `tokenizer_2/`, `vae/`, `scheduler/`.  `fp8=True` loads the transformer with e4m3 block linears
         (HunyuanVideoTransformer3DModel(..., fp8=True)); it has no effect on a transformer instance passed in.
-        `attn_window` > 0 switches the transformer's frame-window joint attention on with that many latent frames on each side
-        (alg_amd/attn_window.py; off by default); `attn_window_recall` > 0 keeps that window only on the heads whose measured
-        recall reaches it (attn_window.HeadWindowHost); `attn_window_balance` (True = "units", "lanes", "units"; needs
-        attn_window_recall > 0, ValueError otherwise) launches the layers with dense and windowed heads in a coverage-balanced
-        order (attn_window.balanced_order), bit-identical output; `attn_window_widths`
-        (a strictly ascending tuple of positive ints ending in attn_window, or "1,2,4"; needs attn_window_recall > 0, ValueError
-        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration.  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
-        transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
-        like `fp8` it has no effect on a transformer instance passed in.  `attn_reuse` (an int, 0 = off, N >= 2; 1 is a ValueError), `attn_reuse_t_lo` = 100 and
-        `attn_reuse_t_hi` = 800 (lo >= hi is a ValueError) switch the transformer's attention reuse across steps on
-        (alg_amd/attn_reuse.py; off by default); like `fp8` they go to the transformer loader and have no effect on a transformer
-        instance passed in.  (They are taken from the trailing keywords: the order of the named ones is pinned.)"""
+        `attn_window` (latent frames on each side), `attn_window_recall`, `attn_window_balance` and `attn_window_widths` set the
+        transformer's attributes of these names, also on an instance passed in; all are off by default, and
+        sampler_ext.window_switches refuses (ValueError) what does not compose before anything is loaded.  `lora`
+        (alg_amd/lora.py) and, from the trailing keywords (the order of the named ones is pinned), `attn_reuse`,
+        `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) go to the transformer loader: like `fp8` they have no
+        effect on a transformer instance passed in."""
         import os
 
         reuse_kw = attn_reuse.switches_from(_)
-
-        from .attn_window import _balance_policy
-        _balance_policy(attn_window_balance)
-        if attn_window_balance and not attn_window_recall:
-            raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
-                             "windowed heads" % (attn_window_balance,))
-        if attn_window_widths is not None:
-            from .attn_window import _widths_tuple
-            attn_window_widths = _widths_tuple(attn_window_widths, "attn_window_widths")
-            if attn_window_widths[-1] != int(attn_window):
-                raise ValueError("attn_window_widths %r: the last (largest) width must equal attn_window = %d"
-                                 % (attn_window_widths, int(attn_window)))
-            if not float(attn_window_recall) > 0.0:
-                raise ValueError("attn_window_widths=%r needs attn_window_recall > 0: the width of a head is the narrowest that "
-                                 "reaches the recall" % (attn_window_widths,))
+        switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths)
 
         from .schedulers import FlowMatchEulerDiscreteScheduler
         from .text_encoder_clip import CLIPTextModel
@@ -166,14 +146,7 @@ class HunyuanVideoImageToVideoPipeline:
         if transformer is None:
             transformer = HunyuanVideoTransformer3DModel.from_pretrained(model_path, device=device, fp8_attention=fp8_attention,
                                                                          fp8=fp8, lora=lora, **reuse_kw)
-        if attn_window:
-            transformer.attn_window = int(attn_window)
-        if attn_window_recall:
-            transformer.attn_window_recall = float(attn_window_recall)
-        if attn_window_balance:
-            transformer.attn_window_balance = attn_window_balance
-        if attn_window_widths is not None:
-            transformer.attn_window_widths = attn_window_widths
+        sampler_ext.apply_switches(transformer, switches)
         if text_encoder is None and has("text_encoder"):
             from .text_encoder_llava import LlavaForConditionalGeneration
             text_encoder = LlavaForConditionalGeneration.from_pretrained(model_path, device=device)
@@ -582,13 +555,8 @@ class HunyuanVideoImageToVideoPipeline:
 
         neg3 = lambda a, b: torch.cat([a, a, b], dim=0)
         neg2 = lambda a, b: torch.cat([a, b], dim=0)
-        # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
-        use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
-        if use_recall:
-            self.transformer.reset_attn_window_heads()
-        # the transformer's opt-in attention reuse (alg_amd/attn_reuse.py): a new video starts from an empty cache, every forward names
-        # the roles of its passes and its timestep, the first and the last step are always computed
-        use_reuse = attn_reuse.begin_video(self.transformer)
+        # the transformer's opt-in extensions (alg_amd/sampler_ext.py): refusals and resets here, one callable per step below
+        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps)
         for i, t in enumerate(timesteps):
             if self._interrupt:
                 continue
@@ -616,17 +584,10 @@ class HunyuanVideoImageToVideoPipeline:
                 mask = cat(negative_prompt_attention_mask, prompt_attention_mask)
             n = latent_model_input.shape[0]
             timestep = t.expand(n).to(device=device, dtype=tdtype)  # hy:1230 (the timestep itself is cast to bf16)
-            cache_kw = {}
-            if use_reuse:
-                self.transformer.attn_reuse_advance()
-                cache_kw = dict(cache_keys=attn_reuse.step_keys(len(groups), latents.shape[0], float(t)),
-                                cache_force=i == len(timesteps) - 1 or not self.transformer.attn_reuse_stats)
-            # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
-            noise_pred = attn_window.call_transformer(
-                self.transformer, i < attn_window_dense_steps, hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
-                encoder_attention_mask=mask, pooled_projections=pooled, guidance=guidance,
-                attention_kwargs=attention_kwargs, return_dict=False,
-                calibrate=use_recall and i == attn_window.calibration_step(attn_window_dense_steps), **cache_kw)[0]
+            dit = ext.step(i, t, len(groups), latents.shape[0])
+            noise_pred = dit(hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
+                             encoder_attention_mask=mask, pooled_projections=pooled, guidance=guidance,
+                             attention_kwargs=attention_kwargs, return_dict=False)[0]
             # hy:1254-1261 keys the combine on shape[0] (3 -> three chunks, 2 -> two chunks, anything else: none)
             if noise_pred.shape[0] in (2, 3):
                 noise_pred = _lib.cfg_combine(noise_pred.contiguous(), noise_pred.shape[0], true_cfg_scale)

@@ -25,13 +25,12 @@ condition video EVERY step with a freshly sampled posterior) is available.
 """
 from __future__ import annotations
 
-import functools
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, attn_reuse, attn_window, lp_utils, step_cache
+from . import _lib, attn_reuse, lp_utils, sampler_ext
 from .schedulers import UniPCMultistepScheduler
 
 
@@ -109,50 +108,17 @@ class WanImageToVideoPipeline:
                         attn_window_balance=False, attn_window_widths=None, attn_band=0, **_):
         """Local-disk loader of a diffusers-format Wan2.1-I2V directory (`run.py:54-66`): `transformer/`, `text_encoder/`
         (UMT5), `tokenizer/`, `image_encoder/` (CLIP ViT-H), `image_processor/`, `scheduler/` (UniPC), `vae/` (AutoencoderKLWan).
-        `step_cache` > 0 switches the transformer's step cache on with that threshold (alg_amd/step_cache.py; off by default);
-        `attn_window` > 0 its frame-window self-attention with that many latent frames on each side (alg_amd/attn_window.py; off by
-        default); `attn_window_recall` > 0 keeps that window only on the heads whose measured recall reaches it (HeadWindowHost);
-        `attn_window_balance` (True = "units", "lanes", "units"; needs attn_window_recall > 0, ValueError otherwise) launches the
-        layers with dense and windowed heads in a coverage-balanced order (attn_window.balanced_order), bit-identical output; `attn_window_widths`
-        (a strictly ascending tuple of positive ints ending in attn_window, or "1,2,4"; needs attn_window_recall > 0, ValueError
-        otherwise) lets every head take the narrowest of these widths that reaches the recall, from a one-pass calibration;
-        `attn_band` (an int, positions on each side; needs attn_window > 0 and attn_window_recall > 0, not with
-        attn_window_widths or fp8_attention, ValueError otherwise) adds the position-major band as a third candidate per head
-        (transformer.attn_band).  `lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is passed to the
-        transformer loader, which merges the adapters into the state dict before the model is built (transformer.lora_report);
-        like `fp8` it has no effect on a transformer instance passed in.  (`lora` is taken from the trailing keywords: the
-        named keywords end with attn_band.)  `attn_reuse` (an int, 0 = off, N >= 2; 1 is a ValueError), `attn_reuse_t_lo` = 100 and
-        `attn_reuse_t_hi` = 800 (lo >= hi is a ValueError) switch the transformer's attention reuse across steps on
-        (alg_amd/attn_reuse.py; off by default); like `fp8` they go to the transformer loader and have no effect on a transformer
-        instance passed in.  (They are taken from the trailing keywords: the order of the named ones is pinned.)"""
+        `step_cache` (a threshold), `attn_window` (latent frames on each side), `attn_window_recall`, `attn_window_balance`,
+        `attn_window_widths` and `attn_band` set the transformer's attributes of these names, also on an instance passed in; all
+        are off by default, and sampler_ext.window_switches refuses (ValueError) what does not compose before anything is loaded.
+        `lora` (alg_amd/lora.py) and `attn_reuse`, `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) are taken from the
+        trailing keywords -- the named ones end with attn_band, their order is pinned -- and go to the transformer loader: like
+        `fp8` they have no effect on a transformer instance passed in."""
         import os
 
         reuse_kw = attn_reuse.switches_from(_)
-
-        from .attn_window import _balance_policy
-        _balance_policy(attn_window_balance)
-        if attn_window_balance and not attn_window_recall:
-            raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
-                             "windowed heads" % (attn_window_balance,))
-        if attn_window_widths is not None:
-            from .attn_window import _widths_tuple
-            attn_window_widths = _widths_tuple(attn_window_widths, "attn_window_widths")
-            if attn_window_widths[-1] != int(attn_window):
-                raise ValueError("attn_window_widths %r: the last (largest) width must equal attn_window = %d"
-                                 % (attn_window_widths, int(attn_window)))
-            if not float(attn_window_recall) > 0.0:
-                raise ValueError("attn_window_widths=%r needs attn_window_recall > 0: the width of a head is the narrowest that "
-                                 "reaches the recall" % (attn_window_widths,))
-        if attn_band:   # (the transformer's own check, before anything is loaded)
-            from types import SimpleNamespace
-
-            from .attn_window import HeadWindowHost
-            HeadWindowHost._head_window_band(SimpleNamespace(attn_band=attn_band, attn_window=attn_window,
-                                                             attn_window_recall=attn_window_recall,
-                                                             attn_window_widths=attn_window_widths))
-            if fp8_attention:
-                raise ValueError("attn_band=%d does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges"
-                                 % attn_band)
+        switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths, attn_band,
+                                               fp8_attention, step_cache=step_cache)
 
         from .image_encoder_clip import CLIPImageProcessor, CLIPVisionModel
         from .schedulers import UniPCMultistepScheduler
@@ -164,18 +130,7 @@ class WanImageToVideoPipeline:
         if transformer is None:
             transformer = WanTransformer3DModel.from_pretrained(model_path, device=device, fp8=fp8, fp8_attention=fp8_attention,
                                                                 lora=_.get("lora"), **reuse_kw)
-        if attn_band:
-            transformer.attn_band = int(attn_band)
-        if step_cache:
-            transformer.step_cache = float(step_cache)
-        if attn_window:
-            transformer.attn_window = int(attn_window)
-        if attn_window_recall:
-            transformer.attn_window_recall = float(attn_window_recall)
-        if attn_window_balance:
-            transformer.attn_window_balance = attn_window_balance
-        if attn_window_widths is not None:
-            transformer.attn_window_widths = attn_window_widths
+        sampler_ext.apply_switches(transformer, switches)
         if text_encoder is None and has("text_encoder"):
             text_encoder = UMT5EncoderModel.from_pretrained(model_path, device=device)
         if tokenizer is None:
@@ -518,24 +473,8 @@ class WanImageToVideoPipeline:
         latents, condition = self.prepare_latents(image_condition, batch_size * num_videos_per_prompt, z_dim, height,
                                                   width, num_frames, torch.float32, device, generator, latents)
 
-        # the transformer's opt-in step cache (alg_amd/step_cache.py): a new video starts from an empty cache, every forward names
-        # the roles of its passes, the last step is always computed.  Transformers without the switch are called as ever.
-        use_cache = step_cache.active(self.transformer)
-        if use_cache:
-            if cfg_split is not None:
-                raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
-                                       "passes and leave the single-GPU result; run one of the two")
-            self.transformer.reset_step_cache()
-        # the transformer's opt-in attention reuse (alg_amd/attn_reuse.py): a new video starts from an empty cache, every forward names
-        # the roles of its passes and its timestep, the first and the last step are always computed
-        use_reuse = attn_reuse.begin_video(self.transformer, cfg_split)
-        # per-head windows chosen by recall (attn_window_recall > 0): every video is calibrated anew, on its last dense step
-        use_recall = getattr(self.transformer, "attn_window", 0) and getattr(self.transformer, "attn_window_recall", 0.0) > 0.0
-        if use_recall:
-            if cfg_split is not None:
-                raise _lib.AlgHipError("attn_window_recall > 0 with cfg_split: the two ranks of a CFG pair would decide the windowed "
-                                       "heads on different passes; run one of the two")
-            self.transformer.reset_attn_window_heads()
+        # the transformer's opt-in extensions (alg_amd/sampler_ext.py): refusals and resets here, one callable per step below
+        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps, cfg_split)
         for i, t in enumerate(timesteps):
             if self._interrupt or i < self._first_step:
                 continue
@@ -573,9 +512,7 @@ class WanImageToVideoPipeline:
                 raise UnboundLocalError("local variable 'latent_model_input' referenced before assignment "
                                         "(the Wan ALG loop needs guidance_scale > 1)")
             latent_model_input = assemble_channel_concat(latents, groups, tdtype)
-            # the transformer's opt-in frame window (alg_amd/attn_window.py): the first attn_window_dense_steps steps run dense
-            dit = functools.partial(attn_window.call_transformer, self.transformer, i < attn_window_dense_steps,
-                                    calibrate=use_recall and i == attn_window.calibration_step(attn_window_dense_steps))
+            dit = ext.step(i, t, len(groups), latents.shape[0])
             n = latent_model_input.shape[0]
             timestep = t.expand(n).to(device)
             ehs = torch.cat(embeds, dim=0)
@@ -589,15 +526,9 @@ class WanImageToVideoPipeline:
                             attention_kwargs=attention_kwargs, return_dict=False)[0]
                 noise_pred = cfg_split.merge(local.contiguous(), len(groups), B_)
             else:
-                cache_kw = dict(cache_keys=step_cache.pass_keys(len(groups), latents.shape[0]),
-                                cache_force=i == len(timesteps) - 1) if use_cache else {}
-                if use_reuse:
-                    self.transformer.attn_reuse_advance()
-                    cache_kw = dict(cache_keys=attn_reuse.step_keys(len(groups), latents.shape[0], float(t)),
-                                    cache_force=i == len(timesteps) - 1 or not self.transformer.attn_reuse_stats)
                 noise_pred = dit(
                     hidden_states=latent_model_input, timestep=timestep, encoder_hidden_states=ehs,
-                    encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False, **cache_kw)[0]
+                    encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False)[0]
             # wan:919-924 keys the 3-chunk combine on shape[0] == 3, so the reference's 3-pass step only works for one
             # video per call (a [3B, ...] prediction would be chunked in two and fail in the scheduler)
             n_pass = 3 if noise_pred.shape[0] == 3 else 2

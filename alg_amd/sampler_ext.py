@@ -1,0 +1,101 @@
+"""The samplers' side of the transformers' opt-in extensions -- frame window, per-head windows by recall (balance, widths, band),
+step cache, attention reuse -- written once for the three ALG loops.  Plain host code: nothing here launches anything.
+
+    from_pretrained   `window_switches` validates the keywords before anything is loaded, `apply_switches` sets what was given
+    start of a video  `SamplerExtensions(transformer, n_steps, ...)` refuses what does not compose and empties the caches
+    every step        `ext.step(i, t, n_pass, batch)` is the callable the loop uses for the step's forwards
+
+What is refused with what, and which forwards are forced: DESIGN.md ("Sampler extensions")."""
+from __future__ import annotations
+
+import functools
+from types import SimpleNamespace
+
+from . import _lib, attn_reuse
+from . import step_cache as _step_cache
+from .attn_window import HeadWindowHost, _balance_policy, _widths_tuple, calibration_step, call_transformer
+
+
+def window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths, attn_band=0, fp8_attention=False,
+                    *, step_cache=0.0, widths_built=True, recall_needs_window=False):
+    """from_pretrained's window keywords (and `step_cache`, which has no rule of its own) -> {attribute: value} of those that
+    were given, widths as a tuple; ValueError where two do not compose.  widths_built=False, recall_needs_window=True: CogVideoX."""
+    if attn_window_widths is not None and not widths_built:
+        raise ValueError("attn_window_widths=%r: the per-head window width (one-pass calibration) is not built for head_dim 64"
+                         % (attn_window_widths,))
+    if recall_needs_window and attn_window_recall and not int(attn_window) > 0:
+        raise ValueError("attn_window_recall=%r needs attn_window > 0: the recall is that of a frame window" % (attn_window_recall,))
+    _balance_policy(attn_window_balance)
+    if attn_window_balance and not attn_window_recall:
+        raise ValueError("attn_window_balance=%r needs attn_window_recall > 0: it orders the launches of layers with dense and "
+                         "windowed heads" % (attn_window_balance,))
+    if attn_window_widths is not None:
+        attn_window_widths = _widths_tuple(attn_window_widths, "attn_window_widths")
+        if attn_window_widths[-1] != int(attn_window):
+            raise ValueError("attn_window_widths %r: the last (largest) width must equal attn_window = %d"
+                             % (attn_window_widths, int(attn_window)))
+        if not float(attn_window_recall) > 0.0:
+            raise ValueError("attn_window_widths=%r needs attn_window_recall > 0: the width of a head is the narrowest that "
+                             "reaches the recall" % (attn_window_widths,))
+    if attn_band:   # (the transformer's own check, before anything is loaded)
+        HeadWindowHost._head_window_band(SimpleNamespace(attn_band=attn_band, attn_window=attn_window,
+                                                         attn_window_recall=attn_window_recall,
+                                                         attn_window_widths=attn_window_widths))
+        if fp8_attention:
+            raise ValueError("attn_band=%d does not compose with fp8_attention: the e4m3 attention kernel takes no key ranges"
+                             % attn_band)
+    given = {}
+    for name, value, cast in (("attn_band", attn_band, int), ("step_cache", step_cache, float), ("attn_window", attn_window, int),
+                              ("attn_window_recall", attn_window_recall, float), ("attn_window_balance", attn_window_balance, None)):
+        if value:
+            given[name] = value if cast is None else cast(value)
+    if attn_window_widths is not None:
+        given["attn_window_widths"] = attn_window_widths
+    return given
+
+
+def apply_switches(transformer, switches):
+    """Set what `window_switches` returned -- also on a transformer instance that was passed in; with every switch off nothing is
+    touched (a stand-in need not take attributes)."""
+    for name, value in switches.items():
+        setattr(transformer, name, value)
+
+
+class SamplerExtensions:
+    """One video's drive of a transformer's step cache, attention reuse and per-head windows.  A transformer without the
+    attributes (the loops' stand-ins) arms nothing and is called as ever."""
+
+    def __init__(self, transformer, n_steps, dense_steps=0, cfg_split=None, forward=None, host_timestep=float):
+        """forward: a bound method of the transformer to call in its place (CogVideoX: forward_assembled); host_timestep: the
+        step's timestep as a host number, taken only while the reuse is on (a device tensor costs a round trip)."""
+        self.transformer, self.last, self.dense_steps = transformer, n_steps - 1, dense_steps
+        self.forward, self.host_timestep = forward, host_timestep
+        # step cache (alg_amd/step_cache.py): a new video starts from an empty cache, the last step is always computed
+        self.cache = _step_cache.active(transformer)
+        if self.cache:
+            if cfg_split is not None:
+                raise _lib.AlgHipError("step_cache > 0 with cfg_split: the two ranks of a CFG pair would each decide on their own "
+                                       "passes and leave the single-GPU result; run one of the two")
+            transformer.reset_step_cache()
+        # attention reuse (alg_amd/attn_reuse.py): an empty cache too, the first and the last step are always computed
+        self.reuse = attn_reuse.begin_video(transformer, cfg_split)
+        # per-head windows chosen by recall: every video is calibrated anew, on its last dense step
+        self.recall = bool(getattr(transformer, "attn_window", 0)) and getattr(transformer, "attn_window_recall", 0.0) > 0.0
+        if self.recall:
+            if cfg_split is not None:
+                raise _lib.AlgHipError("attn_window_recall > 0 with cfg_split: the two ranks of a CFG pair would decide the windowed "
+                                       "heads on different passes; run one of the two")
+            transformer.reset_attn_window_heads()
+
+    def step(self, i, t, n_pass, batch):
+        """The callable for the forwards of step `i` (timestep `t`, a CFG batch of n_pass x batch samples): call_transformer with
+        the step's dense / calibrate flags and, while a cache is on, the roles of the passes and whether the step is forced."""
+        kw = {}
+        if self.cache:
+            kw = dict(cache_keys=_step_cache.pass_keys(n_pass, batch), cache_force=i == self.last)
+        if self.reuse:
+            self.transformer.attn_reuse_advance()
+            kw = dict(cache_keys=attn_reuse.step_keys(n_pass, batch, self.host_timestep(t)),
+                      cache_force=i == self.last or not self.transformer.attn_reuse_stats)
+        return functools.partial(call_transformer, self.transformer, i < self.dense_steps, forward=self.forward,
+                                 calibrate=self.recall and i == calibration_step(self.dense_steps), **kw)

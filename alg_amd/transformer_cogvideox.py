@@ -343,15 +343,12 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
         real checkpoint cannot be downloaded here).  Matrices N(0, std^2), biases 0, norm gains 1.  `lora` (a path,
         (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is merged into the state dict
         before the model is built from it."""
-        from .lora import merge_into
+        from . import lora as _lora
         from .weights import synthetic_state_dict
 
         config = config or CogVideoXTransformerConfig()
         sd = synthetic_state_dict(config, seed=seed, std=std, device=device, randomize_affine=randomize_affine)
-        report = merge_into(sd, lora, device)
-        model = cls(config, sd, device=device, fp8=fp8, fp4=fp4)
-        model.lora_report = report
-        return model
+        return _lora.build(cls, config, sd, lora, device, fp8=fp8, fp4=fp4)
 
     @classmethod
     def from_pretrained(cls, path, subfolder="transformer", torch_dtype=torch.bfloat16, device="cuda", fp8=False, fp4=False,
@@ -361,14 +358,12 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
         the adapter file and merges for itself behind the weight broadcast (alg_lora_merge gives every rank the same bits).  `attn_reuse`, `attn_reuse_t_lo` and `attn_reuse_t_hi` (taken from the trailing keywords; alg_amd/attn_reuse.py) set the
         model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors."""
         from .attn_reuse import apply_switches, switches_from
-        from .lora import merge_into
+        from . import lora as _lora
         from .weights import load_diffusers_transformer
 
         reuse = switches_from(_)
         config, sd = load_diffusers_transformer(path, subfolder)
-        report = merge_into(sd, lora, device)
-        model = cls(config, sd, device=device, fp8=fp8, fp4=fp4)
-        model.lora_report = report
+        model = _lora.build(cls, config, sd, lora, device, fp8=fp8, fp4=fp4)
         apply_switches(model, reuse)
         return model
 

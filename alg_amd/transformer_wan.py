@@ -290,13 +290,10 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
     def from_synthetic(cls, config=None, seed=1234, device="cuda", fp8=False, fp8_attention=False, lora=None):
         """`lora` (a path, (path_or_dict, scale), {"path", "scale", "name"} or a list of them: alg_amd/lora.py) is merged into
         the state dict before the model is built from it."""
-        from .lora import merge_into
+        from . import lora as _lora
         config = config or WanTransformerConfig()
         sd = synthetic_state_dict(config, seed=seed, device=device)
-        report = merge_into(sd, lora, device)
-        model = cls(config, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
-        model.lora_report = report
-        return model
+        return _lora.build(cls, config, sd, lora, device, fp8=fp8, fp8_attention=fp8_attention)
 
     @classmethod
     def from_pretrained(cls, path, subfolder="transformer", torch_dtype=BF, device="cuda", fp8=False, fp8_attention=False,
@@ -317,11 +314,8 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
         fields = WanTransformerConfig.__dataclass_fields__
         cfg = WanTransformerConfig(**{k: (tuple(v) if k == "patch_size" else v) for k, v in raw.items() if k in fields})
         from .weights import read_shards
-        from .lora import merge_into
-        sd = read_shards(root)
-        report = merge_into(sd, lora, device)
-        model = cls(cfg, sd, device=device, fp8=fp8, fp8_attention=fp8_attention)
-        model.lora_report = report
+        from . import lora as _lora
+        model = _lora.build(cls, cfg, read_shards(root), lora, device, fp8=fp8, fp8_attention=fp8_attention)
         apply_switches(model, reuse)
         return model
 

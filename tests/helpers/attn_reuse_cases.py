@@ -1,6 +1,6 @@
 """The three small trained-like DiTs (tests/helpers/trained_like_cases.py: cog_case, wan_case, hy_case) as the attention-reuse
 tests drive them: one `Family` per model with its weights, seeded inputs of any batch size at the case's shapes, and a forward
-that takes cache keys.  Shared by tests/test_gpu_attn_reuse_models.py and tests/test_gpu_attn_reuse_samplers.py."""
+that takes cache keys.  Shared by tests/test_gpu_attn_reuse_models.py and the samplers of tests/helpers/sampler_cases.py."""
 import torch
 
 from alg_amd import transformer_cogvideox, transformer_hunyuan_video, transformer_wan

@@ -8,87 +8,13 @@ F F T F T F F F.  The tests recompute that column from the records' own (keys, t
 import pytest
 import torch
 
-from alg_amd import CogVideoXDDIMScheduler, CogVideoXImageToVideoPipeline
 from alg_amd.attn_reuse import AttnReuse
-from alg_amd.pipeline_hunyuan_video_image2video_lowpass import HunyuanVideoImageToVideoPipeline
-from alg_amd.pipeline_wan_image2video_lowpass import WanImageToVideoPipeline
-from alg_amd.schedulers import FlowMatchEulerDiscreteScheduler, UniPCMultistepScheduler
-from helpers.attn_reuse_cases import BF, DEV, Family
+from helpers.sampler_cases import SAMPLERS, STEPS, cog_sampler, wan_sampler
 
 pytestmark = pytest.mark.gpu
-STEPS = 8
 F, T = False, True
 WANT = [F, F, T, F, T, F, F, F]
 K3, K2 = ["uncond_init", "uncond", "cond"], ["uncond", "cond"]
-
-
-def cog_sampler():
-    fam = Family("cog")
-    model = fam.build()
-    g = torch.Generator().manual_seed(7)
-    first = (torch.randn(1, 1, 8, 8, 12, generator=g) * 0.7).to(BF)
-    pe, ne = torch.randn(1, 10, 128, generator=g).to(BF), torch.randn(1, 10, 128, generator=g).to(BF)
-
-    def run(**kw):
-        pipe = CogVideoXImageToVideoPipeline(transformer=model, scheduler=CogVideoXDDIMScheduler()).to(DEV)
-        trace = []
-        out = pipe(image_latents=first, prompt_embeds=pe, negative_prompt_embeds=ne, height=64, width=96, num_frames=9,
-                   num_inference_steps=STEPS, output_type="latent", use_low_pass_guidance=True, lp_filter_in_latent=True,
-                   lp_filter_type="gaussian_blur", lp_blur_sigma=3.0, lp_blur_kernel_size=3,
-                   lp_strength_schedule_type="linear", generator=torch.Generator().manual_seed(0), step_trace=trace, **kw).frames
-        return out, [n for _, _, n in trace], [float(t) for t in pipe.scheduler.timesteps]
-
-    return model, run
-
-
-def wan_sampler(frames=3):
-    fam = Family("wan")
-    model = fam.build()
-    g = torch.Generator().manual_seed(8)
-    lat, cond = torch.randn(1, 16, frames, 16, 24, generator=g), torch.randn(1, 20, frames, 16, 24, generator=g)
-    pe, ne = torch.randn(1, 512, 64, generator=g).to(BF), torch.randn(1, 512, 64, generator=g).to(BF)
-    ie = torch.randn(1, 257, 64, generator=g).to(BF)
-
-    def run(**kw):
-        pipe = WanImageToVideoPipeline(transformer=model, scheduler=UniPCMultistepScheduler(flow_shift=3.0)).to(DEV)
-        trace = []
-        out = pipe(prompt_embeds=pe.to(DEV), negative_prompt_embeds=ne.to(DEV), image_embeds=ie.to(DEV),
-                   image_condition=cond.to(DEV), latents=lat.to(DEV), height=128, width=192, num_frames=4 * (frames - 1) + 1,
-                   num_inference_steps=STEPS, guidance_scale=5.0, output_type="latent", use_low_pass_guidance=True,
-                   lp_filter_in_latent=True, step_trace=trace, lp_filter_type="down_up", lp_resize_factor=0.4,
-                   lp_strength_schedule_type="interval", schedule_interval_start_time=0.0, schedule_interval_end_time=0.3,
-                   **kw).frames
-        return out, [n for _, n, _ in trace], [float(t) for t in pipe.scheduler.timesteps]
-
-    return model, run
-
-
-def hy_sampler():
-    fam = Family("hy")
-    model = fam.build()
-    g = torch.Generator().manual_seed(9)
-    lat, img = torch.randn(1, 16, 3, 16, 16, generator=g), torch.randn(1, 16, 1, 16, 16, generator=g)
-    mk = lambda v: (torch.randn(1, 20, 64, generator=g).to(BF), torch.randn(1, 64, generator=g).to(BF),
-                    torch.cat([torch.ones(1, v), torch.zeros(1, 20 - v)], dim=1).to(BF))
-    pos, neg = mk(20), mk(13)
-    d = lambda t_: t_.to(DEV)
-
-    def run(**kw):
-        pipe = HunyuanVideoImageToVideoPipeline(transformer=model, scheduler=FlowMatchEulerDiscreteScheduler(shift=7.0)).to(DEV)
-        trace = []
-        out = pipe(prompt_embeds=d(pos[0]), pooled_prompt_embeds=d(pos[1]), prompt_attention_mask=d(pos[2]),
-                   negative_prompt_embeds=d(neg[0]), negative_pooled_prompt_embeds=d(neg[1]), negative_prompt_attention_mask=d(neg[2]),
-                   negative_prompt=None, image_latents=d(img), latents=d(lat), height=128, width=128, num_frames=9,
-                   num_inference_steps=STEPS, true_cfg_scale=6.0, guidance_scale=6.0, output_type="latent", use_low_pass_guidance=True,
-                   lp_filter_in_latent=True, step_trace=trace, lp_filter_type="down_up", lp_resize_factor=0.625,
-                   lp_strength_schedule_type="interval", schedule_interval_start_time=0.0, schedule_interval_end_time=0.25,
-                   **kw).frames
-        return out, [n for _, n, _ in trace], [float(t) for t in pipe.scheduler.timesteps]
-
-    return model, run
-
-
-SAMPLERS = {"cog": cog_sampler, "wan": wan_sampler, "hy": hy_sampler}
 
 
 def by_the_rule(records, every, lo, hi):
