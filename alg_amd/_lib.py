@@ -41,10 +41,11 @@ EXPORTS = (
     "alg_attn_rows_position_major", "alg_attn_vt_position_major",
     "alg_lora_merge",
     "alg_attn_drift", "alg_attn_drift_workspace_bytes",
+    "alg_cfg_ddim_step_delta", "alg_cfg_combine_delta", "alg_cfg_delta_drift", "alg_cfg_delta_drift_workspace_bytes",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
             "alg_gaussian_blur_workspace_bytes", "alg_flash_attn_d64_workspace_bytes", "alg_pack_b_p11_bytes",
-            "alg_step_cache_workspace_bytes", "alg_attn_drift_workspace_bytes")
+            "alg_step_cache_workspace_bytes", "alg_attn_drift_workspace_bytes", "alg_cfg_delta_drift_workspace_bytes")
 
 
 class AlgHipError(RuntimeError):
@@ -122,6 +123,11 @@ def load_library():
     lib.alg_cfg_ddim_step.argtypes = [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_float, c_float, c_float,
                                       c_float, c_float, c_void_p]
     lib.alg_cfg_combine.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_void_p]
+    lib.alg_cfg_ddim_step_delta.argtypes = [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_float, c_float,
+                                            c_float, c_float, c_void_p]
+    lib.alg_cfg_combine_delta.argtypes = [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_void_p]
+    lib.alg_cfg_delta_drift_workspace_bytes.argtypes = [c_int64]
+    lib.alg_cfg_delta_drift.argtypes = [c_void_p, c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p]
     lib.alg_lincomb.argtypes = [POINTER(c_void_p), POINTER(c_float), POINTER(c_int), c_int, c_void_p, c_int, c_int64,
                                 c_void_p]
     lib.alg_step_cache_workspace_bytes.argtypes = [c_int, c_int]
@@ -470,6 +476,81 @@ def cfg_combine(pred, n_pass, guidance_scale):
     _check(lib.alg_cfg_combine(_ptr(pred), _ptr(out), _dt(pred), n_pass, out.numel(), float(guidance_scale), _stream()),
            "alg_cfg_combine")
     return out
+
+
+CFG_DELTA_STORE, CFG_DELTA_REUSE = 0, 1     # include/alg_hip.h: ALG_CFG_DELTA_STORE, ALG_CFG_DELTA_REUSE
+CFG_DRIFT_THREADS, CFG_DRIFT_MAX_BLOCKS = 256, 512     # cfg_step.hip's CD_THREADS, CD_MAX_BLOCKS: one pass of the capped grid
+
+
+def _cfg_delta_mode(mode, what):
+    if mode not in (CFG_DELTA_STORE, CFG_DELTA_REUSE) or isinstance(mode, bool):
+        raise AlgHipError("%s: mode is CFG_DELTA_STORE (0) or CFG_DELTA_REUSE (1), got %r" % (what, mode))
+    return 2 if mode == CFG_DELTA_STORE else 1
+
+
+def cfg_ddim_step_delta_(pred, latents, delta, mode, guidance_scale, sqrt_alpha_t, sqrt_beta_t, coef_a, coef_b):
+    """cfg_ddim_step_ of a two-pass step with the CFG delta (include/alg_hip.h: alg_cfg_ddim_step_delta), in place on ``latents``.
+    STORE: pred [2, numel], delta <- text - uncond; REUSE: pred [1, numel] (the conditional prediction), the unconditional one
+    is rebuilt as text - delta.  delta: a contiguous float32 tensor of latents' numel."""
+    lib = load_library()
+    n_pass = _cfg_delta_mode(mode, "cfg_ddim_step_delta_")
+    for name, t in (("pred", pred), ("latents", latents), ("delta", delta)):
+        _dev(t, name)
+    if not (pred.is_contiguous() and latents.is_contiguous() and delta.is_contiguous()):
+        raise AlgHipError("cfg_ddim_step_delta_ needs contiguous tensors")
+    numel = latents.numel()
+    if pred.numel() != n_pass * numel:
+        raise AlgHipError("pred has %d elements, expected %d * numel = %d in this mode" % (pred.numel(), n_pass, n_pass * numel))
+    if delta.dtype != torch.float32 or delta.numel() != numel:
+        raise AlgHipError("cfg_ddim_step_delta_: delta must be a float32 tensor of latents' %d elements" % numel)
+    _check(lib.alg_cfg_ddim_step_delta(_ptr(pred), _dt(pred), _ptr(delta), _ptr(latents), _dt(latents), int(mode), numel,
+                                       float(guidance_scale), float(sqrt_alpha_t), float(sqrt_beta_t), float(coef_a),
+                                       float(coef_b), _stream()), "alg_cfg_ddim_step_delta")
+    return latents
+
+
+def cfg_combine_delta(pred, delta, mode, guidance_scale):
+    """cfg_combine of a two-pass step with the CFG delta (include/alg_hip.h: alg_cfg_combine_delta), rounded per op in pred's
+    dtype.  STORE: pred [2 * B, ...] -> [B, ...], delta <- text - uncond; REUSE: pred [B, ...] (the conditional prediction).
+    delta: a contiguous tensor of pred's dtype and the output's numel."""
+    lib = load_library()
+    n_pass = _cfg_delta_mode(mode, "cfg_combine_delta")
+    _dev(pred, "pred")
+    _dev(delta, "delta")
+    if not pred.is_contiguous() or not delta.is_contiguous() or pred.shape[0] % n_pass:
+        raise AlgHipError("cfg_combine_delta needs a contiguous [%d * B, ...] prediction in this mode and a contiguous delta" % n_pass)
+    out = torch.empty((pred.shape[0] // n_pass,) + tuple(pred.shape[1:]), device=pred.device, dtype=pred.dtype)
+    if delta.dtype != pred.dtype or delta.numel() != out.numel():
+        raise AlgHipError("cfg_combine_delta: delta must have pred's dtype and the output's %d elements" % out.numel())
+    _check(lib.alg_cfg_combine_delta(_ptr(pred), _ptr(delta), _ptr(out), _dt(pred), int(mode), out.numel(), float(guidance_scale),
+                                     _stream()), "alg_cfg_combine_delta")
+    return out
+
+
+def cfg_delta_drift_workspace_bytes(numel):
+    """Bytes of workspace alg_cfg_delta_drift needs for [numel] operands (one pair of doubles per block of its capped grid)."""
+    n = load_library().alg_cfg_delta_drift_workspace_bytes(int(numel))
+    _check(0 if n >= 0 else int(n), "alg_cfg_delta_drift_workspace_bytes")
+    return int(n)
+
+
+def cfg_delta_drift(a, b, workspace, out):
+    """out[0] = sum |a - b|, out[1] = sum |b| (include/alg_hip.h: alg_cfg_delta_drift).  a, b: contiguous device tensors of one
+    shape, both float32 or both bfloat16; workspace: at least cfg_delta_drift_workspace_bytes(numel) bytes; out: 2 device float64
+    elements (a contiguous view is fine)."""
+    lib = load_library()
+    for name, t in (("a", a), ("b", b)):
+        _dev(t, "cfg_delta_drift: " + name)
+        if t.dtype != a.dtype or t.shape != a.shape or not t.is_contiguous():
+            raise AlgHipError("cfg_delta_drift: a and b must be contiguous tensors of one shape and dtype")
+    _dev(workspace, "cfg_delta_drift: workspace")
+    _dev(out, "cfg_delta_drift: out")
+    if out.dtype != torch.float64 or out.numel() != 2 or not out.is_contiguous():
+        raise AlgHipError("cfg_delta_drift: out must be a contiguous device float64 tensor of 2 elements")
+    if workspace.numel() * workspace.element_size() < cfg_delta_drift_workspace_bytes(a.numel()):
+        raise AlgHipError("cfg_delta_drift: the workspace is smaller than cfg_delta_drift_workspace_bytes(numel)")
+    _check(lib.alg_cfg_delta_drift(_ptr(a), _ptr(b), _dt(a), a.numel(), _ptr(workspace), _ptr(out), _stream()),
+           "alg_cfg_delta_drift")
 
 
 def lincomb(terms, out_dtype, out=None):

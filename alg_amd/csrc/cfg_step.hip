@@ -376,3 +376,294 @@ extern "C" int alg_lincomb(const void* const* xs, const float* coefs, const int*
     hipLaunchKernelGGL(lincomb_kernel<bf16_t>, dim3(grid), dim3(256), 0, (hipStream_t)stream, t, (bf16_t*)out, numel);
   return check_launch("alg_lincomb");
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// CFG residual reuse across steps (an extension: alg_amd/cfg_reuse.py).  The difference text - uncond of a two-pass
+// step is kept (STORE) and, on a later step that runs the conditional pass alone, the unconditional prediction is
+// rebuilt from it (REUSE): u' = text - delta, then the arithmetic of the plain entry on (u', text).  A STORE launch
+// leaves the bits of the plain entry with n_pass = 2 and writes the delta next to them.
+// ---------------------------------------------------------------------------------------------------------------
+namespace alg {
+
+// alg_cfg_ddim_step with the delta: fp32 delta, the dtype pairs and the two paths of cfg_ddim_kernel
+template <typename TP, typename TL, bool VEC, bool REUSE>
+__global__ __launch_bounds__(256) void cfg_ddim_delta_kernel(const TP* __restrict__ pred, float* __restrict__ delta,
+                                                             TL* __restrict__ lat, int64_t numel, StepCoef c) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  // STORE: pred = [uncond | text];  REUSE: pred = [text]
+  const TP* p_tx = REUSE ? pred : pred + numel;
+  constexpr bool LB = sizeof(TL) == 2;
+  if (VEC) {
+    const int64_t nvec = numel / 8;
+    for (int64_t i = gid; i < nvec; i += stride) {
+      float tx[8], u[8], d[8], x[8], r[8];
+      load8<TP>(p_tx, i * 8, tx);
+      if (REUSE) {
+        load8<float>(delta, i * 8, d);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) u[k] = __fsub_rn(tx[k], d[k]);
+      } else {
+        load8<TP>(pred, i * 8, u);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) d[k] = __fsub_rn(tx[k], u[k]);
+        store8<float>(delta, i * 8, d);
+      }
+      load8<TL>(lat, i * 8, x);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) r[k] = step_one<LB>(c, 0.0f, u[k], tx[k], x[k]);
+      store8<TL>(lat, i * 8, r);
+    }
+  } else {
+    for (int64_t e = gid; e < numel; e += stride) {
+      const float tx = load_as_float<TP>(p_tx, e);
+      float u;
+      if (REUSE) {
+        u = __fsub_rn(tx, delta[e]);
+      } else {
+        u = load_as_float<TP>(pred, e);
+        delta[e] = __fsub_rn(tx, u);
+      }
+      store_from_float<TL>(lat, e, step_one<LB>(c, 0.0f, u, tx, load_as_float<TL>(lat, e)));
+    }
+  }
+}
+
+// alg_cfg_combine(n_pass = 2) with the delta: every intermediate, the delta included, rounded to T
+template <typename T, bool REUSE>
+__global__ __launch_bounds__(256) void cfg_combine_delta_kernel(const T* __restrict__ pred, T* __restrict__ delta,
+                                                                T* __restrict__ out, int64_t numel, float g) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const T* p_tx = REUSE ? pred : pred + numel;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < numel; e += stride) {
+    const float tx = load_as_float<T>(p_tx, e);
+    float u;
+    if (REUSE) {
+      u = __fsub_rn(tx, load_as_float<T>(delta, e));
+      if (sizeof(T) == 2) u = rbf(u);
+    } else {
+      u = load_as_float<T>(pred, e);
+    }
+    float d = __fsub_rn(tx, u);
+    if (sizeof(T) == 2) d = rbf(d);
+    if (!REUSE) store_from_float<T>(delta, e, d);
+    float m = __fmul_rn(g, d);
+    if (sizeof(T) == 2) m = rbf(m);
+    store_from_float<T>(out, e, __fadd_rn(u, m));
+  }
+}
+
+// The drift of the delta: out[0] = sum |a - b|, out[1] = sum |b| -- attn_reuse.hip's deterministic scheme over a flat operand.
+// The elements are taken in groups of 8 (group i = elements [8 i, 8 i + 8)); a thread adds the terms of a group in fp32 (a chain
+// of 8) and everything above that in double in a fixed order: lanes by shuffle, waves through LDS, one partial pair per block,
+// a second launch of one block over the pairs.  The last group of a numel that is no multiple of 8 is read element by element
+// and filled with zeros: its chain has numel % 8 terms that count.  The grid is a function of numel alone.  No atomics.
+constexpr int CD_THREADS = 256;
+constexpr int64_t CD_MAX_BLOCKS = 512;
+
+inline int64_t cd_blocks(int64_t numel) {
+  const int64_t groups = (numel + 7) / 8, want = (groups + CD_THREADS - 1) / CD_THREADS;
+  return want < 1 ? 1 : (want > CD_MAX_BLOCKS ? CD_MAX_BLOCKS : want);
+}
+
+template <typename T>
+__global__ __launch_bounds__(CD_THREADS) void cfg_delta_drift_kernel(const T* __restrict__ a, const T* __restrict__ b,
+                                                                     int64_t numel, double* __restrict__ partial) {
+  const int64_t stride = (int64_t)gridDim.x * CD_THREADS;
+  const int64_t full = numel / 8, groups = (numel + 7) / 8;
+  double d = 0.0, n = 0.0;
+  for (int64_t i = (int64_t)blockIdx.x * CD_THREADS + threadIdx.x; i < groups; i += stride) {
+    float fa[8], fb[8];
+    if (i < full) {
+      load8<T>(a, i * 8, fa);
+      load8<T>(b, i * 8, fb);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int64_t e = i * 8 + k;
+        fa[k] = e < numel ? load_as_float<T>(a, e) : 0.0f;
+        fb[k] = e < numel ? load_as_float<T>(b, e) : 0.0f;
+      }
+    }
+    float sd = 0.0f, sn = 0.0f;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      sd = __fadd_rn(sd, fabsf(__fsub_rn(fa[k], fb[k])));
+      sn = __fadd_rn(sn, fabsf(fb[k]));
+    }
+    d += (double)sd;
+    n += (double)sn;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    d += __shfl_down(d, off, 64);
+    n += __shfl_down(n, off, 64);
+  }
+  __shared__ double wd[CD_THREADS / 64], wn[CD_THREADS / 64];
+  if ((threadIdx.x & 63) == 0) {
+    wd[threadIdx.x >> 6] = d;
+    wn[threadIdx.x >> 6] = n;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double sd = wd[0], sn = wn[0];
+#pragma unroll
+    for (int w = 1; w < CD_THREADS / 64; ++w) {
+      sd += wd[w];
+      sn += wn[w];
+    }
+    partial[2 * blockIdx.x] = sd;
+    partial[2 * blockIdx.x + 1] = sn;
+  }
+}
+
+// out[0..1] = the partial pairs of `blocks` workgroups, added in a fixed order in double
+__global__ __launch_bounds__(CD_THREADS) void cfg_delta_drift_sum_kernel(const double* __restrict__ partial, int blocks,
+                                                                         double* __restrict__ out) {
+  __shared__ double sd[CD_THREADS], sn[CD_THREADS];
+  double d = 0.0, n = 0.0;
+  for (int i = threadIdx.x; i < blocks; i += CD_THREADS) {
+    d += partial[2 * i];
+    n += partial[2 * i + 1];
+  }
+  sd[threadIdx.x] = d;
+  sn[threadIdx.x] = n;
+  __syncthreads();
+  for (int w = CD_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) {
+      sd[threadIdx.x] += sd[threadIdx.x + w];
+      sn[threadIdx.x] += sn[threadIdx.x + w];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    out[0] = sd[0];
+    out[1] = sn[0];
+  }
+}
+
+}  // namespace alg
+
+extern "C" int alg_cfg_ddim_step_delta(const void* pred, int pred_dtype, float* delta, void* latents, int lat_dtype, int mode,
+                                       int64_t numel, float guidance_scale, float sqrt_alpha_t, float sqrt_beta_t,
+                                       float coef_a, float coef_b, void* stream) {
+  // check
+  if (numel < 0 || (mode != ALG_CFG_DELTA_STORE && mode != ALG_CFG_DELTA_REUSE)) {
+    set_error("alg_cfg_ddim_step_delta: bad argument (mode=%d numel=%lld; mode is ALG_CFG_DELTA_STORE or ALG_CFG_DELTA_REUSE)", mode,
+              (long long)numel);
+    return ALG_EINVAL;
+  }
+  if ((pred_dtype != ALG_F32 && pred_dtype != ALG_BF16) || (lat_dtype != ALG_F32 && lat_dtype != ALG_BF16)) {
+    set_error("alg_cfg_ddim_step_delta: unsupported dtype codes %d/%d", pred_dtype, lat_dtype);
+    return ALG_EINVAL;
+  }
+  if (numel == 0) return ALG_OK;  // empty tensors carry null data pointers
+  if (!pred || !delta || !latents) {
+    set_error("alg_cfg_ddim_step_delta: null pointer");
+    return ALG_EINVAL;
+  }
+  const size_t psz = pred_dtype == ALG_F32 ? 4 : 2, lsz = lat_dtype == ALG_F32 ? 4 : 2;
+  if ((uintptr_t)pred % psz || (uintptr_t)latents % lsz || (uintptr_t)delta % 4) {
+    set_error("alg_cfg_ddim_step_delta: pred, latents and delta must be aligned to their element size");
+    return ALG_EINVAL;
+  }
+  // plan -- vector path: every chunk base 16-byte aligned and whole 8-element groups, else one element per lane and trip
+  const bool vec = (numel % 8 == 0) && (((uintptr_t)pred | (uintptr_t)latents | (uintptr_t)delta) % 16 == 0) &&
+                   ((numel * psz) % 16 == 0);
+  const int64_t work = vec ? numel / 8 : numel;
+  const int64_t want = (work + 255) / 256;
+  const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 2048 ? 2048 : want));
+  const StepCoef c{guidance_scale, sqrt_alpha_t, sqrt_beta_t, coef_a, coef_b, 2};
+  const bool reuse = mode == ALG_CFG_DELTA_REUSE;
+  hipStream_t s = (hipStream_t)stream;
+  // launch
+#define LAUNCH3(TP, TL, V, R)                                                                                          \
+  hipLaunchKernelGGL((cfg_ddim_delta_kernel<TP, TL, V, R>), dim3(grid), dim3(256), 0, s, (const TP*)pred, delta,      \
+                     (TL*)latents, numel, c)
+#define LAUNCH(TP, TL)                                                                                                 \
+  do {                                                                                                                 \
+    if (vec && reuse) LAUNCH3(TP, TL, true, true);                                                                     \
+    else if (vec) LAUNCH3(TP, TL, true, false);                                                                        \
+    else if (reuse) LAUNCH3(TP, TL, false, true);                                                                      \
+    else LAUNCH3(TP, TL, false, false);                                                                                \
+  } while (0)
+  if (pred_dtype == ALG_F32 && lat_dtype == ALG_F32) LAUNCH(float, float);
+  else if (pred_dtype == ALG_F32) LAUNCH(float, bf16_t);
+  else if (lat_dtype == ALG_F32) LAUNCH(bf16_t, float);
+  else LAUNCH(bf16_t, bf16_t);
+#undef LAUNCH
+#undef LAUNCH3
+  return check_launch("alg_cfg_ddim_step_delta");
+}
+
+extern "C" int alg_cfg_combine_delta(const void* pred, void* delta, void* out, int dtype, int mode, int64_t numel,
+                                     float guidance_scale, void* stream) {
+  // check
+  if (numel < 0 || (mode != ALG_CFG_DELTA_STORE && mode != ALG_CFG_DELTA_REUSE) || (dtype != ALG_F32 && dtype != ALG_BF16)) {
+    set_error("alg_cfg_combine_delta: bad argument (mode=%d numel=%lld dtype=%d)", mode, (long long)numel, dtype);
+    return ALG_EINVAL;
+  }
+  if (numel == 0) return ALG_OK;  // empty tensors carry null data pointers
+  if (!pred || !delta || !out) {
+    set_error("alg_cfg_combine_delta: null pointer");
+    return ALG_EINVAL;
+  }
+  const size_t sz = dtype == ALG_F32 ? 4 : 2;
+  if (((uintptr_t)pred | (uintptr_t)delta | (uintptr_t)out) % sz) {
+    set_error("alg_cfg_combine_delta: pred, delta and out must be aligned to their element size");
+    return ALG_EINVAL;
+  }
+  // plan: alg_cfg_combine's -- one element per lane and trip, a grid capped at 4,096 blocks
+  const int64_t want = (numel + 255) / 256;
+  const unsigned grid = (unsigned)(want > 4096 ? 4096 : want);
+  const bool reuse = mode == ALG_CFG_DELTA_REUSE;
+  hipStream_t s = (hipStream_t)stream;
+  // launch
+#define LAUNCH(T, R)                                                                                                   \
+  hipLaunchKernelGGL((cfg_combine_delta_kernel<T, R>), dim3(grid), dim3(256), 0, s, (const T*)pred, (T*)delta, (T*)out, \
+                     numel, guidance_scale)
+  if (dtype == ALG_F32 && reuse) LAUNCH(float, true);
+  else if (dtype == ALG_F32) LAUNCH(float, false);
+  else if (reuse) LAUNCH(bf16_t, true);
+  else LAUNCH(bf16_t, false);
+#undef LAUNCH
+  return check_launch("alg_cfg_combine_delta");
+}
+
+extern "C" int64_t alg_cfg_delta_drift_workspace_bytes(int64_t numel) {
+  if (numel < 0) {
+    set_error("alg_cfg_delta_drift_workspace_bytes: bad argument (numel=%lld)", (long long)numel);
+    return ALG_EINVAL;
+  }
+  return cd_blocks(numel) * 2 * (int64_t)sizeof(double);
+}
+
+extern "C" int alg_cfg_delta_drift(const void* a, const void* b, int dtype, int64_t numel, void* work, double* out,
+                                   void* stream) {
+  // check
+  if (numel < 0 || (dtype != ALG_F32 && dtype != ALG_BF16)) {
+    set_error("alg_cfg_delta_drift: bad argument (numel=%lld dtype=%d)", (long long)numel, dtype);
+    return ALG_EINVAL;
+  }
+  if (numel == 0) return ALG_OK;  // nothing is launched: out is left as it is
+  if (!a || !b || !work || !out) {
+    set_error("alg_cfg_delta_drift: null pointer");
+    return ALG_EINVAL;
+  }
+  if (((uintptr_t)a | (uintptr_t)b) & 15 || ((uintptr_t)work | (uintptr_t)out) & 7) {
+    set_error("alg_cfg_delta_drift: a and b must be 16-byte aligned, work and out 8-byte aligned");
+    return ALG_EINVAL;
+  }
+  // plan
+  const int blocks = (int)cd_blocks(numel);
+  hipStream_t s = (hipStream_t)stream;
+  // launch
+  if (dtype == ALG_F32)
+    hipLaunchKernelGGL(cfg_delta_drift_kernel<float>, dim3((unsigned)blocks), dim3(CD_THREADS), 0, s, (const float*)a,
+                       (const float*)b, numel, (double*)work);
+  else
+    hipLaunchKernelGGL(cfg_delta_drift_kernel<bf16_t>, dim3((unsigned)blocks), dim3(CD_THREADS), 0, s, (const bf16_t*)a,
+                       (const bf16_t*)b, numel, (double*)work);
+  hipLaunchKernelGGL(cfg_delta_drift_sum_kernel, dim3(1), dim3(CD_THREADS), 0, s, (const double*)work, blocks, out);
+  return check_launch("alg_cfg_delta_drift");
+}

@@ -28,7 +28,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import torch
 
-from . import _lib, attn_reuse, lp_utils, sampler_ext
+from . import _lib, attn_reuse, cfg_reuse, lp_utils, sampler_ext
 from .schedulers import CogVideoXDDIMScheduler, CogVideoXDPMScheduler
 from .transformer_cogvideox import CogVideoXTransformer3DModel
 
@@ -142,11 +142,11 @@ class CogVideoXImageToVideoPipeline:
         and `attn_window_balance` set the transformer's attributes of these names, also on an instance passed in; all are off by
         default, `attn_window_widths` (head_dim 128 only) is refused, and sampler_ext.window_switches raises ValueError for what
         does not compose before anything is loaded.  `lora` (alg_amd/lora.py) and, from the trailing keywords (the order of the
-        named ones is pinned), `attn_reuse`, `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) go to the transformer
-        loader: like `fp8` they have no effect on a transformer instance passed in."""
+        named ones is pinned), `attn_reuse`, `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) and `cfg_reuse`, `cfg_reuse_t_lo`,
+        `cfg_reuse_t_hi` (alg_amd/cfg_reuse.py) go to the transformer loader: like `fp8` they have no effect on a transformer instance passed in."""
         import os
 
-        reuse_kw = attn_reuse.switches_from(_)
+        reuse_kw = dict(attn_reuse.switches_from(_), **cfg_reuse.switches_from(_))
         switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths,
                                                step_cache=step_cache, widths_built=False, recall_needs_window=True)
 
@@ -562,7 +562,7 @@ class CogVideoXImageToVideoPipeline:
         B = latents.shape[0]
         # the transformer's opt-in extensions (alg_amd/sampler_ext.py): refusals and resets here, one callable per step below
         ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps, cfg_split,
-                                            forward=self.transformer.forward_assembled, host_timestep=int)
+                                            forward=self.transformer.forward_assembled, host_timestep=int, do_cfg=do_cfg)
         # every timestep of the schedule on the device ONCE: a step takes a view of it (no host tensor + H2D copy per step)
         ts_dev = torch.as_tensor([int(t_) for t_ in timesteps], dtype=torch.float32).to(device)
         for i, t in enumerate(timesteps):
@@ -609,6 +609,11 @@ class CogVideoXImageToVideoPipeline:
                     raise NameError("name 'two_pass' is not defined (use_low_pass_guidance=True needs guidance_scale > 1)")
                 cond_groups, embeds = [image_latents], prompt_embeds_init
             n_pass = len(cond_groups)
+            # CFG reuse (alg_amd/cfg_reuse.py; off: the plain plan, nothing below differs): a reused step runs the conditional
+            # pass alone -- the last group, the last B rows of the embeddings -- and rebuilds the unconditional prediction
+            plan = ext.cfg_plan(i, t, n_pass)
+            if plan.reuse:
+                cond_groups, embeds, n_pass = cond_groups[-1:], embeds[-B:], 1
             conds = [g[b:b + 1] for g in cond_groups for b in range(B)]
             lat_in = latents if B == 1 else torch.cat([latents] * n_pass, dim=0)
             ts = ts_dev[i:i + 1].expand(n_pass * B)
@@ -630,14 +635,20 @@ class CogVideoXImageToVideoPipeline:
             if is_dpm:
                 # cog:1091-1123, DPM branch: float(); CFG combine in fp32; the two-output step; cast back
                 pred32 = noise_pred.float()
-                if n_pass > 1:
+                if plan.mode is not None:
+                    pred32 = _lib.cfg_combine_delta(pred32, plan.delta(latents.shape, torch.float32, device), plan.mode, gs)
+                elif n_pass > 1:
                     pred32 = _lib.cfg_combine(pred32, n_pass, gs)
                 new_lat, old_pred_original_sample = self.scheduler.step(
                     pred32, old_pred_original_sample, t, timesteps[i - 1] if i > 0 else None, latents,
                     generator=generator, return_dict=False)
                 latents = _lib.lincomb([(1.0, new_lat)], dtype)
+            elif plan.mode is not None:
+                self.scheduler.fused_cfg_step_delta_(noise_pred, latents, plan.delta(latents.shape, torch.float32, device),
+                                                     plan.mode, gs, t)
             else:
                 self.scheduler.fused_cfg_step_(noise_pred, latents, n_pass, gs, t)
+            plan.finish()
             if step_trace is not None:
                 step_trace.append((strength, bool(two_pass), n_pass * B))
             if callback_on_step_end is not None:
@@ -648,6 +659,7 @@ class CogVideoXImageToVideoPipeline:
                 new_lat = outs.pop("latents", latents)
                 if new_lat is not latents:
                     latents = new_lat.to(dtype).contiguous().clone()
+                    ext.cfg_invalidate()
                 new_pe = outs.pop("prompt_embeds", prompt_embeds)
                 new_ne = outs.pop("negative_prompt_embeds", negative_prompt_embeds)
                 if new_pe is not prompt_embeds or new_ne is not negative_prompt_embeds:
@@ -656,6 +668,7 @@ class CogVideoXImageToVideoPipeline:
                     # pre-concatenated CFG batches are rebuilt from what the callback returned.
                     prompt_embeds, negative_prompt_embeds = new_pe.to(device, dtype), (
                         None if new_ne is None else new_ne.to(device, dtype))
+                    ext.cfg_invalidate()
                     if do_cfg and use_low_pass_guidance:
                         prompt_embeds_init = torch.cat([negative_prompt_embeds, prompt_embeds], dim=0)
                         prompt_embeds_3 = torch.cat([negative_prompt_embeds, negative_prompt_embeds, prompt_embeds], dim=0)

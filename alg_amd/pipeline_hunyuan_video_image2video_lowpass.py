@@ -29,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from . import _lib, attn_reuse, lp_utils, sampler_ext
+from . import _lib, attn_reuse, cfg_reuse, lp_utils, sampler_ext
 from .pipeline_cogvideox_image2video_lowpass import retrieve_timesteps
 from .schedulers import FlowMatchEulerDiscreteScheduler
 
@@ -130,11 +130,12 @@ class HunyuanVideoImageToVideoPipeline:
         transformer's attributes of these names, also on an instance passed in; all are off by default, and
         sampler_ext.window_switches refuses (ValueError) what does not compose before anything is loaded.  `lora`
         (alg_amd/lora.py) and, from the trailing keywords (the order of the named ones is pinned), `attn_reuse`,
-        `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) go to the transformer loader: like `fp8` they have no
+        `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py), `cfg_reuse`, `cfg_reuse_t_lo`, `cfg_reuse_t_hi`
+        (alg_amd/cfg_reuse.py) go to the transformer loader: like `fp8` they have no
         effect on a transformer instance passed in."""
         import os
 
-        reuse_kw = attn_reuse.switches_from(_)
+        reuse_kw = dict(attn_reuse.switches_from(_), **cfg_reuse.switches_from(_))
         switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths)
 
         from .schedulers import FlowMatchEulerDiscreteScheduler
@@ -556,7 +557,7 @@ class HunyuanVideoImageToVideoPipeline:
         neg3 = lambda a, b: torch.cat([a, a, b], dim=0)
         neg2 = lambda a, b: torch.cat([a, b], dim=0)
         # the transformer's opt-in extensions (alg_amd/sampler_ext.py): refusals and resets here, one callable per step below
-        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps)
+        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps, do_cfg=bool(do_true_cfg))
         for i, t in enumerate(timesteps):
             if self._interrupt:
                 continue
@@ -575,6 +576,11 @@ class HunyuanVideoImageToVideoPipeline:
             else:  # ALG without true CFG: one pass on the low-passed first frame (hy:1196-1229)
                 strength, lp_lat = lp_for_step(i)
                 groups, cat = [lp_lat], None
+            # CFG reuse (alg_amd/cfg_reuse.py; off: the plain plan, nothing below differs): a reused step runs the conditional
+            # pass alone and rebuilds the unconditional prediction from the cached delta
+            plan = ext.cfg_plan(i, t, len(groups))
+            if plan.reuse:
+                groups, cat = groups[-1:], None
             latent_model_input = assemble_first_frame(latents, groups, tdtype)
             if cat is None:
                 ehs, pooled, mask = prompt_embeds, pooled_prompt_embeds, prompt_attention_mask
@@ -589,7 +595,12 @@ class HunyuanVideoImageToVideoPipeline:
                              encoder_attention_mask=mask, pooled_projections=pooled, guidance=guidance,
                              attention_kwargs=attention_kwargs, return_dict=False)[0]
             # hy:1254-1261 keys the combine on shape[0] (3 -> three chunks, 2 -> two chunks, anything else: none)
-            if noise_pred.shape[0] in (2, 3):
+            if plan.mode is not None:   # (a reused step's one-sample prediction is no CFG batch: the shape rule must not see it)
+                noise_pred = noise_pred.contiguous()
+                noise_pred = _lib.cfg_combine_delta(noise_pred, plan.delta(latents.shape, noise_pred.dtype, device), plan.mode,
+                                                    true_cfg_scale)
+                plan.finish()
+            elif noise_pred.shape[0] in (2, 3):
                 noise_pred = _lib.cfg_combine(noise_pred.contiguous(), noise_pred.shape[0], true_cfg_scale)
             if image_condition_type == "latent_concat":
                 latents = self.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
@@ -606,6 +617,8 @@ class HunyuanVideoImageToVideoPipeline:
             if callback_on_step_end is not None:
                 pool = {"latents": latents, "prompt_embeds": prompt_embeds}
                 outs = callback_on_step_end(self, i, t, {k: pool[k] for k in callback_on_step_end_tensor_inputs}) or {}
+                if any(outs.get(k, pool[k]) is not pool[k] for k in pool):
+                    ext.cfg_invalidate()
                 latents = outs.pop("latents", latents).contiguous()
                 prompt_embeds = outs.pop("prompt_embeds", prompt_embeds)
         self._current_timestep = None

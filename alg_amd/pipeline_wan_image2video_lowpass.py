@@ -30,7 +30,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, attn_reuse, lp_utils, sampler_ext
+from . import _lib, attn_reuse, cfg_reuse, lp_utils, sampler_ext
 from .schedulers import UniPCMultistepScheduler
 
 
@@ -111,12 +111,13 @@ class WanImageToVideoPipeline:
         `step_cache` (a threshold), `attn_window` (latent frames on each side), `attn_window_recall`, `attn_window_balance`,
         `attn_window_widths` and `attn_band` set the transformer's attributes of these names, also on an instance passed in; all
         are off by default, and sampler_ext.window_switches refuses (ValueError) what does not compose before anything is loaded.
-        `lora` (alg_amd/lora.py) and `attn_reuse`, `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) are taken from the
+        `lora` (alg_amd/lora.py), `attn_reuse`, `attn_reuse_t_lo`, `attn_reuse_t_hi` (alg_amd/attn_reuse.py) and `cfg_reuse`,
+        `cfg_reuse_t_lo`, `cfg_reuse_t_hi` (alg_amd/cfg_reuse.py) are taken from the
         trailing keywords -- the named ones end with attn_band, their order is pinned -- and go to the transformer loader: like
         `fp8` they have no effect on a transformer instance passed in."""
         import os
 
-        reuse_kw = attn_reuse.switches_from(_)
+        reuse_kw = dict(attn_reuse.switches_from(_), **cfg_reuse.switches_from(_))
         switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths, attn_band,
                                                fp8_attention, step_cache=step_cache)
 
@@ -474,7 +475,7 @@ class WanImageToVideoPipeline:
                                                   width, num_frames, torch.float32, device, generator, latents)
 
         # the transformer's opt-in extensions (alg_amd/sampler_ext.py): refusals and resets here, one callable per step below
-        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps, cfg_split)
+        ext = sampler_ext.SamplerExtensions(self.transformer, len(timesteps), attn_window_dense_steps, cfg_split, do_cfg=do_cfg)
         for i, t in enumerate(timesteps):
             if self._interrupt or i < self._first_step:
                 continue
@@ -511,6 +512,11 @@ class WanImageToVideoPipeline:
                 # reference quirk (wan:843-898): without CFG no branch assigns `latent_model_input`
                 raise UnboundLocalError("local variable 'latent_model_input' referenced before assignment "
                                         "(the Wan ALG loop needs guidance_scale > 1)")
+            # CFG reuse (alg_amd/cfg_reuse.py; off: the plain plan, nothing below differs): a reused step runs the conditional
+            # pass alone and rebuilds the unconditional prediction from the cached delta
+            plan = ext.cfg_plan(i, t, len(groups))
+            if plan.reuse:
+                groups, embeds = groups[-1:], embeds[-1:]
             latent_model_input = assemble_channel_concat(latents, groups, tdtype)
             dit = ext.step(i, t, len(groups), latents.shape[0])
             n = latent_model_input.shape[0]
@@ -531,11 +537,18 @@ class WanImageToVideoPipeline:
                     encoder_hidden_states_image=ehs_img, attention_kwargs=attention_kwargs, return_dict=False)[0]
             # wan:919-924 keys the 3-chunk combine on shape[0] == 3, so the reference's 3-pass step only works for one
             # video per call (a [3B, ...] prediction would be chunked in two and fail in the scheduler)
-            n_pass = 3 if noise_pred.shape[0] == 3 else 2
-            if n_pass != len(groups):
+            # (a reused step's one-sample prediction is no CFG batch: the shape rule below must not see it)
+            n_pass = 2 if plan.reuse else 3 if noise_pred.shape[0] == 3 else 2
+            if n_pass != len(groups) and not plan.reuse:
                 raise ValueError("the Wan ALG loop (3-pass CFG keyed on shape[0] == 3, wan:919) supports one video "
                                  f"per call; got a batch of {latents.shape[0]}")
-            noise_pred = _lib.cfg_combine(noise_pred.contiguous(), n_pass, guidance_scale)
+            if plan.mode is not None:
+                noise_pred = noise_pred.contiguous()
+                noise_pred = _lib.cfg_combine_delta(noise_pred, plan.delta(latents.shape, noise_pred.dtype, device), plan.mode,
+                                                    guidance_scale)
+                plan.finish()
+            else:
+                noise_pred = _lib.cfg_combine(noise_pred.contiguous(), n_pass, guidance_scale)
             latents = self.scheduler.step(noise_pred, t, latents, return_dict=False)[0]
             if step_trace is not None:
                 step_trace.append((strength, len(groups), n))
@@ -543,6 +556,8 @@ class WanImageToVideoPipeline:
                 pool = {"latents": latents, "prompt_embeds": prompt_embeds,
                         "negative_prompt_embeds": negative_prompt_embeds}
                 outs = callback_on_step_end(self, i, t, {k: pool[k] for k in callback_on_step_end_tensor_inputs}) or {}
+                if any(outs.get(k, pool[k]) is not pool[k] for k in pool):
+                    ext.cfg_invalidate()
                 latents = outs.pop("latents", latents).contiguous()
                 prompt_embeds = outs.pop("prompt_embeds", prompt_embeds)
                 negative_prompt_embeds = outs.pop("negative_prompt_embeds", negative_prompt_embeds)

@@ -129,6 +129,14 @@ class CogVideoXDDIMScheduler(_ConfigLoading):
         sa, sb, ca, cb = self.step_coefficients(timestep)
         return _lib.cfg_ddim_step_(noise_pred, latents, n_pass, guidance_scale, sa, sb, ca, cb)
 
+    def fused_cfg_step_delta_(self, noise_pred, latents, delta, mode, guidance_scale, timestep):
+        """fused_cfg_step_ of a two-pass step with the CFG delta (alg_amd/cfg_reuse.py), in place on ``latents``.  mode
+        _lib.CFG_DELTA_STORE: noise_pred holds both passes, the step is bit for bit fused_cfg_step_(n_pass=2) and ``delta``
+        (float32, latents' shape) receives text - uncond; _lib.CFG_DELTA_REUSE: noise_pred holds the conditional pass alone and
+        the unconditional prediction is rebuilt as text - delta."""
+        sa, sb, ca, cb = self.step_coefficients(timestep)
+        return _lib.cfg_ddim_step_delta_(noise_pred, latents, delta, mode, guidance_scale, sa, sb, ca, cb)
+
 
 def _step_index_for(timesteps, timestep):
     """index_for_timestep of the diffusers schedulers: second match on duplicates, last index on no match."""

@@ -44,6 +44,7 @@ import torch
 
 from . import _lib
 from .attn_reuse import AttnReuseHost
+from .cfg_reuse import CfgReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
 from .step_cache import StepCacheHost
 
@@ -89,7 +90,7 @@ def _bf(t, device):
     return t.to(device=device, dtype=torch.bfloat16).contiguous()
 
 
-class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
+class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWindowHost):
     dtype = torch.bfloat16
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -356,15 +357,19 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, HeadWindowHost):
         """Load a diffusers-format checkpoint directory (config.json + *.safetensors) from local disk.  `lora` (as in
         from_synthetic) is merged into the state dict before the model is built from it; in a multi-rank run every rank reads
         the adapter file and merges for itself behind the weight broadcast (alg_lora_merge gives every rank the same bits).  `attn_reuse`, `attn_reuse_t_lo` and `attn_reuse_t_hi` (taken from the trailing keywords; alg_amd/attn_reuse.py) set the
-        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors."""
+        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors.  `cfg_reuse`,
+        `cfg_reuse_t_lo` and `cfg_reuse_t_hi` (alg_amd/cfg_reuse.py) set the samplers' CFG-reuse switches the same way."""
+        from . import cfg_reuse as _cfg_reuse
         from .attn_reuse import apply_switches, switches_from
         from . import lora as _lora
         from .weights import load_diffusers_transformer
 
         reuse = switches_from(_)
+        cfg_switches = _cfg_reuse.switches_from(_)
         config, sd = load_diffusers_transformer(path, subfolder)
         model = _lora.build(cls, config, sd, lora, device, fp8=fp8, fp4=fp4)
         apply_switches(model, reuse)
+        _cfg_reuse.apply_switches(model, cfg_switches)
         return model
 
     def to(self, *args, **kwargs):

@@ -37,6 +37,7 @@ import torch
 
 from . import _lib
 from .attn_reuse import AttnReuseHost
+from .cfg_reuse import CfgReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
 from .transformer_wan import k_scale_bound
 
@@ -149,7 +150,7 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
     return sd
 
 
-class HunyuanVideoTransformer3DModel(AttnReuseHost, HeadWindowHost):
+class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -324,9 +325,12 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, HeadWindowHost):
                         lora=None, **_):
         """Load a diffusers-format checkpoint directory from local disk.  `lora` (as in from_synthetic) is merged into the state
         dict before the model is built from it; in a multi-rank run every rank merges for itself behind the weight broadcast.  `attn_reuse`, `attn_reuse_t_lo` and `attn_reuse_t_hi` (taken from the trailing keywords; alg_amd/attn_reuse.py) set the
-        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors."""
+        model's attention-reuse switches: 0 / 100 / 800 by default, attn_reuse = 1 and lo >= hi are ValueErrors.  `cfg_reuse`,
+        `cfg_reuse_t_lo` and `cfg_reuse_t_hi` (alg_amd/cfg_reuse.py) set the samplers' CFG-reuse switches the same way."""
+        from . import cfg_reuse as _cfg_reuse
         from .attn_reuse import apply_switches, switches_from
         reuse = switches_from(_)
+        cfg_switches = _cfg_reuse.switches_from(_)
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -341,6 +345,7 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, HeadWindowHost):
         from . import lora as _lora
         model = _lora.build(cls, cfg, read_shards(root), lora, device, fp8_attention=fp8_attention, fp8=fp8)
         apply_switches(model, reuse)
+        _cfg_reuse.apply_switches(model, cfg_switches)
         return model
 
     def to(self, *a, **k):

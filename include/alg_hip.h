@@ -138,6 +138,44 @@ int alg_cfg_ddim_step(const void* pred, int pred_dtype, void* latents, int lat_d
 int alg_cfg_combine(const void* pred, void* out, int dtype, int n_pass, int64_t numel, float guidance_scale,
                     void* stream);
 
+/* CFG residual reuse across steps (an extension: alg_amd/cfg_reuse.py; the reference has none).  A two-pass step keeps
+ * delta = text - uncond (STORE); a later step that ran the conditional pass alone rebuilds the unconditional prediction from it
+ * (REUSE) and goes on with the arithmetic of the plain entry.  All three entries check, plan, launch: a mode outside {0, 1}, a
+ * dtype code the entry does not know, a negative numel, a null pointer, or a pointer that is not aligned to its element size
+ * (alg_cfg_delta_drift: a and b to 16 bytes, work and out to 8) is ALG_EINVAL before anything is launched; numel == 0 is ALG_OK
+ * without a launch (and without a look at the pointers). */
+#define ALG_CFG_DELTA_STORE 0
+#define ALG_CFG_DELTA_REUSE 1
+
+/* alg_cfg_ddim_step with the delta; delta: fp32 [numel]; latents: [numel] of lat_dtype, updated IN PLACE.
+ *   STORE: pred [2, numel] = [uncond, text].  latents get the bits alg_cfg_ddim_step(n_pass = 2) gives them, and
+ *          delta[e] = float(text[e]) - float(uncond[e])  (one fp32 subtraction: the value the combine forms anyway)
+ *   REUSE: pred [1, numel] = [text].  u' = float(text) - delta (fp32), then the n_pass = 2 update on (u', text):
+ *          v = u' + g * (text - u');  x0 = sqrt_alpha_t * x - sqrt_beta_t * v;  x <- coef_a * x + coef_b * x0
+ * The dtype pairs and the two paths of alg_cfg_ddim_step: 8 elements per lane and trip when numel % 8 == 0 and pred, delta and
+ * latents are 16-byte aligned, one element otherwise; a grid of at most 2,048 blocks with a grid-stride loop. */
+int alg_cfg_ddim_step_delta(const void* pred, int pred_dtype, float* delta, void* latents, int lat_dtype, int mode, int64_t numel,
+                            float guidance_scale, float sqrt_alpha_t, float sqrt_beta_t, float coef_a, float coef_b,
+                            void* stream);
+
+/* alg_cfg_combine with the delta (the Wan / HunyuanVideo loops, and the fp32 combine in front of CogVideoX's DPM step): every
+ * intermediate is rounded to `dtype` (rnd), and delta [numel] has that dtype; out [numel].
+ *   STORE: pred [2, numel].  out has the bits of alg_cfg_combine(n_pass = 2), delta = rnd(text - uncond), that kernel's d
+ *   REUSE: pred [1, numel].  u' = rnd(text - delta), then out = u' + rnd(g * rnd(text - u')) */
+int alg_cfg_combine_delta(const void* pred, void* delta, void* out, int dtype, int mode, int64_t numel, float guidance_scale,
+                          void* stream);
+
+/* The drift of the delta (the diagnostic of cfg_reuse_drift): out[0] = sum |float(a) - float(b)|, out[1] = sum |float(b)| over
+ * a (new), b (cached): [numel] of `dtype` (ALG_F32 or ALG_BF16), 16-byte aligned; numel needs no alignment.  DEVICE doubles,
+ * deterministic, alg_attn_drift's scheme: the elements go in groups of 8, the terms of a group are added in fp32 (a chain of 8),
+ * everything above in double in a fixed order that depends on numel alone (a capped grid with a grid-stride loop, one partial
+ * pair per block into `work`, a second launch of one block sums them); no atomics.  The last group of a numel that is no
+ * multiple of 8 is read element by element and filled with zeros, so its chain has numel % 8 terms that count.  A NaN in a
+ * reaches out[0] only.  work: alg_cfg_delta_drift_workspace_bytes(numel) bytes, 8-byte aligned.  numel == 0 launches nothing
+ * and leaves out as it is. */
+int64_t alg_cfg_delta_drift_workspace_bytes(int64_t numel);
+int alg_cfg_delta_drift(const void* a, const void* b, int dtype, int64_t numel, void* work, double* out, void* stream);
+
 /* out = sum_i coefs[i] * xs[i]  (1..4 terms, each ALG_F32 or ALG_BF16).  Rounding follows torch eager: every product
  * is rounded to its tensor's dtype, the running sum is fp32, left to right, unfused; cast to out_dtype at the end.
  * Covers FlowMatchEulerDiscreteScheduler.step (hy:1265-1269: sample + (sigma_next - sigma) * v) and UniPC's
