@@ -42,6 +42,9 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const bf16_t* __restrict
 
 // grid (row blocks, batch * heads); 4 waves, wave w takes query rows row0 + w, + 4, ...; DH = head_dim (64: T5 / UMT5,
 // 80: CLIP ViT-H)
+// A query row with no surviving key (every key masked, or key 0 masked under `causal` for row 0) has sum = 0: inv = 0, every
+// p = 0, and the row is stored as zeros -- the eager graph's softmax over an empty set gives NaN there; alg_hip.h pins the zeros.
+// Key slots [L, Lp) are zero-filled in LDS and never pass `j < L`; the p v loop stops at L.
 // LDS: KT [DH][Lp] bf16 | V [Lp][DH] bf16 | q [4][128] f32 | p [4][Lp] f32
 template <int DH>
 __global__ __launch_bounds__(256) void attn_bias_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ k,
@@ -202,6 +205,12 @@ extern "C" int alg_attn_bias(const void* q, const void* k, const void* v, void* 
   if (batch == 0) return ALG_OK;
   if (!q || !k || !v || !out) {
     set_error("alg_attn_bias: null pointer");
+    return ALG_EINVAL;
+  }
+  // the staging loop reads k and v 16 bytes at a time from ptr + row * qkv_rstride + h * head_dim + 8 c: with the pitch and
+  // the head width multiples of 8 elements, every such address is 16-byte aligned exactly when the base is (q is read per element)
+  if (((uintptr_t)k | (uintptr_t)v) & 15) {
+    set_error("alg_attn_bias: k and v must be 16-byte aligned");
     return ALG_EINVAL;
   }
   static PerDeviceOnce attr_set;  // idempotent one-time setup per device; racing first calls both succeed

@@ -703,7 +703,13 @@ int alg_t5_layernorm(const void* x, const void* weight, void* y, int64_t rows, i
  *   == 0) get probability 0, and with `causal` keys j > i too (CLIPTextModel);  p = bf16(softmax_fp32(s));  out = bf16(p v)
  * q / k / v: element (b, i, h, d) at ptr + (b*L + i)*qkv_rstride + h*head_dim + d (three pointers into one fused QKV buffer);
  * out likewise with out_rstride; bias_table: [buckets][heads] bf16 (relative_attention_bias.weight) or NULL;
- * rel_bucket: int32 [2L - 1], the bucket of relative position (key - query); key_mask: int32 [batch][L] or NULL. */
+ * rel_bucket: int32 [2L - 1], the bucket of relative position (key - query); key_mask: int32 [batch][L] or NULL.
+ * A query row without a surviving key (all of its keys masked or causally excluded) is written as zeros (either sign), where
+ * the eager graph gives NaN.  Masked k / v rows are read and multiplied by p = 0: they must be finite.  Nothing outside
+ * out[(b*L + i)*out_rstride + [0, heads*head_dim)] is written.
+ * ALG_EINVAL before any launch: L <= 0, L above the limit, another head_dim, qkv_rstride % 8 != 0, a bias_table without
+ * rel_bucket, k or v not 16-byte aligned (they are read 16 bytes at a time; q and out may sit on any element).  batch == 0
+ * returns ALG_OK and touches nothing. */
 int alg_attn_bias(const void* q, const void* k, const void* v, void* out, const void* bias_table, const int* rel_bucket,
                   const int* key_mask, int batch, int heads, int head_dim, int L, int64_t qkv_rstride, int64_t out_rstride,
                   float scale, int causal, void* stream);

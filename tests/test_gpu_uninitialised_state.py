@@ -85,6 +85,23 @@ def _cases():
         ((wv, yq, vtb, K, M, K, K, K, Mp), dict(bias=bv, batch=1, strideB=M * K, strideC=K * Mp,
                                                flags=_lib.GEMM_BIAS_PER_ROW | _lib.GEMM_PERMUTE_COLS)),
         wq, bq, wq, bq, cos, sin, K // 64, 17, 1e-6, q_scale=0.18), qkb)
+    # the encoder attention (csrc/t5.hip): K^T, V, q and p live in up to 160 KiB of LDS, the key slots [L, Lp) rely on its own
+    # zero fill; one launch per tower's mode, B = 2, H = 3
+    for name, d, L, causal, scale, biased in (("attn_bias d64 bias + mask, L = 226", 64, 226, False, 1.0, True),
+                                              ("attn_bias d64 causal, L = 77", 64, 77, True, 0.125, False),
+                                              ("attn_bias d80, L = 257", 80, 257, False, 80.0 ** -0.5, False)):
+        eB, eH = 2, 3
+        qkv = rn(eB * L, 3 * eH * d, sc=1.0 if scale != 1.0 else 0.3)
+        eo = torch.empty(eB * L, eH * d, dtype=BF, device="cuda")
+        table = rn(32, eH) if biased else None
+        lut = torch.randint(0, 32, (2 * L - 1,), generator=g, device="cuda", dtype=torch.int32) if biased else None
+        emask = None
+        if biased:
+            emask = torch.ones(eB, L, dtype=torch.int32, device="cuda")
+            emask[0, L - 40:] = 0
+            emask[1, 5:90:7] = 0
+        cases[name] = (lambda qkv=qkv, eo=eo, table=table, lut=lut, emask=emask, L=L, d=d, scale=scale, causal=causal:
+                       _lib.attn_bias(qkv, eo, table, lut, emask, eB, eH, L, scale=scale, head_dim=d, causal=causal), eo)
     return cases
 
 
