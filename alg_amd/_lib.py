@@ -41,6 +41,7 @@ EXPORTS = (
     "alg_attn_rows_position_major", "alg_attn_vt_position_major",
     "alg_lora_merge",
     "alg_attn_drift", "alg_attn_drift_workspace_bytes",
+    "alg_attn_merge_lse",
     "alg_cfg_ddim_step_delta", "alg_cfg_combine_delta", "alg_cfg_delta_drift", "alg_cfg_delta_drift_workspace_bytes",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
@@ -134,6 +135,7 @@ def load_library():
     lib.alg_step_cache_probe.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 3
     lib.alg_attn_drift_workspace_bytes.argtypes = [c_int, c_int]
     lib.alg_attn_drift.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
+    lib.alg_attn_merge_lse.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 4 + [c_void_p, c_void_p]
     lib.alg_lora_merge.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                    c_void_p]
     lib.alg_concat_cast.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_int] + [c_int64] * 7 + [
@@ -634,6 +636,48 @@ def attn_drift(a, b, workspace, out):
         raise AlgHipError("attn_drift: the workspace is smaller than attn_drift_workspace_bytes(rows, cols)")
     _check(lib.alg_attn_drift(_ptr(a), _ptr(b), rows, cols, a.stride(0) if rows > 1 else cols, b.stride(0) if rows > 1 else cols,
                               _ptr(workspace), _ptr(out), _stream()), "alg_attn_drift")
+
+
+def attn_merge_lse(o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_rs, far_bs, far_rs, lse_out=None, o_off=0, lse_off=0,
+                   far_off=0, lse_far_off=0, lse_out_off=0):
+    """o <- the exact attention over the union of two disjoint key sets from its two partials (include/alg_hip.h:
+    alg_attn_merge_lse): o (in place: the near partial) and o_far bf16 [batch][Sq][heads * head_dim] with batch / row strides in
+    elements, lse, lse_far and lse_out (optional) contiguous fp32 with room for [batch][heads][Sq] from their offsets, as the
+    _ranges_heads wrappers write them.  Offsets in elements."""
+    what = "attn_merge_lse"
+    batch, heads, head_dim, Sq = int(batch), int(heads), int(head_dim), int(Sq)
+    if min(batch, heads, Sq) < 1 or head_dim not in (64, 128):
+        raise AlgHipError("%s: batch=%d heads=%d Sq=%d must be positive and head_dim=%d 64 or 128" % (what, batch, heads, Sq, head_dim))
+    row = heads * head_dim
+    for name, t, off, bs, rs in (("o", o, o_off, o_bs, o_rs), ("o_far", o_far, far_off, far_bs, far_rs)):
+        _dev(t, what + ": " + name)
+        if t.dtype != torch.bfloat16:
+            raise AlgHipError("%s: %s must be a bfloat16 tensor, got %s" % (what, name, t.dtype))
+        if rs < row or rs % 8 or bs % 8 or off % 8 or min(off, bs) < 0:
+            raise AlgHipError("%s: %s needs a row stride >= heads * head_dim = %d, and row stride, batch stride and offset that are "
+                              "non-negative multiples of 8 (got %d, %d, %d)" % (what, name, row, rs, bs, off))
+        # the last element the launch touches, counted from the tensor's own first element
+        if off + (batch - 1) * bs + (Sq - 1) * rs + row > _span(t):
+            raise AlgHipError("%s: %s (offset %d, batch stride %d, row stride %d) does not hold [%d][%d][%d]"
+                              % (what, name, off, bs, rs, batch, Sq, row))
+    ptrs = []
+    for name, t, off in (("lse", lse, lse_off), ("lse_far", lse_far, lse_far_off), ("lse_out", lse_out, lse_out_off)):
+        if t is None and name == "lse_out":
+            ptrs.append(c_void_p(0))
+            continue
+        _dev(t, what + ": " + name)
+        if t.dtype != torch.float32 or not t.is_contiguous() or off < 0 or t.numel() < off + batch * heads * Sq:
+            raise AlgHipError("%s: %s must be contiguous fp32 with room for [batch][heads][Sq] behind its offset" % (what, name))
+        ptrs.append(c_void_p(t.data_ptr() + 4 * off))
+    at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
+    _check(load_library().alg_attn_merge_lse(at(o, o_off), ptrs[0], at(o_far, far_off), ptrs[1], batch, heads, head_dim, Sq, o_bs, o_rs,
+                                             far_bs, far_rs, ptrs[2], _stream()), "alg_attn_merge_lse")
+    return o
+
+
+def _span(t):
+    """Elements from t's first element to one past its last (a view's strides included)."""
+    return 1 + sum((n - 1) * abs(s) for n, s in zip(t.shape, t.stride())) if t.numel() else 0
 
 
 def step_cache_workspace_bytes(rows, D):

@@ -80,9 +80,12 @@ class KvRanges:
 
     absent_ok=True (opt-in: a head that another launch computes, see head_layout_ranges) also takes the table whose EVERY entry is
     (0, 0): `absent` is then True and the coverage 0; the kernels write zeros and do no other work for such a head.  A table
-    with some blocks empty and others not stays an error."""
+    with some blocks empty and others not stays an error.
 
-    def __init__(self, table, Skv, Sq, absent_ok=False):
+    empty_ok=True (opt-in: the FAR table of the far-field reuse, see complement_ranges) takes blocks without a key next to blocks
+    with keys: the kernels write zeros and an lse of -inf for such a block's rows."""
+
+    def __init__(self, table, Skv, Sq, absent_ok=False, empty_ok=False):
         t = torch.as_tensor(table)
         if t.dtype != torch.int32 or t.dim() != 3 or t.shape[2] != 2 or t.device.type != "cpu":
             raise ValueError("KvRanges takes a CPU int32 table [q_blocks][max_ranges][2], got %s %s" % (t.dtype, tuple(t.shape)))
@@ -117,7 +120,7 @@ class KvRanges:
                                      % (j, i, b, e, prev_end))
                 prev_end = e
                 visited += (e - b) * min(Q_BLOCK, Sq - j * Q_BLOCK)
-            if prev_end is None:
+            if prev_end is None and not empty_ok:
                 raise ValueError("block %d: no key (every block needs at least one range)" % j)
         self.table = t.clone().contiguous()
         self.Skv, self.Sq = Skv, Sq
@@ -663,6 +666,63 @@ def full_ranges(Sq, Skv):
     return KvRanges(t, Skv, Sq)
 
 
+def _block_ranges(kv_ranges):
+    """The used (begin, end) entries of every block of a KvRanges, as lists of tuples."""
+    a = kv_ranges.table.numpy()
+    return [[(int(b), int(e)) for b, e in blk if b or e] for blk in a]
+
+
+def _ranges_table(per_block, Skv, Sq, **kw):
+    """The blocks' range lists as a KvRanges (at least one column; a block may be empty where the keywords allow it)."""
+    max_ranges = max(1, max(len(r) for r in per_block))
+    if max_ranges > MAX_RANGES:
+        raise ValueError("a block needs %d key ranges, the kernels take %d" % (max_ranges, MAX_RANGES))
+    t = torch.zeros(len(per_block), max_ranges, 2, dtype=torch.int32)
+    for j, r in enumerate(per_block):
+        for i, (b, e) in enumerate(r):
+            t[j, i, 0], t[j, i, 1] = b, e
+    return KvRanges(t, Skv, Sq, **kw)
+
+
+def grid_aligned(kv_ranges):
+    """The same table with every END rounded up to a multiple of 64 (clamped to Skv) and touching ranges merged: a superset whose
+    gaps begin on the kernels' key grid, so that complement_ranges can visit exactly the keys it leaves out."""
+    if not isinstance(kv_ranges, KvRanges) or kv_ranges.absent:
+        raise ValueError("grid_aligned takes a KvRanges with keys in every block")
+    Skv = kv_ranges.Skv
+    per_block = []
+    for blk in _block_ranges(kv_ranges):
+        out = []
+        for b, e in blk:
+            e = min(-(-e // KV_ALIGN) * KV_ALIGN, Skv)
+            if out and b <= out[-1][1]:
+                out[-1][1] = max(out[-1][1], e)
+            else:
+                out.append([b, e])
+        per_block.append([tuple(r) for r in out])
+    return _ranges_table(per_block, Skv, kv_ranges.Sq)
+
+
+def complement_ranges(kv_ranges):
+    """The gaps of each block of a grid-aligned table (grid_aligned's result), as a KvRanges(empty_ok=True): with it the two tables
+    visit every key of every block exactly once.  A block whose table already holds every key has no range here.  ValueError
+    for a table whose gaps would not begin on the key grid (the kernels round a begin DOWN: a key would be visited twice)."""
+    if not isinstance(kv_ranges, KvRanges) or kv_ranges.absent:
+        raise ValueError("complement_ranges takes a KvRanges with keys in every block")
+    Skv = kv_ranges.Skv
+    per_block = []
+    for j, blk in enumerate(_block_ranges(kv_ranges)):
+        gaps, at = [], 0
+        for b, e in blk + [(Skv, Skv)]:
+            if b > at:
+                if at % KV_ALIGN:
+                    raise ValueError("block %d: the range ending at %d is not grid-aligned (grid_aligned makes it so)" % (j, at))
+                gaps.append((at, b))
+            at = e
+        per_block.append(gaps)
+    return _ranges_table(per_block, Skv, kv_ranges.Sq, empty_ok=True)
+
+
 def frame_window_ranges(frames, tokens_per_frame, window, sink_frames=1, tail=None, rows=None, prefix=0):
     """The frame-window policy as a KvRanges, or None when it is the dense attention (every block sees every key).
 
@@ -834,6 +894,7 @@ class SelfAttnPlan:
         self.host, self.shared, self.batch = host, list(shared), int(batch)
         self.mode = self.cal = self.full = self.measure = None
         self.bases = self.shared
+        self.far = None       # the forward's attn_far.AttnFarPass (attn_far_reuse), set by the model; None: off
 
     def order(self, table):
         """The balanced LaunchOrder of a per-head table (attn_window_balance), else None."""
@@ -852,6 +913,8 @@ class SelfAttnPlan:
         """End of the forward: on the calibration forward the decisions and the per-head tables (_head_window_finish)."""
         if self.cal is not None:
             self.host._head_window_finish(self.cal, self.bases, batch=self.batch, band_table=band_table)
+        if self.far is not None:
+            self.far.finish()
 
 
 class HeadWindowHost:
@@ -1237,10 +1300,15 @@ def call_transformer(transformer, dense, *args, forward=None, calibrate=False, *
         return fn(*args, **kw)
     saved = transformer.attn_window
     transformer.attn_window = 0
+    far = bool(getattr(transformer, "attn_far_reuse", 0))   # (alg_amd/attn_far.py: a dense step is not a missing window)
+    if far:
+        transformer._attn_dense_step = True
     try:
         return fn(*args, **kw)
     finally:
         transformer.attn_window = saved
+        if far:
+            transformer._attn_dense_step = False
 
 
 def calibration_step(dense_steps):

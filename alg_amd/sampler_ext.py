@@ -1,5 +1,5 @@
 """The samplers' side of the transformers' opt-in extensions -- frame window, per-head windows by recall (balance, widths, band),
-step cache, attention reuse, CFG reuse -- written once for the three ALG loops.  Plain host code: nothing here launches anything.
+step cache, attention reuse, far-field reuse, CFG reuse -- written once for the three ALG loops.  Plain host code: nothing here launches anything.
 
     from_pretrained   `window_switches` validates the keywords before anything is loaded, `apply_switches` sets what was given
     start of a video  `SamplerExtensions(transformer, n_steps, ...)` refuses what does not compose and empties the caches
@@ -13,7 +13,7 @@ from __future__ import annotations
 import functools
 from types import SimpleNamespace
 
-from . import _lib, attn_reuse, cfg_reuse
+from . import _lib, attn_far, attn_reuse, cfg_reuse
 from . import step_cache as _step_cache
 from .attn_window import HeadWindowHost, _balance_policy, _widths_tuple, calibration_step, call_transformer
 
@@ -82,6 +82,8 @@ class SamplerExtensions:
             transformer.reset_step_cache()
         # attention reuse (alg_amd/attn_reuse.py): an empty cache too, the first and the last step are always computed
         self.reuse = attn_reuse.begin_video(transformer, cfg_split)
+        # far-field reuse (alg_amd/attn_far.py): the same drive -- refusals, an empty cache, the first and the last step refresh
+        self.far = attn_far.begin_video(transformer, cfg_split)
         # CFG reuse (alg_amd/cfg_reuse.py): the video's CfgReuse -- no valid delta, an empty record -- or None: off
         self.cfg = cfg_reuse.begin_video(transformer, cfg_split, do_cfg)
         # per-head windows chosen by recall: every video is calibrated anew, on its last dense step
@@ -129,5 +131,9 @@ class SamplerExtensions:
             self.transformer.attn_reuse_advance()
             kw = dict(cache_keys=attn_reuse.step_keys(n_pass, batch, self.host_timestep(t)),
                       cache_force=i == self.last or not self.transformer.attn_reuse_stats)
+        if self.far:
+            self.transformer.attn_far_reuse_advance()
+            kw = dict(cache_keys=attn_far.step_keys(n_pass, batch, self.host_timestep(t)),
+                      cache_force=i == self.last or not self.transformer.attn_far_reuse_stats)
         return functools.partial(call_transformer, self.transformer, i < self.dense_steps, forward=self.forward,
                                  calibrate=self.recall and i == calibration_step(self.dense_steps), **kw)

@@ -36,6 +36,7 @@ from types import SimpleNamespace
 import torch
 
 from . import _lib
+from .attn_far import AttnFarHost
 from .attn_reuse import AttnReuseHost
 from .cfg_reuse import CfgReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
@@ -150,7 +151,7 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
     return sd
 
 
-class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost):
+class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -195,6 +196,10 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost
         # and the attention (the norm and proj_mlp stay: the MLP half needs them).  0: every forward is the plain one, launch for
         # launch, nothing allocated.  attn_reuse_drift: the diagnostic (AttnReuseHost)
         self.attn_reuse = 0
+        # N >= 2 (opt-in, an extension: alg_amd/attn_far.py; needs attn_window > 0): the keys inside the frame window are attended
+        # to fresh on every step, the keys outside it on every N-th step while attn_far_reuse_t_lo < t < attn_far_reuse_t_hi and
+        # from the cached partial (output and LSE) on the steps between, merged by alg_attn_merge_lse.  0: nothing differs
+        self.attn_far_reuse = 0
         self.fp8 = bool(fp8)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
@@ -331,6 +336,8 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost
         from .attn_reuse import apply_switches, switches_from
         reuse = switches_from(_)
         cfg_switches = _cfg_reuse.switches_from(_)
+        from . import attn_far as _attn_far
+        far_switches = _attn_far.switches_from(_)     # attn_far_reuse, attn_far_reuse_t_lo, attn_far_reuse_t_hi
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -346,6 +353,7 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost
         model = _lora.build(cls, cfg, read_shards(root), lora, device, fp8_attention=fp8_attention, fp8=fp8)
         apply_switches(model, reuse)
         _cfg_reuse.apply_switches(model, cfg_switches)
+        _attn_far.apply_switches(model, far_switches)
         return model
 
     def to(self, *a, **k):
@@ -455,7 +463,9 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost
             ops = SelfAttnOperands(128, ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D,
                                    D * ws.J_pad, ws.J_pad, J * AM, AM, scale, q_off=b * J * 2 * D, k_off=b * J * 2 * D + D,
                                    vt_off=b * D * ws.J_pad, o_off=b * J * AM)
-            if plan.cal is not None:   # the calibration forward: the recall over the latent queries only
+            if plan.far is not None:   # attn_far_reuse: near launch, (far launch,) merge of sample b
+                plan.far.attention(direct, "attn_self", ops, bi, group=b, sample0=b)
+            elif plan.cal is not None:   # the calibration forward: the recall over the latent queries only
                 calibrate_self_attention(direct, "attn_self", ops, plan.cal, bi, N, b, (0, S), plan.full[b], plan.measure[b])
             else:
                 launch_self_attention(direct, "attn_self", ops, *plan.layer(bi, b))
@@ -578,6 +588,8 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, CfgReuseHost, HeadWindowHost
                                      table_of=lambda b, w_: self._window_ranges(F_, first, valid[b], J, window=w_),
                                      profile_of=lambda b, ws_: self._profile_table(F_, first, ws_, (valid[b], J),
                                                                                    tail=(S, S + valid[b]), rows=J))
+        # far-field reuse (alg_amd/attn_far.py): None -- off (or a dense step, or a window that covers the video)
+        plan.far = self._attn_far_begin(cache_keys, cache_force, kvr, N, len(self.dual) + len(self.single), heads, 128, J)
         attention = lambda bi: self._joint_attention(ws, plan, bi, valid, S, scale)
         # attention reuse (alg_amd/attn_reuse.py): None -- off, nothing below differs from the plain forward.  An entry holds the J
         # joint rows (latents, then prompt) of every block; att_rows: their place in the front columns of ws.am, per sample

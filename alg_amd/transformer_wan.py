@@ -32,6 +32,7 @@ import torch
 
 from . import _lib
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention, position_band_ranges
+from .attn_far import AttnFarHost
 from .attn_reuse import AttnReuseHost
 from .cfg_reuse import CfgReuseHost
 from .step_cache import StepCacheHost
@@ -155,7 +156,7 @@ def k_scale_bound(norm_weight, norm_dim, heads, rope):
     return (w * (1.02 * math.sqrt(norm_dim * (2.0 if rope else 1.0)) / 448.0)).contiguous()
 
 
-class WanTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWindowHost):
+class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -190,6 +191,10 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWind
         # whatever form it runs; the cross-attention and the feed-forward run as ever.  0: every forward is the plain one, launch
         # for launch, nothing allocated.  attn_reuse_drift: the diagnostic (AttnReuseHost)
         self.attn_reuse = 0
+        # N >= 2 (opt-in, an extension: alg_amd/attn_far.py; needs attn_window > 0): the keys inside the frame window are attended
+        # to fresh on every step, the keys outside it on every N-th step while attn_far_reuse_t_lo < t < attn_far_reuse_t_hi and
+        # from the cached partial (output and LSE) on the steps between, merged by alg_attn_merge_lse.  0: nothing differs
+        self.attn_far_reuse = 0
         # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): the self-attention of every block
         # attends to the conditioning frames (attn_sink_frames) and to the latent frames within attn_window of the query block's
         # own, as ONE alg_flash_attn_d128_ranges launch for the whole batch.  0: today's launches, nothing allocated
@@ -308,6 +313,8 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWind
         from .attn_reuse import apply_switches, switches_from
         reuse = switches_from(_)
         cfg_switches = _cfg_reuse.switches_from(_)
+        from . import attn_far as _attn_far
+        far_switches = _attn_far.switches_from(_)     # attn_far_reuse, attn_far_reuse_t_lo, attn_far_reuse_t_hi
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -322,6 +329,7 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWind
         model = _lora.build(cls, cfg, read_shards(root), lora, device, fp8=fp8, fp8_attention=fp8_attention)
         apply_switches(model, reuse)
         _cfg_reuse.apply_switches(model, cfg_switches)
+        _attn_far.apply_switches(model, far_switches)
         return model
 
     def to(self, *args, **kwargs):
@@ -450,6 +458,8 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWind
         D, heads, S_pad = self.config.dim, self.config.num_attention_heads, ws.S_pad
         ops = SelfAttnOperands(128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad,
                                S * D, D, scale, k_off=D)
+        if plan.far is not None:   # attn_far_reuse: near launch, (far launches,) merge
+            return plan.far.attention(T, "attn_self", ops, li)
         cal = plan.cal
         if cal is not None:   # the calibration forward: the dense output, the window's recall
             calibrate_self_attention(T, "attn_self", ops, cal, li, N, 0, (0, S), plan.full[0], plan.measure[0])
@@ -575,6 +585,8 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, CfgReuseHost, HeadWind
                                      heads, S, (N, S, D), batch=N, band=band if band_t is not None else 0,
                                      table_of=lambda g, w_: self._window_ranges(F_, S // F_, window=w_),
                                      profile_of=lambda g, ws_: self._profile_table(F_, S // F_, ws_))
+        # far-field reuse (alg_amd/attn_far.py): None -- off (or a dense step, or a window that covers the video)
+        plan.far = self._attn_far_begin(cache_keys, cache_force, [kvr], N, len(self.blocks), heads, 128, S)
         for li, L in enumerate(self.blocks):
             if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
                 break                 # hit: x = x1 + the cached tail, straight to the head

@@ -209,6 +209,25 @@ int64_t alg_attn_drift_workspace_bytes(int rows, int cols);
 int alg_attn_drift(const void* a, const void* b, int rows, int cols, int64_t a_rstride, int64_t b_rstride, void* work, double* out,
                    void* stream);
 
+/* Far-field attention reuse (an extension: alg_amd/attn_far.py) -- the merge of two partial attentions over DISJOINT key sets.
+ * o: bf16 [batch][Sq][heads * head_dim], batch and row strides in ELEMENTS, IN PLACE: the near partial on entry, the merged
+ * attention on return; o_far: the same shape with its own strides; lse, lse_far, lse_out: fp32 [batch][heads][Sq], contiguous, the
+ * log2-domain log-sum-exp of the keys each partial visited, exactly as alg_flash_attn_d64_ranges_heads and
+ * alg_flash_attn_d128_ranges_heads write it.  head_dim: 64 or 128.  For every (b, h, q), with a = lse and f = lse_far:
+ *   f == -inf               the row of o keeps its BITS (it is not written)
+ *   a == -inf, f finite     the row of o becomes the far row's bits
+ *   otherwise               m = max(a, f), wa = exp2(a - m), wf = exp2(f - m),
+ *                           o = bf16_rne((wa * o + wf * o_far) / (wa + wf))   in fp32, no contraction: ONE rounding to bf16
+ *                           a weight that underflows to 0 gives the other side's bits, as above
+ *   lse_out (may be NULL)   m + log2(wa + wf); -inf when both are; it may be lse itself
+ * Every output element is a function of its own operands alone (16-byte accesses, a capped grid with a grid-stride loop, vector
+ * stores only, no atomics, no scratch): run-to-run bit-identical.  Enqueue-only, allocation-free.  Bytes between heads * head_dim and
+ * a row stride are neither read nor written.  ALG_EINVAL before anything is launched: batch, heads or Sq < 1; head_dim not 64 / 128;
+ * a row stride below heads * head_dim or not a multiple of 8; a batch stride that is not a multiple of 8 or (batch > 1) does not
+ * hold a sample's rows; a null pointer (except lse_out); o or o_far not 16-byte aligned, an lse not 4-byte aligned. */
+int alg_attn_merge_lse(void* o, const float* lse, const void* o_far, const float* lse_far, int batch, int heads, int head_dim, int Sq,
+                       int64_t o_bstride, int64_t o_rstride, int64_t far_bstride, int64_t far_rstride, float* lse_out, void* stream);
+
 /* LoRA merge at load time (an extension; the reference pipelines inherit diffusers' LoRA loader mixins; alg_amd/lora.py merges
  * the adapters into the state dict BEFORE a transformer is built from it, so no forward path knows about them):
  *   t[n, r]   = double(scale[r]) * double(B[n, r])                exact
