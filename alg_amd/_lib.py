@@ -42,6 +42,7 @@ EXPORTS = (
     "alg_lora_merge",
     "alg_attn_drift", "alg_attn_drift_workspace_bytes",
     "alg_attn_merge_lse",
+    "alg_attn_pool_k", "alg_attn_pool_vt", "alg_attn_merge_lse_shift",
     "alg_cfg_ddim_step_delta", "alg_cfg_combine_delta", "alg_cfg_delta_drift", "alg_cfg_delta_drift_workspace_bytes",
 )
 _RET_I64 = ("alg_vae_groupnorm_workspace", "alg_lowpass_tables_bytes", "alg_down_up_workspace_bytes",
@@ -136,6 +137,9 @@ def load_library():
     lib.alg_attn_drift_workspace_bytes.argtypes = [c_int, c_int]
     lib.alg_attn_drift.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
     lib.alg_attn_merge_lse.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 4 + [c_void_p, c_void_p]
+    lib.alg_attn_merge_lse_shift.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_int64] * 4 + [c_float, c_void_p, c_void_p]
+    lib.alg_attn_pool_k.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64] + [c_int] * 5 + [c_void_p]
+    lib.alg_attn_pool_vt.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64] + [c_int] * 5 + [c_void_p]
     lib.alg_lora_merge.argtypes = [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                    c_void_p]
     lib.alg_concat_cast.argtypes = [POINTER(c_void_p), c_int, POINTER(c_void_p), c_int, c_int] + [c_int64] * 7 + [
@@ -644,7 +648,23 @@ def attn_merge_lse(o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_r
     alg_attn_merge_lse): o (in place: the near partial) and o_far bf16 [batch][Sq][heads * head_dim] with batch / row strides in
     elements, lse, lse_far and lse_out (optional) contiguous fp32 with room for [batch][heads][Sq] from their offsets, as the
     _ranges_heads wrappers write them.  Offsets in elements."""
-    what = "attn_merge_lse"
+    return _attn_merge_lse("attn_merge_lse", None, o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_rs, far_bs, far_rs, lse_out,
+                           o_off, lse_off, far_off, lse_far_off, lse_out_off)
+
+
+def attn_merge_lse_shift(o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_rs, far_bs, far_rs, far_lse_shift, lse_out=None,
+                         o_off=0, lse_off=0, far_off=0, lse_far_off=0, lse_out_off=0):
+    """attn_merge_lse with far_lse_shift (a finite float) added to every far log-sum-exp: far keys that each stand for
+    2^far_lse_shift keys (include/alg_hip.h: alg_attn_merge_lse_shift).  A shift of 0 gives attn_merge_lse's bits."""
+    shift = float(far_lse_shift)
+    if shift != shift or shift in (float("inf"), float("-inf")):
+        raise AlgHipError("attn_merge_lse_shift: far_lse_shift must be finite, got %r" % (far_lse_shift,))
+    return _attn_merge_lse("attn_merge_lse_shift", shift, o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_rs, far_bs, far_rs,
+                           lse_out, o_off, lse_off, far_off, lse_far_off, lse_out_off)
+
+
+def _attn_merge_lse(what, shift, o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_rs, far_bs, far_rs, lse_out, o_off,
+                    lse_off, far_off, lse_far_off, lse_out_off):
     batch, heads, head_dim, Sq = int(batch), int(heads), int(head_dim), int(Sq)
     if min(batch, heads, Sq) < 1 or head_dim not in (64, 128):
         raise AlgHipError("%s: batch=%d heads=%d Sq=%d must be positive and head_dim=%d 64 or 128" % (what, batch, heads, Sq, head_dim))
@@ -670,9 +690,57 @@ def attn_merge_lse(o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bs, o_r
             raise AlgHipError("%s: %s must be contiguous fp32 with room for [batch][heads][Sq] behind its offset" % (what, name))
         ptrs.append(c_void_p(t.data_ptr() + 4 * off))
     at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
-    _check(load_library().alg_attn_merge_lse(at(o, o_off), ptrs[0], at(o_far, far_off), ptrs[1], batch, heads, head_dim, Sq, o_bs, o_rs,
-                                             far_bs, far_rs, ptrs[2], _stream()), "alg_attn_merge_lse")
+    if shift is None:
+        _check(load_library().alg_attn_merge_lse(at(o, o_off), ptrs[0], at(o_far, far_off), ptrs[1], batch, heads, head_dim, Sq, o_bs,
+                                                 o_rs, far_bs, far_rs, ptrs[2], _stream()), "alg_attn_merge_lse")
+    else:
+        _check(load_library().alg_attn_merge_lse_shift(at(o, o_off), ptrs[0], at(o_far, far_off), ptrs[1], batch, heads, head_dim, Sq,
+                                                       o_bs, o_rs, far_bs, far_rs, shift, ptrs[2], _stream()),
+               "alg_attn_merge_lse_shift")
     return o
+
+
+def _attn_pool(what, entry, src, dst, batch, heads, head_dim, S, group, src_bs, src_rs, dst_bs, dst_rs, src_off, dst_off, vt):
+    batch, heads, head_dim, S, group = int(batch), int(heads), int(head_dim), int(S), int(group)
+    if min(batch, heads) < 1 or head_dim not in (64, 128) or group not in (2, 4, 8) or S < group:
+        raise AlgHipError("%s: batch=%d heads=%d must be positive, head_dim=%d 64 or 128, group=%d 2, 4 or 8 and S=%d at least one "
+                          "group" % (what, batch, heads, head_dim, group, S))
+    row = heads * head_dim
+    P_pad = -(-(S // group) // 64) * 64
+    S_pad = -(-S // 64) * 64
+    # (rows, the width of a row, the least row stride) of the source and of the destination
+    shapes = ((row, S_pad, S_pad), (row, P_pad, P_pad)) if vt else ((S, row, row), (P_pad, row, row))
+    for name, t, off, bs, rs, (n, width, least) in (("src", src, src_off, src_bs, src_rs, shapes[0]),
+                                                    ("dst", dst, dst_off, dst_bs, dst_rs, shapes[1])):
+        _dev(t, what + ": " + name)
+        if t.dtype != torch.bfloat16:
+            raise AlgHipError("%s: %s must be a bfloat16 tensor, got %s" % (what, name, t.dtype))
+        if rs < least or rs % 8 or bs % 8 or off % 8 or min(off, bs) < 0:
+            raise AlgHipError("%s: %s needs a row stride >= %d, and row stride, batch stride and offset that are non-negative "
+                              "multiples of 8 (got %d, %d, %d)" % (what, name, least, rs, bs, off))
+        if off + (batch - 1) * bs + (n - 1) * rs + width > _span(t):
+            raise AlgHipError("%s: %s (offset %d, batch stride %d, row stride %d) does not hold [%d][%d][%d]"
+                              % (what, name, off, bs, rs, batch, n, width))
+    at = lambda t, off: c_void_p(t.data_ptr() + 2 * off)
+    _check(getattr(load_library(), entry)(at(src, src_off), src_bs, src_rs, at(dst, dst_off), dst_bs, dst_rs, batch, heads, head_dim, S,
+                                          group, _stream()), entry)
+    return dst
+
+
+def attn_pool_k(src, dst, batch, heads, head_dim, S, group, src_bs, src_rs, dst_bs, dst_rs, src_off=0, dst_off=0):
+    """dst <- the K rows of src pooled by `group` (2, 4, 8) along the key axis (include/alg_hip.h: alg_attn_pool_k): src bf16
+    [batch][S][heads * head_dim], dst [batch][S // group rounded up to 64][heads * head_dim], the rows behind S // group zero.
+    Strides and offsets in elements."""
+    return _attn_pool("attn_pool_k", "alg_attn_pool_k", src, dst, batch, heads, head_dim, S, group, src_bs, src_rs, dst_bs, dst_rs,
+                      src_off, dst_off, False)
+
+
+def attn_pool_vt(src, dst, batch, heads, head_dim, S, group, src_bs, src_rs, dst_bs, dst_rs, src_off=0, dst_off=0):
+    """dst <- V^T (bf16 [batch][heads * head_dim][S padded to 64], key axis permuted as the attention entries expect) pooled by
+    `group` along the key axis, in the same permuted layout, [..][S // group rounded up to 64] columns, those behind S // group
+    zero (include/alg_hip.h: alg_attn_pool_vt).  Strides and offsets in elements."""
+    return _attn_pool("attn_pool_vt", "alg_attn_pool_vt", src, dst, batch, heads, head_dim, S, group, src_bs, src_rs, dst_bs, dst_rs,
+                      src_off, dst_off, True)
 
 
 def _span(t):

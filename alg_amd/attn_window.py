@@ -684,23 +684,51 @@ def _ranges_table(per_block, Skv, Sq, **kw):
     return KvRanges(t, Skv, Sq, **kw)
 
 
-def grid_aligned(kv_ranges):
+def grid_aligned(kv_ranges, grid=KV_ALIGN):
     """The same table with every END rounded up to a multiple of 64 (clamped to Skv) and touching ranges merged: a superset whose
-    gaps begin on the kernels' key grid, so that complement_ranges can visit exactly the keys it leaves out."""
+    gaps begin on the kernels' key grid, so that complement_ranges can visit exactly the keys it leaves out.
+
+    grid (a multiple of 64; attn_pool.py: 64 G) > 64: every BEGIN is rounded down and every end up to a multiple of `grid`, and
+    every block also gets the keys behind the last multiple of `grid`, [Skv - Skv % grid, Skv): every gap then begins AND ends on
+    that grid, so a group of G = grid / 64 consecutive keys lies on one side of every cut."""
     if not isinstance(kv_ranges, KvRanges) or kv_ranges.absent:
         raise ValueError("grid_aligned takes a KvRanges with keys in every block")
+    grid = int(grid)
+    if grid < KV_ALIGN or grid % KV_ALIGN:
+        raise ValueError("grid_aligned: grid=%d must be a positive multiple of %d" % (grid, KV_ALIGN))
     Skv = kv_ranges.Skv
     per_block = []
     for blk in _block_ranges(kv_ranges):
+        if grid != KV_ALIGN and Skv % grid:
+            blk = blk + [(Skv - Skv % grid, Skv)]
         out = []
         for b, e in blk:
-            e = min(-(-e // KV_ALIGN) * KV_ALIGN, Skv)
+            b, e = b - b % grid, min(-(-e // grid) * grid, Skv)
             if out and b <= out[-1][1]:
                 out[-1][1] = max(out[-1][1], e)
             else:
                 out.append([b, e])
         per_block.append([tuple(r) for r in out])
     return _ranges_table(per_block, Skv, kv_ranges.Sq)
+
+
+def pooled_ranges(far, group, Skv=None):
+    """The far table of complement_ranges(grid_aligned(table, grid=64 * group)) with every begin and end divided by `group`: the
+    ranges of the POOLED keys (pooled key p stands for the keys [p group, (p + 1) group)), on the kernels' 64-key grid, as a
+    KvRanges(empty_ok=True) for the same queries.  Skv: the key count the launch will state (default: the far table's keys
+    divided by group; the d = 64 entries have one S for queries and keys and state Sq).  ValueError for a table with a begin or
+    an end off the 64 group grid: a pooled key would then stand for keys that the near table visits too."""
+    group = int(group)
+    if not isinstance(far, KvRanges) or group < 1:
+        raise ValueError("pooled_ranges takes a KvRanges and a group >= 1")
+    per_block = []
+    for j, blk in enumerate(_block_ranges(far)):
+        for b, e in blk:
+            if b % (KV_ALIGN * group) or e % (KV_ALIGN * group):
+                raise ValueError("block %d: the far range (%d, %d) does not lie on the %d-key grid (grid_aligned(table, grid=%d) "
+                                 "makes it so)" % (j, b, e, KV_ALIGN * group, KV_ALIGN * group))
+        per_block.append([(b // group, e // group) for b, e in blk])
+    return _ranges_table(per_block, far.Skv // group if Skv is None else int(Skv), far.Sq, empty_ok=True)
 
 
 def complement_ranges(kv_ranges):
@@ -894,7 +922,8 @@ class SelfAttnPlan:
         self.host, self.shared, self.batch = host, list(shared), int(batch)
         self.mode = self.cal = self.full = self.measure = None
         self.bases = self.shared
-        self.far = None       # the forward's attn_far.AttnFarPass (attn_far_reuse), set by the model; None: off
+        self.far = None       # the forward's attn_far.AttnFarPass (attn_far_reuse) or attn_pool.AttnPoolPass (attn_far_pool), set by
+                              # the model; None: off
 
     def order(self, table):
         """The balanced LaunchOrder of a per-head table (attn_window_balance), else None."""
@@ -1300,7 +1329,8 @@ def call_transformer(transformer, dense, *args, forward=None, calibrate=False, *
         return fn(*args, **kw)
     saved = transformer.attn_window
     transformer.attn_window = 0
-    far = bool(getattr(transformer, "attn_far_reuse", 0))   # (alg_amd/attn_far.py: a dense step is not a missing window)
+    # (alg_amd/attn_far.py, alg_amd/attn_pool.py: a dense step is not a missing window)
+    far = bool(getattr(transformer, "attn_far_reuse", 0) or getattr(transformer, "attn_far_pool", 0))
     if far:
         transformer._attn_dense_step = True
     try:

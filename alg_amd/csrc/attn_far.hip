@@ -19,7 +19,8 @@ template <int HD>
 __global__ __launch_bounds__(AF_THREADS) void attn_merge_lse_kernel(uint4* __restrict__ o, const float* __restrict__ lse,
                                                                     const uint4* __restrict__ o_far, const float* __restrict__ lse_far,
                                                                     int heads, int Sq, int64_t nvec, int64_t o_bvs, int64_t o_rvs,
-                                                                    int64_t far_bvs, int64_t far_rvs, float* __restrict__ lse_out) {
+                                                                    int64_t far_bvs, int64_t far_rvs, float* __restrict__ lse_out,
+                                                                    float far_shift) {
   constexpr int VPH = HD / 8;   // 16-byte vectors per head
   const int64_t stride = (int64_t)gridDim.x * AF_THREADS;
   for (int64_t v = (int64_t)blockIdx.x * AF_THREADS + threadIdx.x; v < nvec; v += stride) {
@@ -31,7 +32,8 @@ __global__ __launch_bounds__(AF_THREADS) void attn_merge_lse_kernel(uint4* __res
     const int q = (int)(t % Sq);
     const int64_t b = t / Sq;
     const int64_t li = (b * heads + h) * Sq + q;
-    const float a = lse[li], f = lse_far[li];
+    // far_shift (alg_attn_merge_lse_shift: every far key stands for 2^far_shift keys); 0 leaves the far LSE's bits
+    const float a = lse[li], f = far_shift != 0.0f ? lse_far[li] + far_shift : lse_far[li];
     const float m = fmaxf(a, f);
     float wa = 0.0f, wf = 0.0f;   // both -inf: nothing to merge, o keeps its bits
     if (m != -INFINITY) {
@@ -56,39 +58,36 @@ __global__ __launch_bounds__(AF_THREADS) void attn_merge_lse_kernel(uint4* __res
   }
 }
 
-}  // namespace alg
-
-using namespace alg;
-
-extern "C" int alg_attn_merge_lse(void* o, const float* lse, const void* o_far, const float* lse_far, int batch, int heads,
-                                  int head_dim, int Sq, int64_t o_bstride, int64_t o_rstride, int64_t far_bstride,
-                                  int64_t far_rstride, float* lse_out, void* stream) {
+// Both entries run this (alg_attn_merge_lse_shift lives in attn_pool.hip): `what` names the caller in the error text.
+int merge_lse_entry(const char* what, void* o, const float* lse, const void* o_far, const float* lse_far, int batch, int heads,
+                    int head_dim, int Sq, int64_t o_bstride, int64_t o_rstride, int64_t far_bstride, int64_t far_rstride,
+                    float far_shift, float* lse_out, void* stream) {
   if (batch <= 0 || heads <= 0 || Sq <= 0) {
-    set_error("alg_attn_merge_lse: bad argument (batch=%d heads=%d Sq=%d must be positive)", batch, heads, Sq);
+    set_error("%s: bad argument (batch=%d heads=%d Sq=%d must be positive)", what, batch, heads, Sq);
     return ALG_EINVAL;
   }
   if (head_dim != 64 && head_dim != 128) {
-    set_error("alg_attn_merge_lse: head_dim=%d (64 or 128)", head_dim);
+    set_error("%s: head_dim=%d (64 or 128)", what, head_dim);
     return ALG_EINVAL;
   }
   const int64_t row = (int64_t)heads * head_dim;
   if (o_rstride < row || far_rstride < row || o_rstride % 8 || far_rstride % 8) {
-    set_error("alg_attn_merge_lse: row strides o=%lld far=%lld must be multiples of 8 elements and at least heads * head_dim = %lld",
+    set_error("%s: row strides o=%lld far=%lld must be multiples of 8 elements and at least heads * head_dim = %lld", what,
               (long long)o_rstride, (long long)far_rstride, (long long)row);
     return ALG_EINVAL;
   }
   if (o_bstride < 0 || far_bstride < 0 || o_bstride % 8 || far_bstride % 8 ||
       (batch > 1 && (o_bstride < (Sq - 1) * o_rstride + row || far_bstride < (Sq - 1) * far_rstride + row))) {
-    set_error("alg_attn_merge_lse: batch strides o=%lld far=%lld must be multiples of 8 elements and hold the Sq=%d rows of a sample",
+    set_error("%s: batch strides o=%lld far=%lld must be multiples of 8 elements and hold the Sq=%d rows of a sample", what,
               (long long)o_bstride, (long long)far_bstride, Sq);
     return ALG_EINVAL;
   }
   if (!o || !lse || !o_far || !lse_far) {
-    set_error("alg_attn_merge_lse: null pointer");
+    set_error("%s: null pointer", what);
     return ALG_EINVAL;
   }
   if (((uintptr_t)o | (uintptr_t)o_far) & 15 || ((uintptr_t)lse | (uintptr_t)lse_far | (uintptr_t)lse_out) & 3) {
-    set_error("alg_attn_merge_lse: o and o_far must be 16-byte aligned, lse, lse_far and lse_out 4-byte aligned");
+    set_error("%s: o and o_far must be 16-byte aligned, lse, lse_far and lse_out 4-byte aligned", what);
     return ALG_EINVAL;
   }
   const int64_t nvec = (int64_t)batch * Sq * (row / 8);
@@ -96,9 +95,20 @@ extern "C" int alg_attn_merge_lse(void* o, const float* lse, const void* o_far, 
   hipStream_t s = (hipStream_t)stream;
   if (head_dim == 64)
     hipLaunchKernelGGL(attn_merge_lse_kernel<64>, grid, block, 0, s, (uint4*)o, lse, (const uint4*)o_far, lse_far, heads, Sq, nvec,
-                       o_bstride / 8, o_rstride / 8, far_bstride / 8, far_rstride / 8, lse_out);
+                       o_bstride / 8, o_rstride / 8, far_bstride / 8, far_rstride / 8, lse_out, far_shift);
   else
     hipLaunchKernelGGL(attn_merge_lse_kernel<128>, grid, block, 0, s, (uint4*)o, lse, (const uint4*)o_far, lse_far, heads, Sq, nvec,
-                       o_bstride / 8, o_rstride / 8, far_bstride / 8, far_rstride / 8, lse_out);
-  return check_launch("alg_attn_merge_lse");
+                       o_bstride / 8, o_rstride / 8, far_bstride / 8, far_rstride / 8, lse_out, far_shift);
+  return check_launch(what);
+}
+
+}  // namespace alg
+
+using namespace alg;
+
+extern "C" int alg_attn_merge_lse(void* o, const float* lse, const void* o_far, const float* lse_far, int batch, int heads,
+                                  int head_dim, int Sq, int64_t o_bstride, int64_t o_rstride, int64_t far_bstride,
+                                  int64_t far_rstride, float* lse_out, void* stream) {
+  return merge_lse_entry("alg_attn_merge_lse", o, lse, o_far, lse_far, batch, heads, head_dim, Sq, o_bstride, o_rstride, far_bstride,
+                         far_rstride, 0.0f, lse_out, stream);
 }

@@ -29,7 +29,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import numpy as np
 import torch
 
-from . import _lib, attn_far, attn_reuse, cfg_reuse, lp_utils, sampler_ext
+from . import _lib, attn_far, attn_pool, attn_reuse, cfg_reuse, lp_utils, sampler_ext
 from .pipeline_cogvideox_image2video_lowpass import retrieve_timesteps
 from .schedulers import FlowMatchEulerDiscreteScheduler
 
@@ -140,6 +140,10 @@ class HunyuanVideoImageToVideoPipeline:
         reuse_kw.update(attn_far.pipeline_switches(_, reuse_kw, attn_window=attn_window, attn_window_recall=attn_window_recall,
                                                     attn_window_balance=attn_window_balance,
                                                     attn_window_widths=attn_window_widths, fp8_attention=fp8_attention))
+        # pooled far field (alg_amd/attn_pool.py): its trailing keyword, refused here where it does not compose
+        reuse_kw.update(attn_pool.pipeline_switches(_, reuse_kw, attn_window=attn_window, attn_window_recall=attn_window_recall,
+                                                     attn_window_balance=attn_window_balance,
+                                                     attn_window_widths=attn_window_widths, fp8_attention=fp8_attention))
         switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths)
 
         from .schedulers import FlowMatchEulerDiscreteScheduler

@@ -30,7 +30,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 
 import torch
 
-from . import _lib, attn_far, attn_reuse, cfg_reuse, lp_utils, sampler_ext
+from . import _lib, attn_far, attn_pool, attn_reuse, cfg_reuse, lp_utils, sampler_ext
 from .schedulers import UniPCMultistepScheduler
 
 
@@ -123,6 +123,10 @@ class WanImageToVideoPipeline:
                                                     attn_window_balance=attn_window_balance,
                                                     attn_window_widths=attn_window_widths, attn_band=attn_band, fp8_attention=fp8_attention,
                                                     step_cache=step_cache))
+        # pooled far field (alg_amd/attn_pool.py): its trailing keyword, refused here where it does not compose
+        reuse_kw.update(attn_pool.pipeline_switches(_, reuse_kw, attn_window=attn_window, attn_window_recall=attn_window_recall,
+                                                     attn_window_balance=attn_window_balance,
+                                                     attn_window_widths=attn_window_widths, attn_band=attn_band, fp8_attention=fp8_attention))
         switches = sampler_ext.window_switches(attn_window, attn_window_recall, attn_window_balance, attn_window_widths, attn_band,
                                                fp8_attention, step_cache=step_cache)
 

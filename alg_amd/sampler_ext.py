@@ -1,5 +1,5 @@
 """The samplers' side of the transformers' opt-in extensions -- frame window, per-head windows by recall (balance, widths, band),
-step cache, attention reuse, far-field reuse, CFG reuse -- written once for the three ALG loops.  Plain host code: nothing here launches anything.
+step cache, attention reuse, far-field reuse, pooled far field, CFG reuse -- written once for the three ALG loops.  Plain host code: nothing here launches anything.
 
     from_pretrained   `window_switches` validates the keywords before anything is loaded, `apply_switches` sets what was given
     start of a video  `SamplerExtensions(transformer, n_steps, ...)` refuses what does not compose and empties the caches
@@ -13,7 +13,7 @@ from __future__ import annotations
 import functools
 from types import SimpleNamespace
 
-from . import _lib, attn_far, attn_reuse, cfg_reuse
+from . import _lib, attn_far, attn_pool, attn_reuse, cfg_reuse
 from . import step_cache as _step_cache
 from .attn_window import HeadWindowHost, _balance_policy, _widths_tuple, calibration_step, call_transformer
 
@@ -84,6 +84,8 @@ class SamplerExtensions:
         self.reuse = attn_reuse.begin_video(transformer, cfg_split)
         # far-field reuse (alg_amd/attn_far.py): the same drive -- refusals, an empty cache, the first and the last step refresh
         self.far = attn_far.begin_video(transformer, cfg_split)
+        # pooled far field (alg_amd/attn_pool.py): the refusals only -- no state crosses a step, nothing to drive
+        attn_pool.begin_video(transformer)
         # CFG reuse (alg_amd/cfg_reuse.py): the video's CfgReuse -- no valid delta, an empty record -- or None: off
         self.cfg = cfg_reuse.begin_video(transformer, cfg_split, do_cfg)
         # per-head windows chosen by recall: every video is calibrated anew, on its last dense step

@@ -44,6 +44,7 @@ import torch
 
 from . import _lib
 from .attn_far import AttnFarHost
+from .attn_pool import AttnPoolHost
 from .attn_reuse import AttnReuseHost
 from .cfg_reuse import CfgReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
@@ -91,7 +92,7 @@ def _bf(t, device):
     return t.to(device=device, dtype=torch.bfloat16).contiguous()
 
 
-class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseHost, HeadWindowHost):
+class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, AttnPoolHost, CfgReuseHost, HeadWindowHost):
     dtype = torch.bfloat16
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -169,6 +170,10 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, Cfg
         # to fresh on every step, the keys outside it on every N-th step while attn_far_reuse_t_lo < t < attn_far_reuse_t_hi and
         # from the cached partial (output and LSE) on the steps between, merged by alg_attn_merge_lse.  0: nothing differs
         self.attn_far_reuse = 0
+        # G in {2, 4, 8} (opt-in, an extension: alg_amd/attn_pool.py; needs attn_window > 0): the keys outside the frame window are
+        # attended to on every step as groups of G consecutive keys pooled into one (mean k, mean v, a score bias of log2 G), merged
+        # with the window's partial by alg_attn_merge_lse_shift.  No state across steps.  0: nothing differs
+        self.attn_far_pool = 0
         # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): in the joint attention of every block a
         # block of latent queries attends to the prompt keys, to the conditioning frames (attn_sink_frames) and to the latent frames
         # within attn_window of its own; prompt queries see everything.  ONE alg_flash_attn_d64_ranges launch for the whole batch.
@@ -373,11 +378,14 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, Cfg
         cfg_switches = _cfg_reuse.switches_from(_)
         from . import attn_far as _attn_far
         far_switches = _attn_far.switches_from(_)     # attn_far_reuse, attn_far_reuse_t_lo, attn_far_reuse_t_hi
+        from . import attn_pool as _attn_pool
+        pool_switches = _attn_pool.switches_from(_)   # attn_far_pool
         config, sd = load_diffusers_transformer(path, subfolder)
         model = _lora.build(cls, config, sd, lora, device, fp8=fp8, fp4=fp4)
         apply_switches(model, reuse)
         _cfg_reuse.apply_switches(model, cfg_switches)
         _attn_far.apply_switches(model, far_switches)
+        _attn_pool.apply_switches(model, pool_switches)
         return model
 
     def to(self, *args, **kwargs):
@@ -560,7 +568,7 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, Cfg
         D, Hn, S_pad = self.config.inner_dim, self.config.num_attention_heads, ws["S_pad"]
         ops = SelfAttnOperands(64, ws["qk"], ws["qk"], ws["vt"], ws["att"], N, Hn, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad,
                                S_pad, S * D, D, scale, k_off=D, q_prescaled=prescale)
-        if plan.far is not None:   # attn_far_reuse: near launch, (far launches,) merge
+        if plan.far is not None:   # attn_far_reuse / attn_far_pool: near launch, (far launches,) merge
             return plan.far.attention(self._timed, "attn", ops, li)
         if plan.cal is not None:
             return calibrate_self_attention(self._timed, "attn", ops, plan.cal, li, N, 0, (T, S - T), plan.full[0], plan.measure[0])
@@ -686,7 +694,10 @@ class CogVideoXTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, Cfg
         plan = self._self_attn_begin([kvr], (Fr // p_t, (Hh // p) * (Ww // p), T, int(self.attn_window), int(self.attn_sink_frames)),
                                      len(self.layers), N, Hn, S, (N, S, D), batch=N)
         # far-field reuse (alg_amd/attn_far.py): None -- off (or a dense step, or a window that covers the video)
-        plan.far = self._attn_far_begin(cache_keys, cache_force, [kvr], N, len(self.layers), Hn, 64, S)
+        # pooled far field (alg_amd/attn_pool.py): None -- off (or a dense step, or a window that covers the video); it takes the
+        # place of the far-field reuse in plan.far and refuses to run next to it
+        pool = self._attn_pool_begin([kvr], N, Hn, 64, S)
+        plan.far = pool if pool is not None else self._attn_far_begin(cache_keys, cache_force, [kvr], N, len(self.layers), Hn, 64, S)
         for li, L in enumerate(self.layers):
             if li == 1 and sc is not None and TM("step_cache", sc.after_block0, x):
                 break                 # hit: x = x1 + the cached tail, straight to the head

@@ -37,6 +37,7 @@ import torch
 
 from . import _lib
 from .attn_far import AttnFarHost
+from .attn_pool import AttnPoolHost
 from .attn_reuse import AttnReuseHost
 from .cfg_reuse import CfgReuseHost
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention
@@ -151,7 +152,7 @@ def synthetic_state_dict(cfg, seed=1234, device="cuda"):
     return sd
 
 
-class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, HeadWindowHost):
+class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, AttnPoolHost, CfgReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -200,6 +201,10 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, H
         # to fresh on every step, the keys outside it on every N-th step while attn_far_reuse_t_lo < t < attn_far_reuse_t_hi and
         # from the cached partial (output and LSE) on the steps between, merged by alg_attn_merge_lse.  0: nothing differs
         self.attn_far_reuse = 0
+        # G in {2, 4, 8} (opt-in, an extension: alg_amd/attn_pool.py; needs attn_window > 0): the keys outside the frame window are
+        # attended to on every step as groups of G consecutive keys pooled into one (mean k, mean v, a score bias of log2 G), merged
+        # with the window's partial by alg_attn_merge_lse_shift.  No state across steps.  0: nothing differs
+        self.attn_far_pool = 0
         self.fp8 = bool(fp8)
         if config.qk_norm != "rms_norm" or config.attention_head_dim != 128 or config.patch_size_t != 1:
             raise NotImplementedError("the HunyuanVideo DiT path is built for rms_norm, head_dim 128, patch_size_t 1")
@@ -338,6 +343,8 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, H
         cfg_switches = _cfg_reuse.switches_from(_)
         from . import attn_far as _attn_far
         far_switches = _attn_far.switches_from(_)     # attn_far_reuse, attn_far_reuse_t_lo, attn_far_reuse_t_hi
+        from . import attn_pool as _attn_pool
+        pool_switches = _attn_pool.switches_from(_)   # attn_far_pool
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -354,6 +361,7 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, H
         apply_switches(model, reuse)
         _cfg_reuse.apply_switches(model, cfg_switches)
         _attn_far.apply_switches(model, far_switches)
+        _attn_pool.apply_switches(model, pool_switches)
         return model
 
     def to(self, *a, **k):
@@ -463,7 +471,7 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, H
             ops = SelfAttnOperands(128, ws.qk, ws.qk, ws.vt, ws.am, 1, heads, J, S + valid[b], J * 2 * D, 2 * D, J * 2 * D, 2 * D,
                                    D * ws.J_pad, ws.J_pad, J * AM, AM, scale, q_off=b * J * 2 * D, k_off=b * J * 2 * D + D,
                                    vt_off=b * D * ws.J_pad, o_off=b * J * AM)
-            if plan.far is not None:   # attn_far_reuse: near launch, (far launch,) merge of sample b
+            if plan.far is not None:   # attn_far_reuse / attn_far_pool: near launch, (far launch,) merge of sample b
                 plan.far.attention(direct, "attn_self", ops, bi, group=b, sample0=b)
             elif plan.cal is not None:   # the calibration forward: the recall over the latent queries only
                 calibrate_self_attention(direct, "attn_self", ops, plan.cal, bi, N, b, (0, S), plan.full[b], plan.measure[b])
@@ -589,7 +597,11 @@ class HunyuanVideoTransformer3DModel(AttnReuseHost, AttnFarHost, CfgReuseHost, H
                                      profile_of=lambda b, ws_: self._profile_table(F_, first, ws_, (valid[b], J),
                                                                                    tail=(S, S + valid[b]), rows=J))
         # far-field reuse (alg_amd/attn_far.py): None -- off (or a dense step, or a window that covers the video)
-        plan.far = self._attn_far_begin(cache_keys, cache_force, kvr, N, len(self.dual) + len(self.single), heads, 128, J)
+        # pooled far field (alg_amd/attn_pool.py): None -- off (or a dense step, or a window that covers the video); it takes the
+        # place of the far-field reuse in plan.far and refuses to run next to it
+        pool = self._attn_pool_begin(kvr, N, heads, 128, J)
+        plan.far = pool if pool is not None else self._attn_far_begin(cache_keys, cache_force, kvr, N,
+                                                                      len(self.dual) + len(self.single), heads, 128, J)
         attention = lambda bi: self._joint_attention(ws, plan, bi, valid, S, scale)
         # attention reuse (alg_amd/attn_reuse.py): None -- off, nothing below differs from the plain forward.  An entry holds the J
         # joint rows (latents, then prompt) of every block; att_rows: their place in the front columns of ws.am, per sample

@@ -33,6 +33,7 @@ import torch
 from . import _lib
 from .attn_window import HeadWindowHost, SelfAttnOperands, calibrate_self_attention, launch_self_attention, position_band_ranges
 from .attn_far import AttnFarHost
+from .attn_pool import AttnPoolHost
 from .attn_reuse import AttnReuseHost
 from .cfg_reuse import CfgReuseHost
 from .step_cache import StepCacheHost
@@ -156,7 +157,7 @@ def k_scale_bound(norm_weight, norm_dim, heads, rope):
     return (w * (1.02 * math.sqrt(norm_dim * (2.0 if rope else 1.0)) / 448.0)).contiguous()
 
 
-class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseHost, HeadWindowHost):
+class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, AttnPoolHost, CfgReuseHost, HeadWindowHost):
     dtype = BF
     # what lora.merge_into did to the state dict this model was built from (from_pretrained / from_synthetic(lora=...)): a tuple
     # of lora.LoraReport(name, scale, targets, ranks) per adapter; () without LoRA
@@ -195,6 +196,10 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseH
         # to fresh on every step, the keys outside it on every N-th step while attn_far_reuse_t_lo < t < attn_far_reuse_t_hi and
         # from the cached partial (output and LSE) on the steps between, merged by alg_attn_merge_lse.  0: nothing differs
         self.attn_far_reuse = 0
+        # G in {2, 4, 8} (opt-in, an extension: alg_amd/attn_pool.py; needs attn_window > 0): the keys outside the frame window are
+        # attended to on every step as groups of G consecutive keys pooled into one (mean k, mean v, a score bias of log2 G), merged
+        # with the window's partial by alg_attn_merge_lse_shift.  No state across steps.  0: nothing differs
+        self.attn_far_pool = 0
         # > 0 (opt-in, an extension: alg_amd/attn_window.py; may be flipped between calls): the self-attention of every block
         # attends to the conditioning frames (attn_sink_frames) and to the latent frames within attn_window of the query block's
         # own, as ONE alg_flash_attn_d128_ranges launch for the whole batch.  0: today's launches, nothing allocated
@@ -315,6 +320,8 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseH
         cfg_switches = _cfg_reuse.switches_from(_)
         from . import attn_far as _attn_far
         far_switches = _attn_far.switches_from(_)     # attn_far_reuse, attn_far_reuse_t_lo, attn_far_reuse_t_hi
+        from . import attn_pool as _attn_pool
+        pool_switches = _attn_pool.switches_from(_)   # attn_far_pool
         root = os.path.join(path, subfolder) if subfolder and os.path.isdir(os.path.join(path, subfolder)) else path
         cfg_path = os.path.join(root, "config.json")
         if not os.path.exists(cfg_path):
@@ -330,6 +337,7 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseH
         apply_switches(model, reuse)
         _cfg_reuse.apply_switches(model, cfg_switches)
         _attn_far.apply_switches(model, far_switches)
+        _attn_pool.apply_switches(model, pool_switches)
         return model
 
     def to(self, *args, **kwargs):
@@ -458,7 +466,7 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseH
         D, heads, S_pad = self.config.dim, self.config.num_attention_heads, ws.S_pad
         ops = SelfAttnOperands(128, ws.qk, ws.qk, ws.vt, ws.att, N, heads, S, S, S * 2 * D, 2 * D, S * 2 * D, 2 * D, D * S_pad, S_pad,
                                S * D, D, scale, k_off=D)
-        if plan.far is not None:   # attn_far_reuse: near launch, (far launches,) merge
+        if plan.far is not None:   # attn_far_reuse / attn_far_pool: near launch, (far launches,) merge
             return plan.far.attention(T, "attn_self", ops, li)
         cal = plan.cal
         if cal is not None:   # the calibration forward: the dense output, the window's recall
@@ -586,7 +594,10 @@ class WanTransformer3DModel(StepCacheHost, AttnReuseHost, AttnFarHost, CfgReuseH
                                      table_of=lambda g, w_: self._window_ranges(F_, S // F_, window=w_),
                                      profile_of=lambda g, ws_: self._profile_table(F_, S // F_, ws_))
         # far-field reuse (alg_amd/attn_far.py): None -- off (or a dense step, or a window that covers the video)
-        plan.far = self._attn_far_begin(cache_keys, cache_force, [kvr], N, len(self.blocks), heads, 128, S)
+        # pooled far field (alg_amd/attn_pool.py): None -- off (or a dense step, or a window that covers the video); it takes the
+        # place of the far-field reuse in plan.far and refuses to run next to it
+        pool = self._attn_pool_begin([kvr], N, heads, 128, S)
+        plan.far = pool if pool is not None else self._attn_far_begin(cache_keys, cache_force, [kvr], N, len(self.blocks), heads, 128, S)
         for li, L in enumerate(self.blocks):
             if li == 1 and sc is not None and T("step_cache", sc.after_block0, ws.x):
                 break                 # hit: x = x1 + the cached tail, straight to the head

@@ -228,6 +228,34 @@ int alg_attn_drift(const void* a, const void* b, int rows, int cols, int64_t a_r
 int alg_attn_merge_lse(void* o, const float* lse, const void* o_far, const float* lse_far, int batch, int heads, int head_dim, int Sq,
                        int64_t o_bstride, int64_t o_rstride, int64_t far_bstride, int64_t far_rstride, float* lse_out, void* stream);
 
+/* Pooled far-field attention (an extension: alg_amd/attn_pool.py) -- the far-side operands at 1 / group of their resolution.
+ * Every group of `group` (2, 4 or 8) consecutive keys, aligned to `group` on the absolute key index, becomes one pooled key: the
+ * fp32 sum of its rows in ascending key order, times the exact 1 / group, rounded ONCE to bf16.  P = S / group (floor) pooled
+ * keys; keys behind P * group are not read into any of them; the pooled keys P .. P_pad - 1, P_pad = P rounded up to 64, are
+ * written as zero.  head_dim: 64 or 128; strides in ELEMENTS.
+ *   alg_attn_pool_k   src: bf16 [batch][S][heads * head_dim] rows (a row stride >= heads * head_dim: the K half of a Q|K buffer),
+ *                     dst: bf16 [batch][P_pad][heads * head_dim]; bytes between heads * head_dim and a row stride are neither
+ *                     read nor written
+ *   alg_attn_pool_vt  src: bf16 V^T [batch][heads * head_dim][>= S rounded up to 64], dst: [batch][heads * head_dim][>= P_pad],
+ *                     pooled along the key axis; in both, the keys of every 16 columns are stored with index bits 2 and 3
+ *                     swapped, as the attention entries expect them.  Source columns behind S rounded up to 16 are not read,
+ *                     destination columns behind P_pad not written
+ * Memory-bound: 16-byte accesses on both sides, a capped grid with a grid-stride loop, vector stores only, no atomics, no
+ * scratch; run-to-run bit-identical.  Enqueue-only, allocation-free.  ALG_EINVAL before anything is launched: a null or not
+ * 16-byte aligned pointer; batch or heads < 1; head_dim not 64 / 128; group not 2 / 4 / 8; S < group; a stride that is not a
+ * multiple of 8, a row stride below what is stated above, a batch stride (batch > 1) that does not hold a sample. */
+int alg_attn_pool_k(const void* src, int64_t src_bstride, int64_t src_rstride, void* dst, int64_t dst_bstride, int64_t dst_rstride,
+                    int batch, int heads, int head_dim, int S, int group, void* stream);
+int alg_attn_pool_vt(const void* src, int64_t src_bstride, int64_t src_rstride, void* dst, int64_t dst_bstride, int64_t dst_rstride,
+                     int batch, int heads, int head_dim, int S, int group, void* stream);
+
+/* alg_attn_merge_lse with far_lse_shift (finite) added to every far log-sum-exp before the merge: far keys that each stand for
+ * 2^far_lse_shift keys (the pooled keys above: log2 group).  An lse_far of -inf stays -inf: the row of o keeps its bits.  With
+ * far_lse_shift == 0 the result is alg_attn_merge_lse's bit for bit.  lse_far itself is not written. */
+int alg_attn_merge_lse_shift(void* o, const float* lse, const void* o_far, const float* lse_far, int batch, int heads, int head_dim,
+                             int Sq, int64_t o_bstride, int64_t o_rstride, int64_t far_bstride, int64_t far_rstride,
+                             float far_lse_shift, float* lse_out, void* stream);
+
 /* LoRA merge at load time (an extension; the reference pipelines inherit diffusers' LoRA loader mixins; alg_amd/lora.py merges
  * the adapters into the state dict BEFORE a transformer is built from it, so no forward path knows about them):
  *   t[n, r]   = double(scale[r]) * double(B[n, r])                exact
